@@ -18,7 +18,10 @@ Arithmetic: --arithmetic default (the default) renders in the arithmetic of the 
 produces (PTMI_FLAG_DEFAULT_ARITHMETIC: images equal that kernel's bit for bit, tests/test_reference_default_gpu.py);
 --arithmetic strict is the other bit-exact mode (the reference's strict build).
 
-Prints ONE JSON line on rank 0.  Extra objects:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the line; everything else it
+can measure takes --full.  --dump-outputs DIR writes the framebuffer rank 0 holds after the last timed step (what a caller of
+the timed path receives) as DIR/color.npy and DIR/sample_count.npy (float32; a fixed sample of pixels, DIR/pixel_index.npy,
+where the image exceeds 64 MB).  Extra objects, with --full only:
   "roofline"          the ceiling that BINDS this kernel (bound / frac <= 1), from the PMC passes of this command committed
                       under profiles/ (used only if they were taken on this very kernel source) and this run's launch time
                       (HIP events on the kernel's stream); beside it "hbm_measured" (memory-side traffic / time) and
@@ -109,10 +112,15 @@ def main():
     ap.add_argument("--arithmetic", choices=["default", "strict"], default="default",
                     help="default = the arithmetic of the reference's own build (OpenCL default: what its build line produces); "
                          "strict = its -ffp-contract=off -cl-fp32-correctly-rounded-divide-sqrt build.  Both bit-exact modes")
-    ap.add_argument("--no-reference-kernel", action="store_true", help="skip timing the reference's own kernel beside (N=1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline, the reference's kernel, the reference-style per-image "
+                         "loop and the CPU baseline (the --no-* options below leave single legs out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the framebuffer of the last timed step to DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-reference-kernel", action="store_true", help="with --full: skip timing the reference's own kernel beside (N=1 only)")
     ap.add_argument("--scheduler-stats", action="store_true", help="also report wave-scheduler statistics (costs ~1 %)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-boundary", action="store_true", help="skip the reference-style per-image loop (N=1 only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-boundary", action="store_true", help="with --full: skip the reference-style per-image loop (N=1 only)")
     ap.add_argument("--no-histograms", action="store_true",
                     help="skip the reference's three per-path statistics atomics (FullKernel.cl:1319-1331); default: keep them")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -121,6 +129,8 @@ def main():
     ap.add_argument("--cpu-rows", type=int, default=0, help="image rows the CPU baseline renders (0 = auto)")
     ap.add_argument("--cpu-spp", type=int, default=0, help="iterations the CPU baseline renders (0 = auto: 10-30 s of CPU work)")
     args = ap.parse_args()
+    if args.steps < 1 and args.total_spp <= 0:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
     import torch
@@ -233,41 +243,8 @@ def main():
         spp_done = (args.warmup + args.steps) * B * (1 if strong else world)
         assert np.isfinite(color).all() and float(count.min()) == float(spp_done) == float(count.max()), \
             f"sample count {count.min()}..{count.max()} != {spp_done}"
-        tex_frac = textured_hit_fraction(pt, scene, W, H, D, local_rank, flags) if args.kernel == "wavefront" else 0.0
-        n_texel = tex_frac * delta["surface_hits"]
-        b_alg = algorithmic_bytes(delta, n_pix, launches, n_texel)
-        avg_launch_s = kernel_ms / 1e3 / max(launches, 1)
-        achieved = b_alg / max(launches, 1) / avg_launch_s / 1e9
-        records_per_launch = (delta["box_tests"] / 2 + delta["triangle_tests"]) / max(launches, 1)
-        model = {"achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac_of_hbm_peak": achieved / HBM_PEAK_GBS,
-                 "algorithmic_bytes_per_launch": b_alg / max(launches, 1),
-                 "textured_hits_per_surface_hit": tex_frac, "texel_lookups_per_launch": n_texel / max(launches, 1),
-                 "note": "SURVEY 8d ALGORITHMIC bytes (32 B per box test, 48 B per triangle test, 96 B per surface hit, 24 B of uv + "
-                         "4 B of texel per hit on a textured material, 40 B per pixel flush) / launch time: what the traversal must read, nearly all of it served by the L1s / L2s / "
-                         "Infinity Cache (hbm_measured is what reaches memory) - a model of the work, NOT a ceiling of this kernel"}
-        roof = {"bound": None, "achieved": None, "peak": None, "unit": None, "frac": None, "traffic": None,
-                "kernel": "render_wavefront_kernel" if args.kernel == "wavefront" else "render_kernel",
-                "arithmetic": args.arithmetic,
-                "launches": launches, "avg_launch_ms": avg_launch_s * 1e3,
-                "box_tests_per_path": delta["box_tests"] / max(delta["paths"], 1),
-                "triangle_tests_per_path": delta["triangle_tests"] / max(delta["paths"], 1),
-                "record_fetches_per_s": records_per_launch / avg_launch_s,
-                "hbm_algorithmic_model": model}
-        pmc = committed_pmc(args, W, H, D, B)
-        if pmc:
-            roof.update(binding_ceilings(pmc, avg_launch_s, records_per_launch))
-        else:
-            # no PMC passes of THIS kernel source on this workload: the one ceiling that can be priced from this run alone -
-            # 64-byte record gathers against what the chip's L1s deliver for that access pattern (tools/microbench/record_fetch)
-            rate = records_per_launch / avg_launch_s * L1_ACCESSES_PER_RECORD
-            roof.update({"bound": "l1_accesses (estimated)", "achieved": rate / 1e9, "peak": L1_ACCESS_RATE / 1e9, "unit": "G accesses/s",
-                         "frac": rate / L1_ACCESS_RATE, "ceiling": L1_CEILING_SOURCE,
-                         "pmc_fallback": "LOUD: no PMC passes of this kernel source are committed for this workload - the counter-backed "
-                                         "table (binding, traffic, hbm_measured) is missing from this line; run tools/profile_round.sh",
-                         "note": "no committed PMC passes match this kernel source + workload + arithmetic (profiles/r04_pmc_*.json): the L1 "
-                                 f"access rate is ESTIMATED as records fetched x {L1_ACCESSES_PER_RECORD} accesses per record (measured for this "
-                                 "kernel on the 1M-triangle workload) against the gather ceiling of tools/microbench/record_fetch; run "
-                                 "tools/profile_round.sh for the measured table"})
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, color, count)
         out = {
             "metric": "Msamples/s (paths x bounces) at 1920x1080",
             "value": total["segments"] / elapsed / 1e6,
@@ -296,8 +273,9 @@ def main():
             "segments_per_path": total["segments"] / max(total["paths"], 1),
             # paths whose ray was not a number at some bounce: given up by the launch and traced again by the literal loops (rank 0)
             "paths_retraced": sched["paths_retraced"],
-            "roofline": roof,
         }
+        if args.full:
+            out["roofline"] = roofline_leg(pt, scene, args, W, H, D, B, local_rank, flags, delta, kernel_ms, launches)
         if sched["trips_node"]:
             out["wave_scheduler"] = {k: round(sched["lanes_" + k] / (64.0 * sched["trips_" + k]), 3) if sched["trips_" + k] else None
                                      for k in ("node", "triangle", "path")}
@@ -307,9 +285,9 @@ def main():
             # raw counts per launch (tools/valu_cost_model.py weights the static instruction mix of each trip kind with them)
             out["wave_scheduler"]["trips_per_launch"] = {k: sched["trips_" + k] / max(launches + args.warmup, 1) for k in ("node", "triangle", "path")}
             out["wave_scheduler"]["leaf_item_violations"] = sched["leaf_item_violations"]
-        if world == 1 and not args.no_boundary:
+        if args.full and world == 1 and not args.no_boundary:
             out["boundary"] = boundary_loop(pt, scene, W, H, D, local_rank, flags, out["value"])
-        if world == 1 and not args.no_reference_kernel and args.kernel == "wavefront":
+        if args.full and world == 1 and not args.no_reference_kernel and args.kernel == "wavefront":
             ref = reference_kernel_leg(pt, scene, args, W, H, D, local_rank, flags, out["Mpaths/s"])
             if ref:
                 out["reference_kernel"] = ref
@@ -323,13 +301,70 @@ def main():
             seg_per_path = out["segments_per_path"]
             out["reference_kernel"]["ratio_per_image_protocol_shim_default"] = (
                 out["boundary"]["per_image_burst16_Msamples/s"] / seg_per_path / out["reference_kernel"]["Mpaths/s"])
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(scene, W, H, D, args.cpu_rows, args.cpu_spp, args.arithmetic == "default")
         print(json.dumps(out), flush=True)
 
     if world > 1:
         dist.destroy_process_group()
 
+
+def dump_outputs(folder, color, count, budget=64 << 20):
+    """The framebuffer of the last timed step as DIR/color.npy (H x W x 4) and DIR/sample_count.npy (H x W), float32.  An
+    image above `budget` bytes is cut to a fixed sample of pixels (seed 0, ascending flat indices in DIR/pixel_index.npy):
+    the same pixels in every run with the same arguments."""
+    import numpy as np
+    os.makedirs(folder, exist_ok=True)
+    n_pix = count.size
+    arrays = {"color": color, "sample_count": count}
+    if n_pix * 20 > budget - 4096:  # 16 B of color + 4 B of count per pixel; 4 KB for the .npy headers
+        k = (budget - 4096) // 28  # + 8 B of float64 index per sampled pixel
+        idx = np.sort(np.random.default_rng(0).choice(n_pix, k, replace=False))
+        arrays = {"color": color.reshape(n_pix, 4)[idx], "sample_count": count.reshape(n_pix)[idx],
+                  "pixel_index": idx.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(folder, name + ".npy"), np.ascontiguousarray(a))
+
+
+def roofline_leg(pt, scene, args, W, H, D, B, device, flags, delta, kernel_ms, launches):
+    """The ceiling that binds this kernel in the timed steps (--full: the textured-hit fraction takes a run of its own)."""
+    n_pix = W * H
+    tex_frac = textured_hit_fraction(pt, scene, W, H, D, device, flags) if args.kernel == "wavefront" else 0.0
+    n_texel = tex_frac * delta["surface_hits"]
+    b_alg = algorithmic_bytes(delta, n_pix, launches, n_texel)
+    avg_launch_s = kernel_ms / 1e3 / max(launches, 1)
+    achieved = b_alg / max(launches, 1) / avg_launch_s / 1e9
+    records_per_launch = (delta["box_tests"] / 2 + delta["triangle_tests"]) / max(launches, 1)
+    model = {"achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac_of_hbm_peak": achieved / HBM_PEAK_GBS,
+             "algorithmic_bytes_per_launch": b_alg / max(launches, 1),
+             "textured_hits_per_surface_hit": tex_frac, "texel_lookups_per_launch": n_texel / max(launches, 1),
+             "note": "SURVEY 8d ALGORITHMIC bytes (32 B per box test, 48 B per triangle test, 96 B per surface hit, 24 B of uv + "
+                     "4 B of texel per hit on a textured material, 40 B per pixel flush) / launch time: what the traversal must read, nearly all of it served by the L1s / L2s / "
+                     "Infinity Cache (hbm_measured is what reaches memory) - a model of the work, NOT a ceiling of this kernel"}
+    roof = {"bound": None, "achieved": None, "peak": None, "unit": None, "frac": None, "traffic": None,
+            "kernel": "render_wavefront_kernel" if args.kernel == "wavefront" else "render_kernel",
+            "arithmetic": args.arithmetic,
+            "launches": launches, "avg_launch_ms": avg_launch_s * 1e3,
+            "box_tests_per_path": delta["box_tests"] / max(delta["paths"], 1),
+            "triangle_tests_per_path": delta["triangle_tests"] / max(delta["paths"], 1),
+            "record_fetches_per_s": records_per_launch / avg_launch_s,
+            "hbm_algorithmic_model": model}
+    pmc = committed_pmc(args, W, H, D, B)
+    if pmc:
+        roof.update(binding_ceilings(pmc, avg_launch_s, records_per_launch))
+    else:
+        # no PMC passes of THIS kernel source on this workload: the one ceiling that can be priced from this run alone -
+        # 64-byte record gathers against what the chip's L1s deliver for that access pattern (tools/microbench/record_fetch)
+        rate = records_per_launch / avg_launch_s * L1_ACCESSES_PER_RECORD
+        roof.update({"bound": "l1_accesses (estimated)", "achieved": rate / 1e9, "peak": L1_ACCESS_RATE / 1e9, "unit": "G accesses/s",
+                     "frac": rate / L1_ACCESS_RATE, "ceiling": L1_CEILING_SOURCE,
+                     "pmc_fallback": "LOUD: no PMC passes of this kernel source are committed for this workload - the counter-backed "
+                                     "table (binding, traffic, hbm_measured) is missing from this line; run tools/profile_round.sh",
+                     "note": "no committed PMC passes match this kernel source + workload + arithmetic (profiles/r04_pmc_*.json): the L1 "
+                             f"access rate is ESTIMATED as records fetched x {L1_ACCESSES_PER_RECORD} accesses per record (measured for this "
+                             "kernel on the 1M-triangle workload) against the gather ceiling of tools/microbench/record_fetch; run "
+                             "tools/profile_round.sh for the measured table"})
+    return roof
 
 def workload_name(scene):
     return {"tris1m": "BASELINE configs[2]: synthetic random-triangle scene (numpy MT19937 seed 12345)",

@@ -2,8 +2,10 @@
 
 * where oracle/_ref/libref_bvh.so exists (the reference's PathTracer_BVH.cpp compiled UNMODIFIED) every
   field the reference writes must be equal, and the triangle array must be reordered identically;
+* elsewhere the same fields, hashed, against the digests of the reference builder's own trees
+  (tests/golden/bvh_reference_trees.json);
 * everywhere: committed digests of trees that were checked against the reference when they were made
-  (tests/golden/bvh_digests.json, generator: this file run as a script).
+  (tests/golden/bvh_digests.json).  Generator of both: this file run as a script where libref_bvh.so exists.
 """
 import hashlib
 import json
@@ -18,6 +20,7 @@ import oracle_ffi as O
 from opencl_pathtracer_amd import scenes, bvh_create, structs as S, PtmiError
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bvh_digests.json")
+REF_TREES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bvh_reference_trees.json")
 NODE_FIELDS = ["cutAxis", "triangleStartIndex", "nbTriangles", "son1Id", "son2Id", "isLeaf"]
 CASES = [("cornell", 64, 48), ("matmix", 96, 96), ("tris20k", 96, 64), ("tris1m", 160, 90)]
 
@@ -55,16 +58,46 @@ def assert_same_tree(ref_nodes, ref_tris, ref_depth, sc):
             assert np.array_equal(bits(a), bits(b)), f
 
 
+def tree_digest(nodes, tris, depth):
+    """SHA-256 over everything assert_same_tree compares, field by field (a record's padding bytes are left out)."""
+    h = hashlib.sha256()
+    h.update(np.array([len(nodes), depth], np.int64).tobytes())
+    for f in NODE_FIELDS:
+        h.update(np.ascontiguousarray(nodes[f]).tobytes())
+    for bb in ("trianglesAABB", "centroidsAABB"):
+        for f in ("pMin", "pMax", "centroid", "isEmpty"):
+            h.update(np.ascontiguousarray(nodes[bb][f]).tobytes())
+    h.update(np.ascontiguousarray(nodes["comments"][nodes["isLeaf"] != 0]).tobytes())
+    for f in S.Triangle.names:
+        a = tris[f]
+        for g in a.dtype.names or (None,):
+            h.update(np.ascontiguousarray(a if g is None else a[g]).tobytes())
+    return h.hexdigest()
+
+
+def reference_tree(key, triangulation):
+    """The reference's BVH_Create on `triangulation` (call it before the product's builder reorders the triangles): its tree
+    where oracle/_ref/libref_bvh.so exists, elsewhere the digest of that tree stored in tests/golden/bvh_reference_trees.json."""
+    if O.have_ref_bvh():
+        return O.ref_bvh_create(triangulation)
+    return json.load(open(REF_TREES))[key]
+
+
+def assert_same_as_reference(ref, sc):
+    if isinstance(ref, str):
+        assert tree_digest(sc.bvh, sc.triangulation, sc.bvhMaxDepth) == ref
+    else:
+        assert_same_tree(*ref, sc)
+
+
 @pytest.mark.parametrize("name,w,h", CASES)
 def test_matches_reference_builder(name, w, h, built):
-    if not O.have_ref_bvh():
-        (O.missing_reference if os.path.isdir("/root/reference") else pytest.skip)("oracle/_ref/libref_bvh.so not present")
     if name == "tris1m" and os.environ.get("PTMI_SKIP_SLOW"):
         pytest.skip("slow")
     sc = scenes.build(name, w, h)
-    ref_nodes, ref_tris, ref_depth = O.ref_bvh_create(sc.triangulation)
+    ref = reference_tree(f"{name}_{w}x{h}", sc.triangulation)
     bvh_create(sc)
-    assert_same_tree(ref_nodes, ref_tris, ref_depth, sc)
+    assert_same_as_reference(ref, sc)
 
 
 @pytest.mark.parametrize("name,w,h", CASES)
@@ -86,6 +119,7 @@ def test_small_and_ragged_sizes(n, built):
     tris = _random_soup(n, 100 + n)
     sc = scenes.cornell_box(8, 8)
     sc.triangulation = tris
+    ref = reference_tree(f"soup{n}", tris)
     bvh_create(sc)
     assert sc.bvh["isLeaf"][0] == (1 if n <= 4 else 0) or n > 4
     leaves = sc.bvh[sc.bvh["isLeaf"] != 0]
@@ -94,24 +128,26 @@ def test_small_and_ragged_sizes(n, built):
     for l in leaves:
         covered[l["triangleStartIndex"]:l["triangleStartIndex"] + l["nbTriangles"]] = True
     assert covered.all() and sorted(sc.triangulation["id"].tolist()) == list(range(n))
-    if O.have_ref_bvh():
-        ref_nodes, ref_tris, ref_depth = O.ref_bvh_create(tris)
-        assert_same_tree(ref_nodes, ref_tris, ref_depth, sc)
+    assert_same_as_reference(ref, sc)
+
+
+def _coincident_stack():
+    rs = np.random.RandomState(7)
+    base = rs.uniform(-0.2, 0.2, (1, 3, 3)).astype(np.float32)
+    v = np.repeat(base, 40, axis=0)
+    return scenes.triangle_create(v[:, 0], v[:, 1], v[:, 2])
 
 
 def test_coincident_centroids_stop_on_min_diagonal(built):
     """All centroids (nearly) equal: the reference stops with NODE_LEAF_MIN_DIAG and a big leaf (BVH.cpp:142-149)."""
-    rs = np.random.RandomState(7)
-    base = rs.uniform(-0.2, 0.2, (1, 3, 3)).astype(np.float32)
-    v = np.repeat(base, 40, axis=0)
-    tris = scenes.triangle_create(v[:, 0], v[:, 1], v[:, 2])
+    tris = _coincident_stack()
     sc = scenes.cornell_box(8, 8)
     sc.triangulation = tris
+    ref = reference_tree("coincident40", tris)
     bvh_create(sc)
     assert len(sc.bvh) == 1 and sc.bvh["isLeaf"][0] and sc.bvh["nbTriangles"][0] == 40
     assert sc.bvh["comments"][0] == S.NODE_LEAF_MIN_DIAG
-    if O.have_ref_bvh():
-        assert_same_tree(*O.ref_bvh_create(tris), sc)
+    assert_same_as_reference(ref, sc)
 
 
 @pytest.mark.parametrize("seed", range(0, 60, 3))
@@ -121,15 +157,13 @@ def test_fuzzed_scenes_match_reference_builder(seed, built):
     ones (w components that are not 1 enter the boxes' fourth component): the same tree as the reference's own builder,
     field for field, and the same triangle order."""
     import warnings
-    if not O.have_ref_bvh():
-        (O.missing_reference if os.path.isdir("/root/reference") else pytest.skip)("oracle/_ref/libref_bvh.so not present")
     for suffix in ("", "h", "r", "hr"):
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
             sc = scenes.build(f"fuzz{seed}{suffix}_l1", 64, 64)
-        ref_nodes, ref_tris, ref_depth = O.ref_bvh_create(sc.triangulation)
+        ref = reference_tree(f"fuzz{seed}{suffix}_l1", sc.triangulation)
         bvh_create(sc)
-        assert_same_tree(ref_nodes, ref_tris, ref_depth, sc)
+        assert_same_as_reference(ref, sc)
 
 
 @pytest.mark.parametrize("value", [np.nan, np.inf, -np.inf, 3e38])
@@ -222,3 +256,23 @@ if __name__ == "__main__":  # regenerate the digests (only meaningful where the 
         out[name] = digest(sc)
         print(name, out[name])
     json.dump(out, open(GOLDEN, "w"), indent=1, sort_keys=True)
+    if O.have_ref_bvh():  # the reference builder's own trees, hashed (each one checked against the product's first)
+        import warnings
+        inputs = [(f"{name}_{w}x{h}", lambda name=name, w=w, h=h: scenes.build(name, w, h).triangulation) for name, w, h in CASES]
+        inputs += [(f"soup{n}", lambda n=n: _random_soup(n, 100 + n)) for n in (1, 2, 4, 5, 9, 33, 257)]
+        inputs += [("coincident40", _coincident_stack)]
+        inputs += [(f"fuzz{s}{x}_l1", lambda s=s, x=x: scenes.build(f"fuzz{s}{x}_l1", 64, 64).triangulation)
+                   for s in range(0, 60, 3) for x in ("", "h", "r", "hr")]
+        trees = {}
+        for key, make in inputs:
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                tris = make()
+            ref = O.ref_bvh_create(tris)
+            sc = scenes.cornell_box(8, 8)
+            sc.triangulation = tris
+            bvh_create(sc)
+            assert_same_tree(*ref, sc)
+            trees[key] = tree_digest(*ref)
+            assert tree_digest(sc.bvh, sc.triangulation, sc.bvhMaxDepth) == trees[key], key
+        json.dump(trees, open(REF_TREES, "w"), indent=1, sort_keys=True)

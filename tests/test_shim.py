@@ -63,16 +63,30 @@ def fnv(a):
     return h
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
 def test_mirror_header_layout_equals_reference(tmp_path):
-    """include/pathtracer_backend.hpp must be binary-identical to the reference's GlobalVars and scene structs,
-    and PathTracer_HIP.cpp must compile against the reference's OWN headers (the maintainer's build)."""
-    fields = ["window", "importer", "cameraDirection", "cameraRight", "cameraUp", "cameraPosition", "bvh", "triangulation",
+    """include/pathtracer_backend.hpp must be binary-identical to the reference's GlobalVars and scene structs: against their
+    layout as stored in tests/golden/backend_layout_reference.json (tests/golden/make_reference_layout.py), and where the
+    reference tree is present against its headers, and PathTracer_HIP.cpp must compile against the reference's OWN headers
+    (the maintainer's build)."""
+    import json
+    fields =["window", "importer", "cameraDirection", "cameraRight", "cameraUp", "cameraPosition", "bvh", "triangulation",
               "lights", "materiaux", "textures", "texturesData", "bvhSize", "triangulationSize", "lightsSize",
               "materiauxSize", "texturesSize", "texturesDataSize", "bvhMaxDepth", "sampler", "printLogInfos",
               "superSampling", "sky", "imageWidth", "imageHeight", "imageSize", "rayMaxDepth", "imageColor", "imageRayNb",
               "rayDepths", "rayIntersectedBBx", "rayIntersectedTri"]
-    checks = "\n".join(f'static_assert(offsetof(PathTracerNS::GlobalVars, {f}) == offsetof(PtmiMirrorNS::GlobalVars, {f}), "{f}");'
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "backend_layout_reference.json")))
+    gv, size = golden["GlobalVars"], golden["sizeof"]
+    assert set(gv) == set(fields) | {"sizeof"} and set(size) == {"Triangle", "Node", "Material", "Light", "Sky", "Texture"}
+    mirror = tmp_path / "mirror.cpp"
+    mirror.write_text('#include <cstddef>\n#include "pathtracer_backend.hpp"\n'
+                      f'static_assert(sizeof(PathTracerNS::GlobalVars) == {gv["sizeof"]}, "GlobalVars size");\n'
+                      + "".join(f'static_assert(sizeof(ptmi_{s.lower()}) == {n}, "{s}");\n' for s, n in size.items())
+                      + "".join(f'static_assert(offsetof(PathTracerNS::GlobalVars, {f}) == {gv[f]}, "{f}");\n' for f in fields)
+                      + "int main(){return 0;}\n")
+    subprocess.run([CLANGXX, "-std=c++14", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(mirror)], check=True)
+    if not os.path.isdir(REF):
+        return
+    checks ="\n".join(f'static_assert(offsetof(PathTracerNS::GlobalVars, {f}) == offsetof(PtmiMirrorNS::GlobalVars, {f}), "{f}");'
                        for f in fields)
     src = tmp_path / "layout.cpp"
     src.write_text('#include <cstddef>\n#include <climits>\n#include <cstring>\n#include "PathTracer_Structs.h"\n'

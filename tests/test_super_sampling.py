@@ -26,12 +26,15 @@ def test_generated_table():
     assert abs(t[1000] - 898.912447) < 1e-3 and abs(t[1] - 0.000157) < 1e-6
 
 
-@pytest.mark.skipif(not os.path.exists(REF_TABLE), reason="reference tree not present")
 def test_table_equals_the_reference_file():
-    txt = open(REF_TABLE).read()
-    body = txt[txt.index("{") + 1:txt.rindex("}")]
-    ref = np.array([float(v.strip().rstrip("f")) for v in body.split(",") if v.strip()], np.float32)
-    assert np.array_equal(ref, product_table())
+    """Against the reference's X2inv.cl as stored in tests/golden (tests/golden/make_reference_layout.py), and against the
+    file itself where the reference tree is present."""
+    ref = np.load(os.path.join(ROOT, "tests", "golden", "x2inv_reference.npy"))
+    assert ref.dtype == np.float32 and np.array_equal(ref, product_table())
+    if os.path.exists(REF_TABLE):
+        txt = open(REF_TABLE).read()
+        body = txt[txt.index("{") + 1:txt.rindex("}")]
+        assert np.array_equal(np.array([float(v.strip().rstrip("f")) for v in body.split(",") if v.strip()], np.float32), ref)
 
 
 def test_oracle_skips_converged_pixels(scene_factory):

@@ -12,10 +12,10 @@ run() { name=$1; shift; echo "== $name: bench.py $*"; python bench.py "$@" > gpu
         python -c "import json,sys; d=json.load(open('gpurun_out/r04_bench_$name.json')); print('$name', round(d['value'],1), d['unit'], '| roofline frac', round(d['roofline']['frac'],3), '| cpu', d.get('cpu_baseline',{}).get('value'), '| boundary', d.get('boundary',{}).get('per_image_vs_batched'))"; }
 want="$@"; [ -z "$want" ] && want="config0 config1 config2 config4 matmix tris4m"
 for n in $want; do case $n in
-  config0) run config0_cornell_512_d4_64spp --scene cornell --width 512 --height 512 --depth 4 --steps 2 --warmup 1 --cpu-spp 64 --cpu-rows 512;;
-  config1) run config1_cornell_1080p_d8_1024spp --scene cornell --depth 8 --steps 64 --warmup 0;;
-  config2) run config2_tris1m_1080p_d10_256spp --steps 16 --warmup 0;;
-  config4) run config4_standin_mayalike_4k_d16 --scene mayalike --width 3840 --height 2160 --depth 16 --spp-per-step 25 --steps 4 --warmup 1;;
-  matmix)  run matmix_4k_d16 --scene matmix --width 3840 --height 2160 --depth 16 --spp-per-step 25 --steps 4 --warmup 1;;
-  tris4m)  run tris4m_1080p_d10 --scene tris4m --steps 4 --warmup 1;;
+  config0) run config0_cornell_512_d4_64spp --full --scene cornell --width 512 --height 512 --depth 4 --steps 2 --warmup 1 --cpu-spp 64 --cpu-rows 512;;
+  config1) run config1_cornell_1080p_d8_1024spp --full --scene cornell --depth 8 --steps 64 --warmup 0;;
+  config2) run config2_tris1m_1080p_d10_256spp --full --steps 16 --warmup 0;;
+  config4) run config4_standin_mayalike_4k_d16 --full --scene mayalike --width 3840 --height 2160 --depth 16 --spp-per-step 25 --steps 4 --warmup 1;;
+  matmix)  run matmix_4k_d16 --full --scene matmix --width 3840 --height 2160 --depth 16 --spp-per-step 25 --steps 4 --warmup 1;;
+  tris4m)  run tris4m_1080p_d10 --full --scene tris4m --steps 4 --warmup 1;;
 esac; done

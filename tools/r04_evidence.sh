@@ -29,12 +29,12 @@ PY
 }
 case $part in
   tris1m)
-    one_scene r04_tris1m ""
-    echo "== strict arithmetic"; python bench.py --steps 6 --warmup 1 --arithmetic strict --no-cpu-baseline --no-boundary > gpurun_out/r04_tris1m_bench_strict.json 2> gpurun_out/r04_tris1m_bench_strict.err;;
+    one_scene r04_tris1m "" --full
+    echo "== strict arithmetic"; python bench.py --full --steps 6 --warmup 1 --arithmetic strict --no-cpu-baseline --no-boundary 2>&1 | tail -1;;
   mayalike)
-    one_scene r04_mayalike "--general --narrow" --scene mayalike --width 3840 --height 2160 --depth 16 --spp-per-step 25;;
+    one_scene r04_mayalike "--general --narrow" --full --scene mayalike --width 3840 --height 2160 --depth 16 --spp-per-step 25;;
   cornell)
-    one_scene r04_cornell "" --scene cornell --depth 8;;
+    one_scene r04_cornell "" --full --scene cornell --depth 8;;
   configs)
     bash tools/bench_configs.sh config0 config1 matmix tris4m
     echo "== north star at full sizes"; python tools/north_star_full_size.py tris1m cornell mayalike 2>&1 | grep -v "^{" | tail -8;;
