@@ -38,7 +38,7 @@ def main():
         scene = obj_import.scene_from_obj(args.obj, w, h)
     else:
         scene = pt.scenes.build(args.scene, w, h)
-    scene = pt.bvh_create(scene)
+    scene = pt.bvh_create(scene, device=args.device)  # the tree on the device it renders on (the host's tree, byte for byte)
     flags = 0 if args.strict_arithmetic else pt.backend.FLAG_DEFAULT_ARITHMETIC  # default: the reference kernel's own pixels
     be = pt.Backend().setup_context(w, h, args.depth, scene.lightsSize, pt.structs.JITTERED, device=args.device, flags=flags)
     be.initialize_memory(scene)

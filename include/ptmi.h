@@ -330,6 +330,42 @@ int ptmi_validate_scene(const ptmi_config* config, const ptmi_scene* scene);
 int ptmi_bvh_create(ptmi_triangle* triangulation, uint32_t triangulation_size, ptmi_node* bvh,
                     uint32_t* bvh_size, uint32_t* bvh_max_depth);
 
+/* ptmi_bvh_create on device `device`: the same tree and the same reordering of `triangulation`, byte for byte, with the
+ * same in/out contract and the same status codes and messages.  The caller's host arrays go in and come out; the call
+ * uses a stream and workspace of its own, leaves the calling thread's current device as it found it and does not touch
+ * any context.  PTMI_ERR_NO_DEVICE (arrays untouched) when `device` is not a HIP device: no CPU fallback, the caller
+ * chooses; PTMI_ERR_HIP when a runtime call fails (arrays untouched).
+ *
+ * The device builds the tree level by level.  The host builder keeps per-axis state from node to node: at a node where an
+ * axis is skipped (centroid extent < 1e-3) the axis keeps the bin scans of the node built before it in depth-first
+ * order, and if the SAH then chooses that axis (possible only when every other candidate cost is >= INT_MAX - large
+ * flat walls) the split is made from that stale state.  A level-synchronous build cannot reproduce it, so the call then
+ * discards the device work and runs ptmi_bvh_create on the caller's unmodified arrays (PTMI_BVH_FALLBACK_STALE_AXIS).
+ * Likewise for every condition the host builder turns into an error (a bin out of range, a split with an empty side,
+ * a tree deeper than 8 * PTMI_BVH_MAX_DEPTH): the host builder runs and its status and message are returned
+ * (PTMI_BVH_FALLBACK_HOST_ERROR), and for records whose boxes the device does not fold (a NaN w, a box marked empty:
+ * PTMI_BVH_FALLBACK_RECORDS).  Nothing is written to the caller's arrays before the device build has succeeded.
+ * `info` may be NULL. */
+enum {
+    PTMI_BVH_FALLBACK_NONE = 0,
+    PTMI_BVH_FALLBACK_STALE_AXIS = 1,
+    PTMI_BVH_FALLBACK_HOST_ERROR = 2,
+    PTMI_BVH_FALLBACK_RECORDS = 3
+};
+typedef struct ptmi_bvh_build_info {
+    uint32_t struct_size;     /* set by the library: sizeof(ptmi_bvh_build_info) */
+    uint32_t built_on_device; /* 1: the device built the tree; 0: the host builder did (see fallback) */
+    uint32_t fallback;        /* PTMI_BVH_FALLBACK_* */
+    uint32_t levels;          /* level passes the device ran */
+    double device_ms;         /* device work between the upload and the download (HIP events) */
+    double total_ms;          /* the whole call, copies and the reordering of the triangles included */
+    double upload_ms, download_ms, permute_ms; /* host -> device; device -> host; reordering the caller's triangles */
+    uint64_t workspace_bytes; /* device memory the call allocated */
+} ptmi_bvh_build_info;
+
+int ptmi_bvh_create_device(int32_t device, ptmi_triangle* triangulation, uint32_t triangulation_size, ptmi_node* bvh,
+                           uint32_t* bvh_size, uint32_t* bvh_max_depth, ptmi_bvh_build_info* info);
+
 #ifdef __cplusplus
 }
 #endif

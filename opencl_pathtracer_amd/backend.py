@@ -68,6 +68,19 @@ class Counters(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class BvhBuildInfo(C.Structure):
+    """ptmi_bvh_build_info: what ptmi_bvh_create_device did (fallback: 0 none, 1 stale axis, 2 host error, 3 records)."""
+    _fields_ = [("struct_size", C.c_uint32), ("built_on_device", C.c_uint32), ("fallback", C.c_uint32), ("levels", C.c_uint32),
+                ("device_ms", C.c_double), ("total_ms", C.c_double), ("upload_ms", C.c_double), ("download_ms", C.c_double),
+                ("permute_ms", C.c_double), ("workspace_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+BVH_FALLBACK_NONE, BVH_FALLBACK_STALE_AXIS, BVH_FALLBACK_HOST_ERROR, BVH_FALLBACK_RECORDS = 0, 1, 2, 3
+
+
 class SchedulerStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("trips_node", "lanes_node", "trips_triangle", "lanes_triangle", "trips_path",
                                          "lanes_path", "cycles_path", "cycles_loop", "leaf_item_violations", "paths_retraced", "textured_hits", "workgroup_lanes",
@@ -101,7 +114,8 @@ ABI_SYMBOLS = ["ptmi_setup_context", "ptmi_initialize_memory", "ptmi_render", "p
                "ptmi_kernel_time", "ptmi_reduce_path",
                "ptmi_set_stream", "ptmi_device_accumulators", "ptmi_bind_accumulators", "ptmi_read_variance",
                "ptmi_device_variance", "ptmi_last_error",
-               "ptmi_abi_version", "ptmi_device_count", "ptmi_device_share", "ptmi_bvh_create"]
+               "ptmi_abi_version", "ptmi_device_count", "ptmi_device_share", "ptmi_bvh_create",
+               "ptmi_bvh_create_device"]
 
 
 def library_path():
@@ -150,6 +164,7 @@ def load_library():
     lib.ptmi_last_error.argtypes = [vp]
     lib.ptmi_last_error.restype = C.c_char_p
     lib.ptmi_bvh_create.argtypes = [vp, u32, vp, C.POINTER(u32), C.POINTER(u32)]
+    lib.ptmi_bvh_create_device.argtypes = [C.c_int32, vp, u32, vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(BvhBuildInfo)]
     lib.ptmi_device_share.argtypes = [u32, u32, u32, u32, C.POINTER(u32), C.POINTER(u32)]
     lib.ptmi_device_share.restype = None
     _lib = lib
@@ -173,9 +188,11 @@ def device_share(first_iteration, n_iterations, k, n_devices):
     return f.value, n.value
 
 
-def bvh_create(scene):
+def bvh_create(scene, device=None):
     """``BVH_Create(globalVars)`` (PathTracer_BVH.cpp:12-37): builds ``scene.bvh`` and reorders
-    ``scene.triangulation`` in place, exactly like the reference (host code, no GPU needed)."""
+    ``scene.triangulation`` in place, exactly like the reference.  ``device=None``: on the host (no GPU needed);
+    an ordinal: ``ptmi_bvh_create_device`` on that HIP device - the same bytes - with its ``BvhBuildInfo`` in
+    ``scene.bvh_build_info`` (whether the device built the tree or handed the scene to the host builder, and timings)."""
     lib = load_library()
     tris = np.ascontiguousarray(scene.triangulation)
     if tris.dtype != S.Triangle:
@@ -183,7 +200,12 @@ def bvh_create(scene):
     n = len(tris)
     nodes = np.zeros(max(2 * n - 1, 1), dtype=S.Node)
     size, depth = C.c_uint32(0), C.c_uint32(0)
-    rc = lib.ptmi_bvh_create(_ptr(tris), n, _ptr(nodes), C.byref(size), C.byref(depth))
+    if device is None:
+        rc = lib.ptmi_bvh_create(_ptr(tris), n, _ptr(nodes), C.byref(size), C.byref(depth))
+    else:
+        info = BvhBuildInfo()
+        rc = lib.ptmi_bvh_create_device(int(device), _ptr(tris), n, _ptr(nodes), C.byref(size), C.byref(depth), C.byref(info))
+        scene.bvh_build_info = info
     if rc:
         raise PtmiError(rc, lib.ptmi_last_error(None).decode())
     scene.triangulation = tris

@@ -53,6 +53,7 @@
 #include "pathtracer_backend.hpp"
 #endif
 
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <ctime>
@@ -85,23 +86,18 @@ bool g_log = false;
 bool g_staged = true;
 bool sampler_owns_pixels(const GlobalVars&) { return g_staged; }
 
+// BVH_Create builds on the device from this many triangles on (the timings: profiles/bvh_build_time.json)
+constexpr uint32_t kDeviceBuildMinTriangles = 20000;
+
 unsigned env_uint(const char* name, unsigned fallback)
 {
     const char* v = std::getenv(name);
     return v && *v ? (unsigned)std::strtoul(v, nullptr, 10) : fallback;
 }
 
-}  // namespace
-
-void OpenCL_SetupContext(GlobalVars& globalVars, Sampler sampler)
+// devices: PTMI_DEVICE = one ordinal; else PTMI_DEVICES = list or "all" (default: every device of the node)
+std::vector<int> render_devices()
 {
-    if (g_ctx) {  // a previous render that never reached OpenCL_RunKernel
-        ptmi_release(g_ctx);
-        g_ctx = nullptr;
-    }
-    ptmi_config cfg{};
-    cfg.struct_size = sizeof cfg;
-    // devices: PTMI_DEVICE = one ordinal; else PTMI_DEVICES = list or "all" (default: every device of the node)
     std::vector<int> devices;
     const char* one = std::getenv("PTMI_DEVICE");
     const char* list = std::getenv("PTMI_DEVICES");
@@ -119,6 +115,20 @@ void OpenCL_SetupContext(GlobalVars& globalVars, Sampler sampler)
         const int n = ptmi_device_count();
         for (int i = 0; i < n && i < PTMI_MAX_DEVICES; i++) devices.push_back(i);
     }
+    return devices;
+}
+
+}  // namespace
+
+void OpenCL_SetupContext(GlobalVars& globalVars, Sampler sampler)
+{
+    if (g_ctx) {  // a previous render that never reached OpenCL_RunKernel
+        ptmi_release(g_ctx);
+        g_ctx = nullptr;
+    }
+    ptmi_config cfg{};
+    cfg.struct_size = sizeof cfg;
+    std::vector<int> devices = render_devices();
     if (devices.empty()) devices.push_back(0);  // no device at all: ptmi_setup_context reports it
     if (devices.size() > PTMI_MAX_DEVICES) devices.resize(PTMI_MAX_DEVICES);
     cfg.device = devices[0];
@@ -291,8 +301,28 @@ void BVH_Create(GlobalVars& globalVars)
     globalVars.bvhSize = 0;
     globalVars.bvh = new Node[2 * (size_t)n - 1];
     uint32_t size = 0, depth = 0;
-    const int rc = ptmi_bvh_create(reinterpret_cast<ptmi_triangle*>(globalVars.triangulation), n,
-                                   reinterpret_cast<ptmi_node*>(globalVars.bvh), &size, &depth);
+    ptmi_triangle* tris = reinterpret_cast<ptmi_triangle*>(globalVars.triangulation);
+    ptmi_node* nodes = reinterpret_cast<ptmi_node*>(globalVars.bvh);
+    // Both builders write the same bytes: the device one (ptmi_bvh_create_device) on the device the render will use first,
+    // when there is one and the scene is large enough to gain; the host one otherwise, and when the device call cannot run.
+    const std::vector<int> devices = render_devices();
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = PTMI_ERR_NO_DEVICE;
+    ptmi_bvh_build_info info{};
+    if (!devices.empty() && n >= kDeviceBuildMinTriangles)
+        rc = ptmi_bvh_create_device(devices[0], tris, n, nodes, &size, &depth, &info);
+    const bool on_device = rc != PTMI_ERR_NO_DEVICE && rc != PTMI_ERR_HIP;
+    if (!on_device) rc = ptmi_bvh_create(tris, n, nodes, &size, &depth);
+    if (globalVars.printLogInfos || env_uint("PTMI_LOG", 0) != 0) {
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (on_device && info.built_on_device)
+            std::fprintf(stderr, "[ptmi] BVH_Create: %u triangles, device builder on device %d, %.1f ms\n", n, devices[0], ms);
+        else if (on_device)
+            std::fprintf(stderr, "[ptmi] BVH_Create: %u triangles, host builder (handed over by the device builder, reason %u), %.1f ms\n",
+                         n, info.fallback, ms);
+        else
+            std::fprintf(stderr, "[ptmi] BVH_Create: %u triangles, host builder, %.1f ms\n", n, ms);
+    }
     if (rc) {  // host-only entry point: its message is the library's global one, and a live render context is left alone
         delete[] globalVars.bvh;
         globalVars.bvh = nullptr;
