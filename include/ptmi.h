@@ -42,7 +42,8 @@ typedef enum ptmi_status {
     PTMI_ERR_LIMIT = -4,            /* bvh depth >= 30 or lights >= 30 (reference guard, PathTracer.cpp:54-65) */
     PTMI_ERR_BAD_SCENE = -5,        /* scene arrays inconsistent (index out of range, cyclic bvh ...) */
     PTMI_ERR_STATE = -6,            /* call order violated (e.g. render before initialize_memory) */
-    PTMI_ERR_UNSUPPORTED = -7       /* feature compiled out / not available in this build */
+    PTMI_ERR_UNSUPPORTED = -7,      /* feature compiled out / not available in this build */
+    PTMI_ERR_INTERNAL = -8          /* a bug: the library refused to launch work that broke one of its own invariants */
 } ptmi_status;
 
 typedef struct ptmi_ctx ptmi_ctx;

@@ -21,6 +21,7 @@
 #include "ptmi.h"
 #include "ptmi_internal.h"
 #include "scene_layout.h"
+#include "stage_sets.h"
 
 using namespace ptmi_internal;
 
@@ -64,7 +65,7 @@ struct DeviceState {
     // counters.  That is what lets the library RENDER AHEAD of a caller that asks for one image per call and waits for it, as
     // the reference's loop does, OpenCL.cpp:76-107: the launches of the next calls are already running when they are asked
     // for - `ahead` - and are dropped without a trace if the caller asks for something else.)
-    static constexpr int kStageSets = 4;
+    static constexpr int kStageSets = ptmi_internal::kStageSets;
     float* d_stage[kStageSets] = {};
     size_t stage_cap[kStageSets] = {};            // iterations a set holds
     hipStream_t launch_stream[kStageSets] = {};
@@ -470,7 +471,7 @@ int render_ahead_depth()
 // four calls has one tail in four; each call adopts its quarter of the staging arrays and its own block of counters.
 // (Eight calls per launch would need eight blocks of totals in the workgroup's LDS, which has room for four: as 32-bit words with
 // a carry into memory they cost the kernel itself 1 - 3 %, 973 -> 965 Msamples/s on 1M triangles, material mix 2626 -> 2550.)
-constexpr uint32_t kAheadIterations = PTMI_COUNTER_SPLITS;  // iterations of such a launch at most (calls x iterations per call)
+static_assert(kAheadIterations == PTMI_COUNTER_SPLITS, "a launch ahead counts per call: at most that many calls");  // (stage_sets.h)
 uint32_t render_ahead_calls()
 {
     const char* e = std::getenv("PTMI_RENDER_AHEAD_CALLS");
@@ -512,7 +513,7 @@ int render_on_device(ptmi_ctx* ctx, DeviceState& d, uint32_t first, uint32_t n, 
     static const bool serial_env = std::getenv("PTMI_SERIAL_LAUNCHES") != nullptr;
     const bool may_overlap = staged && !ctx->cfg.super_sampling && d.stream == d.own_stream && !serial_env;
     const size_t npix = ctx->npix();
-    constexpr uint32_t kShort = 4;  // launches of fewer iterations run beside their neighbours (see below)
+    constexpr uint32_t kShort = kShortLaunch;  // launches of fewer iterations run beside their neighbours (see below)
     // Rendering ahead: the call is ONE short launch on this device, nothing but staged results leaves the kernel (the histograms
     // of very deep paths are atomics inside it), and the caller has not asked for an image per iteration.  Per device: in a
     // context of G devices a caller that asks for one image per call comes to this device with every G-th call (ids first,
@@ -524,14 +525,15 @@ int render_on_device(ptmi_ctx* ctx, DeviceState& d, uint32_t first, uint32_t n, 
     const bool continues = d.have_last && d.last_n == n && d.last_stride == stride &&
                            (uint64_t)d.last_first + (uint64_t)n * stride == (uint64_t)first;
     if (staged) {
-        // staging arrays: set 0 for the longest launch of this call, every set for a short one; grown on demand
-        const size_t want = n < ctx->iterations_per_launch ? n : ctx->iterations_per_launch;
-        if (int rc = ensure_stage_set(ctx, d, 0, want)) return rc;
-        if (may_overlap && (n % ctx->iterations_per_launch) != 0 && (n % ctx->iterations_per_launch) < kShort)
-            for (int i = can_run_ahead && continues ? 0 : 1; i < DeviceState::kStageSets; i++) {
+        // staging arrays: set 0 for the longest launch of this call, every set a short one can land on for the longest short
+        // one, from the same predicate that routes a launch to a set (stage_sets.h); grown on demand
+        const StageNeed need = stage_need(n, ctx->iterations_per_launch, may_overlap, can_run_ahead, continues);
+        if (int rc = ensure_stage_set(ctx, d, 0, need.set0)) return rc;
+        if (need.others)
+            for (int i = need.ahead ? 0 : 1; i < DeviceState::kStageSets; i++) {
                 // (room for launches ahead of several calls: only once they are due, and only if the device has it - a launch
                 // ahead renders for as many calls as its set holds)
-                const size_t small = kShort - 1, large = can_run_ahead && continues && kAheadIterations > small ? kAheadIterations : small;
+                const size_t small = need.others, large = need.ahead > small ? need.ahead : small;
                 int rc = ensure_stage_set(ctx, d, i, large);
                 if (rc != PTMI_OK && large > small) {
                     (void)hipGetLastError();
@@ -577,10 +579,19 @@ int render_on_device(ptmi_ctx* ctx, DeviceState& d, uint32_t first, uint32_t n, 
         if (!(d.d_stage[set] && d.ds.hist_depths && ctx->cfg.ray_max_depth < 64)) return nullptr;
         return reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(d.d_stage[set]) + d.stage_cap[set] * npix * 16);
     };
+    // a launch of m iterations into stage set `set`: refused if the set cannot hold them (a planning bug; never a fault)
+    auto set_holds = [&](int set, uint32_t m) {
+        if (d.d_stage[set] && d.stage_cap[set] >= m) return true;
+        rc = PTMI_ERR_INTERNAL;
+        err = "stage set " + std::to_string(set) + " holds " + std::to_string(d.d_stage[set] ? d.stage_cap[set] : 0) +
+              " iterations, a launch of " + std::to_string(m) + " was to stage into it";
+        return false;
+    };
     // A SHORT launch on stage set `set`: on the set's own stream, counting into the set's own block - it touches nothing else
     // of the context, whether a call has asked for it or not.
     // `calls` > 1: the launch renders for that many calls of m / calls iterations each, and counts per call.
     auto launch_on_set = [&](int set, uint32_t f, uint32_t m, uint32_t calls) {
+        if (!set_holds(set, m)) return;
         hipStream_t ls = d.launch_stream[set];
         if (d.reuse_after[set]) e = hipStreamWaitEvent(ls, d.reuse_after[set], 0);
         if (e == hipSuccess) e = hipMemsetAsync(d.d_set_counters[set], 0, PTMI_COUNTER_SPLITS * C_COUNT * 8, ls);
@@ -634,7 +645,7 @@ int render_on_device(ptmi_ctx* ctx, DeviceState& d, uint32_t first, uint32_t n, 
                     if (e != hipSuccess) break;
                 } else {
                     if (d.reuse_after[0]) e = hipStreamWaitEvent(d.stream, d.reuse_after[0], 0);  // (a short launch nobody adopted)
-                    if (e != hipSuccess) break;
+                    if (e != hipSuccess || (staged && !set_holds(0, m))) break;
                     rc = KERNELS_OF(ctx, launch_render_wavefront)(d.ds, d.d_scene, f, m, stride, d.d_job_counter, ctx->stack_levels, stats_build,
                                                                   staged ? d.d_stage[0] : nullptr, staged ? stats_of(0) : nullptr, d.stream, &err);
                     if (rc != PTMI_OK) break;
@@ -1023,6 +1034,11 @@ int ptmi_setup_context(ptmi_ctx** out, const ptmi_config* cfg)
         if (by_jobs < cap) cap = by_jobs;
         if (by_bytes < cap) cap = by_bytes;
         ctx->iterations_per_launch = cap < 1 ? 1u : (uint32_t)cap;
+        // env: test switch - a lower cap, so that small images take the launch plans of very large ones (1..32; never higher)
+        if (const char* v = std::getenv("PTMI_ITERATIONS_PER_LAUNCH")) {
+            const long want = std::strtol(v, nullptr, 10);
+            if (want >= 1 && want <= 32 && (uint32_t)want < ctx->iterations_per_launch) ctx->iterations_per_launch = (uint32_t)want;
+        }
     }
     *out = ctx;
     return PTMI_OK;

@@ -57,9 +57,17 @@ class Model:
         self.totals = dict(tot) if self.totals is None else {key: self.totals[key] + tot[key] for key in tot}
 
 
+# (and a few at caps of 1 - 3 iterations per launch, PTMI_ITERATIONS_PER_LAUNCH: every launch short; tests/test_launch_caps_gpu.py)
+LOW_CAP_SEEDS = [pytest.param(seed, cap, id=f"{seed}-cap{cap}") for cap, seeds in ((1, (1000, 1001)), (2, (1002, 1003)), (3, (1005, 1006)))
+                 for seed in seeds]
+
+
 @pytest.mark.parametrize("devices", [None, [0, 0], [0, 0, 0]], ids=["one", "two", "three"])
-@pytest.mark.parametrize("seed", range(int(os.environ.get("PTMI_API_FUZZ_SEEDS", "24"))))  # (a soak: PTMI_API_FUZZ_SEEDS=400)
-def test_random_call_sequences(seed, devices, per_iteration):
+@pytest.mark.parametrize("seed, cap", [pytest.param(seed, None, id=str(seed)) for seed in range(int(os.environ.get("PTMI_API_FUZZ_SEEDS", "24")))] +
+                         LOW_CAP_SEEDS)  # (a soak: PTMI_API_FUZZ_SEEDS=400)
+def test_random_call_sequences(seed, cap, devices, per_iteration, monkeypatch):
+    if cap is not None:
+        monkeypatch.setenv("PTMI_ITERATIONS_PER_LAUNCH", str(cap))
     rs = np.random.RandomState(1234 + seed)
     exact = devices is None
     da = seed % 3 != 0
