@@ -12,7 +12,6 @@
 #include <limits>
 #include <cstdlib>
 #include <cstring>
-#include <deque>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -21,7 +20,7 @@
 #include "ptmi.h"
 #include "ptmi_internal.h"
 #include "scene_layout.h"
-#include "stage_sets.h"
+#include "launch_schedule.h"
 
 using namespace ptmi_internal;
 
@@ -52,19 +51,11 @@ struct DeviceState {
     uint32_t* d_hist = nullptr;  // depths | bbx | tri
     unsigned long long* d_counters = nullptr;
     uint32_t* d_job_counter = nullptr;
-    // Staged radiances [iteration][pixel] float4 (+ one statistics word per path) of the launches in flight.  TWO sets, each
-    // with a launch stream and job-queue counters of its own: consecutive launches alternate between them, so that the
-    // ramp-up of launch k+1 fills the CUs the tail of launch k leaves idle (a persistent launch ends ragged: its last paths
-    // finish one by one).  What keeps the results those of sequential launches: the staged values reach the accumulators
-    // on the ONE main stream, launch after launch (launch_accumulate_staged), and set k % 2 is reused by launch k + 2
-    // only after launch k's have been added (stage_free).
-    // (round 4: FOUR sets.  Set 0 is sized for the longest launch and is the one long launches use, on the main stream; short
-    // launches - fewer than 4 iterations - take the sets in turn, each with a COUNTER BLOCK and a device copy of the scene
-    // record of its own, so that such a launch touches nothing of the context but its set until the main stream ADOPTS it:
-    // adds its staged radiances to the accumulators, its statistics words to the histograms, its counter block to the
-    // counters.  That is what lets the library RENDER AHEAD of a caller that asks for one image per call and waits for it, as
-    // the reference's loop does, OpenCL.cpp:76-107: the launches of the next calls are already running when they are asked
-    // for - `ahead` - and are dropped without a trace if the caller asks for something else.)
+    // Staged radiances [iteration][pixel] float4 (+ one statistics word per path) of the launches in flight: the stage sets of
+    // launch_schedule.h, which decides what runs on them (`schedule`).  What keeps the results those of sequential launches:
+    // the staged values reach the accumulators on the ONE main stream, launch after launch (launch_accumulate_staged), and a
+    // set is reused only after its previous launch's values have been added (stage_free) or, if nobody adopted it, after it has
+    // ended (rendered).
     static constexpr int kStageSets = ptmi_internal::kStageSets;
     float* d_stage[kStageSets] = {};
     size_t stage_cap[kStageSets] = {};            // iterations a set holds
@@ -74,18 +65,8 @@ struct DeviceState {
     hipEvent_t reuse_after[kStageSets] = {};      // what the set's next launch waits for: stage_free (adopted) or rendered (dropped)
     unsigned long long* d_set_counters[kStageSets] = {};  // [PTMI_COUNTER_SPLITS][C_COUNT] each: one block per call a launch renders for
     DScene* d_scene_set[kStageSets] = {};         // ds with .counters = the set's block
-    // a launch that renders for `calls` calls of n iterations each (ids from `first` on), of which `taken` have come and adopted
-    // their part
-    struct Ahead { uint32_t first, n, stride; int set; uint32_t calls, taken; };
-    std::deque<Ahead> ahead;                      // launches in flight that calls have not (all) asked for yet, oldest first
-    uint32_t streak = 0;                          // calls in a row that continued where the previous one left off
-    uint32_t next_set = 0;
-    // the previous ptmi_render call on this device: launches only run ahead of a caller that has been SEEN to continue where
-    // it left off (ids first + n, same n), so a caller that jumps around pays nothing
-    bool have_last = false;
-    uint32_t last_first = 0, last_n = 0, last_stride = 0;
+    LaunchSchedule schedule;
     hipEvent_t previous_call_done = nullptr;  // the event behind the previous call's work on the main stream
-    uint32_t launches_issued = 0;
     DScene ds{};
     DScene* d_scene = nullptr;  // device copy of ds (what the wavefront kernel's path logic reads)
     // ptmi_snapshot ring: float[5*W*H] per slot (colour, then count), allocated on first use
@@ -185,8 +166,7 @@ void free_scene_memory(ptmi_ctx* ctx)
         // launch and the main stream's wait for it (render_on_device) a persistent kernel may still be reading the scene
         for (int i = 0; i < DeviceState::kStageSets; i++)
             if (d.launch_stream[i]) (void)hipStreamSynchronize(d.launch_stream[i]);
-        d.ahead.clear();
-        d.have_last = false;
+        d.schedule.forget();
         d.previous_call_done = nullptr;
         (void)hipStreamSynchronize(d.stream);
         if (d.copy_stream) (void)hipStreamSynchronize(d.copy_stream);
@@ -455,37 +435,23 @@ int snapshots_up_to(ptmi_ctx* ctx, DeviceState& d, SnapshotPlan& plan, uint32_t 
     return PTMI_OK;
 }
 
-// How many launches the library keeps in flight AHEAD of a caller that renders one short call after the other and waits for
-// each (DeviceState::ahead): PTMI_RENDER_AHEAD, default 2, 0 = never.
-int render_ahead_depth()
-{
-    const char* e = std::getenv("PTMI_RENDER_AHEAD");  // (read per call: the tests switch it between contexts)
-    const int v = e ? std::atoi(e) : 2;
-    // (at most kStageSets - 2: beside them one launch whose calls are coming, and one set for a call that finds nothing)
-    return v < 0 ? 0 : (v > DeviceState::kStageSets - 2 ? DeviceState::kStageSets - 2 : v);
-}
-
-// ... and how many CALLS one of those launches may render for (PTMI_RENDER_AHEAD_CALLS, default PTMI_COUNTER_SPLITS = 4, 1 = one
-// launch per call): a persistent launch of ONE iteration spends a fifth of its time in its ragged end, and two such launches
-// side by side share the CUs only as the first one's workgroups retire - at the very end of that tail.  One launch for the next
-// four calls has one tail in four; each call adopts its quarter of the staging arrays and its own block of counters.
-// (Eight calls per launch would need eight blocks of totals in the workgroup's LDS, which has room for four: as 32-bit words with
-// a carry into memory they cost the kernel itself 1 - 3 %, 973 -> 965 Msamples/s on 1M triangles, material mix 2626 -> 2550.)
+// The render-ahead switches, read per call (tests switch them between contexts): launches kept in flight AHEAD of a blocking
+// caller (PTMI_RENDER_AHEAD, default 2, 0 = never, at most kStageSets - 2: beside them one launch whose calls are coming, and one
+// set for a call that finds nothing), and CALLS one of them may render for (PTMI_RENDER_AHEAD_CALLS, default 4).
 static_assert(kAheadIterations == PTMI_COUNTER_SPLITS, "a launch ahead counts per call: at most that many calls");  // (stage_sets.h)
-uint32_t render_ahead_calls()
+uint32_t env_in(const char* name, int fallback, int lo, int hi)
 {
-    const char* e = std::getenv("PTMI_RENDER_AHEAD_CALLS");
-    const int v = e ? std::atoi(e) : PTMI_COUNTER_SPLITS;
-    return v < 1 ? 1u : (v > PTMI_COUNTER_SPLITS ? (uint32_t)PTMI_COUNTER_SPLITS : (uint32_t)v);
+    const char* e = std::getenv(name);
+    const int v = e ? std::atoi(e) : fallback;
+    return (uint32_t)(v < lo ? lo : (v > hi ? hi : v));
 }
 
-// Stage set `set` able to hold `iterations` iterations (radiance float4 + one statistics word per path).  Growing it waits
-// for whatever may still use the old arrays.
-int ensure_stage_set(ptmi_ctx* ctx, DeviceState& d, int set, size_t iterations)
+// Stage set `set` able to hold `iterations` iterations (radiance float4 + one statistics word per path), or `at_least` where the
+// device does not have the memory for that many.  Growing it waits for whatever may still use the old arrays.
+int ensure_stage_set(ptmi_ctx* ctx, DeviceState& d, int set, size_t iterations, size_t at_least = 0)
 {
     if (d.stage_cap[set] >= iterations) return PTMI_OK;
-    for (auto it = d.ahead.begin(); it != d.ahead.end();)
-        it = it->set == set ? d.ahead.erase(it) : it + 1;
+    d.schedule.forget_set(set);
     if (d.launch_stream[set]) HIP_TRY(ctx, hipStreamSynchronize(d.launch_stream[set]));
     HIP_TRY(ctx, hipStreamSynchronize(d.stream));
     if (d.d_stage[set]) (void)hipFree(d.d_stage[set]);
@@ -493,237 +459,138 @@ int ensure_stage_set(ptmi_ctx* ctx, DeviceState& d, int set, size_t iterations)
     d.stage_cap[set] = 0;
     d.reuse_after[set] = nullptr;
     void* p = nullptr;
-    HIP_TRY(ctx, hipMalloc(&p, iterations * ctx->npix() * 20));
+    if (at_least && at_least < iterations && hipMalloc(&p, iterations * ctx->npix() * 20) != hipSuccess) {
+        (void)hipGetLastError();
+        p = nullptr, iterations = at_least;
+    }
+    if (!p) HIP_TRY(ctx, hipMalloc(&p, iterations * ctx->npix() * 20));
     d.d_stage[set] = (float*)p;
     d.stage_cap[set] = iterations;
     return PTMI_OK;
 }
 
-// One device's launches for its share of a ptmi_render call, bracketed by an event pair for ptmi_kernel_time.
+// where the statistics words of a set's launches go: staged per path and counted after the launch, unless there is no histogram
+// (PTMI_FLAG_NO_HISTOGRAMS) or a depth that does not fit the 6-bit field
+uint32_t* stats_of(const ptmi_ctx* ctx, const DeviceState& d, int set)
+{
+    if (!(d.d_stage[set] && d.ds.hist_depths && ctx->cfg.ray_max_depth < 64)) return nullptr;
+    return reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(d.d_stage[set]) + d.stage_cap[set] * ctx->npix() * 16);
+}
+
+// A launch of m iterations from id f: on the main stream into set 0 (`main`; staged or not), or a SHORT one on stage set `set`:
+// on the set's own stream, counting into the set's own block - it touches nothing else of the context, whether a call has asked
+// for it or not.  `calls` > 1: the launch renders for that many calls of m / calls iterations each, and counts per call.
+int launch(ptmi_ctx* ctx, DeviceState& d, bool main, bool staged, int set, uint32_t f, uint32_t m, uint32_t stride, uint32_t calls = 1)
+{
+    hipStream_t st = main ? d.stream : d.launch_stream[set];
+    if (d.reuse_after[set]) HIP_TRY(ctx, hipStreamWaitEvent(st, d.reuse_after[set], 0));  // (main: a short launch nobody adopted)
+    if (staged && !(d.d_stage[set] && d.stage_cap[set] >= m))  // (a planning bug: refused, never a fault)
+        return fail(ctx, PTMI_ERR_INTERNAL, "stage set " + std::to_string(set) + " holds " + std::to_string(d.d_stage[set] ? d.stage_cap[set] : 0) +
+                                                " iterations, a launch of " + std::to_string(m) + " was to stage into it");
+    DScene k = d.ds;
+    if (!main) {
+        HIP_TRY(ctx, hipMemsetAsync(d.d_set_counters[set], 0, PTMI_COUNTER_SPLITS * C_COUNT * 8, st));
+        k.counters = d.d_set_counters[set];
+        k.split_paths = calls > 1 ? (uint32_t)((m / calls) * ctx->npix()) : 0u;
+    }
+    std::string err;
+    if (int rc = KERNELS_OF(ctx, launch_render_wavefront)(k, main ? d.d_scene : d.d_scene_set[set], f, m, stride, d.d_job_counter + set * 8 * 1024,
+                                                          ctx->stack_levels, d.schedule.call.stats_build, staged ? d.d_stage[set] : nullptr,
+                                                          staged ? stats_of(ctx, d, set) : nullptr, st, &err))
+        return fail(ctx, rc, err);
+    if (main) return PTMI_OK;
+    d.reuse_after[set] = d.rendered[set];  // (until the main stream adopts it)
+    HIP_TRY(ctx, hipEventRecord(d.rendered[set], st));
+    return PTMI_OK;
+}
+
+// One device's launches for its share of a ptmi_render call, as d.schedule plans them, bracketed by an event pair for
+// ptmi_kernel_time.
 int render_on_device(ptmi_ctx* ctx, DeviceState& d, uint32_t first, uint32_t n, uint32_t stride, SnapshotPlan* plan = nullptr)
 {
     if (n == 0) return plan ? snapshots_up_to(ctx, d, *plan, plan->n) : PTMI_OK;
     ON_DEVICE(ctx, d);
-    if (d.pending_events.size() >= 512)
-        if (int rc = fold_events(ctx, d)) return rc;
+    if (int rc = d.pending_events.size() >= 512 ? fold_events(ctx, d) : PTMI_OK) return rc;
     const bool megakernel = one_path_per_lane(ctx);
     const bool staged = !megakernel && ctx->cfg.sampler != PTMI_SAMPLER_RANDOM;
-    // launch streams of their own: only where the launch itself neither reads nor writes the accumulators (staged results, no
-    // adaptive sampling), on the context's own stream, and unless switched off (PTMI_SERIAL_LAUNCHES: developer A/B switch)
+    // launch streams of their own (for SHORT launches only: long ones side by side get in each other's way): only where the
+    // launch neither reads nor writes the accumulators (staged results, no adaptive sampling), on the context's own stream,
+    // and unless switched off (PTMI_SERIAL_LAUNCHES: developer A/B switch)
     static const bool serial_env = std::getenv("PTMI_SERIAL_LAUNCHES") != nullptr;
     const bool may_overlap = staged && !ctx->cfg.super_sampling && d.stream == d.own_stream && !serial_env;
-    const size_t npix = ctx->npix();
-    constexpr uint32_t kShort = kShortLaunch;  // launches of fewer iterations run beside their neighbours (see below)
-    // Rendering ahead: the call is ONE short launch on this device, nothing but staged results leaves the kernel (the histograms
-    // of very deep paths are atomics inside it), and the caller has not asked for an image per iteration.  Per device: in a
-    // context of G devices a caller that asks for one image per call comes to this device with every G-th call (ids first,
-    // first + G, ...: the same pattern with stride G), and without launches ahead only ONE of the G devices would work at a time.
-    const bool can_run_ahead = may_overlap && render_ahead_depth() > 0 && !plan && n < kShort &&
-                               !(d.ds.hist_depths && ctx->cfg.ray_max_depth >= 64);
-    if (!can_run_ahead) d.ahead.clear();  // (their sets are free again once their kernels have ended: reuse_after)
-    // the caller comes back for the next ids with the same count
-    const bool continues = d.have_last && d.last_n == n && d.last_stride == stride &&
-                           (uint64_t)d.last_first + (uint64_t)n * stride == (uint64_t)first;
+    // rendering ahead (per device: with G devices each sees every G-th call, stride G): nothing but staged results leaves the
+    // kernel (the histograms of very deep paths are atomics inside it), and the caller has not asked for an image per iteration
+    const bool ahead_allowed = !plan && !(d.ds.hist_depths && ctx->cfg.ray_max_depth >= 64);
+    const StageNeed need = d.schedule.begin({first, n, stride, ctx->iterations_per_launch, ctx->cfg.super_sampling != 0, may_overlap,
+                                             ahead_allowed, env_in("PTMI_RENDER_AHEAD", 2, 0, DeviceState::kStageSets - 2),
+                                             env_in("PTMI_RENDER_AHEAD_CALLS", PTMI_COUNTER_SPLITS, 1, PTMI_COUNTER_SPLITS),
+                                             (ctx->cfg.flags & PTMI_FLAG_SCHEDULER_STATS) != 0});
     if (staged) {
-        // staging arrays: set 0 for the longest launch of this call, every set a short one can land on for the longest short
-        // one, from the same predicate that routes a launch to a set (stage_sets.h); grown on demand
-        const StageNeed need = stage_need(n, ctx->iterations_per_launch, may_overlap, can_run_ahead, continues);
+        // staging arrays, grown on demand: room for launches ahead only once they are due, and only where the device has it
         if (int rc = ensure_stage_set(ctx, d, 0, need.set0)) return rc;
-        if (need.others)
-            for (int i = need.ahead ? 0 : 1; i < DeviceState::kStageSets; i++) {
-                // (room for launches ahead of several calls: only once they are due, and only if the device has it - a launch
-                // ahead renders for as many calls as its set holds)
-                const size_t small = need.others, large = need.ahead > small ? need.ahead : small;
-                int rc = ensure_stage_set(ctx, d, i, large);
-                if (rc != PTMI_OK && large > small) {
-                    (void)hipGetLastError();
-                    rc = ensure_stage_set(ctx, d, i, small);
-                }
-                if (rc != PTMI_OK) return rc;
-            }
+        for (int i = need.ahead ? 0 : 1; need.others && i < DeviceState::kStageSets; i++)
+            if (int rc = ensure_stage_set(ctx, d, i, std::max(need.ahead, need.others), need.others)) return rc;
         for (int i = 0; i < DeviceState::kStageSets && may_overlap; i++) {
             if (!d.launch_stream[i]) HIP_TRY(ctx, hipStreamCreateWithFlags(&d.launch_stream[i], hipStreamNonBlocking));
             if (!d.rendered[i]) HIP_TRY(ctx, hipEventCreateWithFlags(&d.rendered[i], hipEventDisableTiming));
             if (!d.stage_free[i]) HIP_TRY(ctx, hipEventCreateWithFlags(&d.stage_free[i], hipEventDisableTiming));
         }
     }
-    std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
-    if (!d.free_events.empty()) {
-        ev = d.free_events.back();
-        d.free_events.pop_back();
-    } else {
-        HIP_TRY(ctx, hipEventCreate(&ev.first));
-        if (hipEventCreate(&ev.second) != hipSuccess) {
-            (void)hipEventDestroy(ev.first);
-            return fail(ctx, PTMI_ERR_HIP, "hipEventCreate failed");
-        }
-    }
+    // the event pair stays in the pool until the call has been issued
+    if (d.free_events.empty()) d.free_events.push_back({nullptr, nullptr});
+    if (!d.free_events.back().first) HIP_TRY(ctx, hipEventCreate(&d.free_events.back().first));
+    if (!d.free_events.back().second) HIP_TRY(ctx, hipEventCreate(&d.free_events.back().second));
+    const std::pair<hipEvent_t, hipEvent_t> ev = d.free_events.back();
+    const size_t npix = ctx->npix();
     std::string err;
-    int rc = PTMI_OK;
-    hipError_t e = hipSuccess;
-    const bool stats_build = (ctx->cfg.flags & PTMI_FLAG_SCHEDULER_STATS) != 0;
-    // a stage set no launch in flight ahead of the caller holds (there always is one: fewer launches ahead than sets)
-    auto pick_set = [&]() {
-        int set = 0;
-        for (int tries = 0; tries < DeviceState::kStageSets; tries++) {
-            set = (int)(d.next_set++ % DeviceState::kStageSets);
-            bool held = false;
-            for (const DeviceState::Ahead& a : d.ahead) held = held || a.set == set;
-            if (!held) break;
-        }
-        return set;
-    };
-    // where the statistics words of a set's launches go: staged per path and counted after the launch, unless there is no
-    // histogram (PTMI_FLAG_NO_HISTOGRAMS) or a depth that does not fit the 6-bit field
-    auto stats_of = [&](int set) -> uint32_t* {
-        if (!(d.d_stage[set] && d.ds.hist_depths && ctx->cfg.ray_max_depth < 64)) return nullptr;
-        return reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(d.d_stage[set]) + d.stage_cap[set] * npix * 16);
-    };
-    // a launch of m iterations into stage set `set`: refused if the set cannot hold them (a planning bug; never a fault)
-    auto set_holds = [&](int set, uint32_t m) {
-        if (d.d_stage[set] && d.stage_cap[set] >= m) return true;
-        rc = PTMI_ERR_INTERNAL;
-        err = "stage set " + std::to_string(set) + " holds " + std::to_string(d.d_stage[set] ? d.stage_cap[set] : 0) +
-              " iterations, a launch of " + std::to_string(m) + " was to stage into it";
-        return false;
-    };
-    // A SHORT launch on stage set `set`: on the set's own stream, counting into the set's own block - it touches nothing else
-    // of the context, whether a call has asked for it or not.
-    // `calls` > 1: the launch renders for that many calls of m / calls iterations each, and counts per call.
-    auto launch_on_set = [&](int set, uint32_t f, uint32_t m, uint32_t calls) {
-        if (!set_holds(set, m)) return;
-        hipStream_t ls = d.launch_stream[set];
-        if (d.reuse_after[set]) e = hipStreamWaitEvent(ls, d.reuse_after[set], 0);
-        if (e == hipSuccess) e = hipMemsetAsync(d.d_set_counters[set], 0, PTMI_COUNTER_SPLITS * C_COUNT * 8, ls);
-        if (e != hipSuccess) return;
-        DScene on_set = d.ds;
-        on_set.counters = d.d_set_counters[set];
-        on_set.split_paths = calls > 1 ? (uint32_t)((m / calls) * npix) : 0u;
-        rc = KERNELS_OF(ctx, launch_render_wavefront)(on_set, d.d_scene_set[set], f, m, stride, d.d_job_counter + set * 8 * 1024, ctx->stack_levels,
-                                                      stats_build, d.d_stage[set], stats_of(set), ls, &err);
-        if (rc != PTMI_OK) return;
-        e = hipEventRecord(d.rendered[set], ls);
-        d.reuse_after[set] = d.rendered[set];  // (until the main stream adopts it)
-        d.launches_issued++;
-    };
-    // Both events on the MAIN stream: [previous launch accumulated, this one accumulated].  With launch streams of their own
-    // the intervals still tile the time line (no double counting of the overlap).
-    e = hipEventRecord(ev.first, d.stream);
-    if (e == hipSuccess) {
-        if (megakernel) {
-            rc = KERNELS_OF(ctx, launch_render)(d.ds, first, n, stride, d.stream, &err);
-        } else {
-            // one launch per chunk of iterations
-            for (uint32_t done = 0; done < n && rc == PTMI_OK && e == hipSuccess;) {
-                // SUPER_SAMPLING: the stop criterion of iteration k reads the accumulators after k-1 => one per launch
-                const uint32_t cap = ctx->cfg.super_sampling ? 1u : ctx->iterations_per_launch;
-                const uint32_t m = n - done < cap ? n - done : cap;
-                const uint32_t f = first + done * stride;
-                // Only SHORT launches get streams of their own (measured on MI355X, 1M triangles 1080p: one image per launch 631 -> 657
-                // Msamples/s with the overlap; 16 images per launch 763 -> 753: two long persistent launches side by side only
-                // get in each other's way, and their ragged ends are 1 % of their length anyway)
-                const bool on_own_stream = may_overlap && m < kShort;
-                int set = 0;
-                uint32_t part = 0;  // which of the calls a launch that ran ahead rendered for this one is
-                if (on_own_stream) {
-                    // a launch that ran ahead for this call?  (the oldest first; anything else the caller did not come back for)
-                    bool found = false;
-                    while (can_run_ahead && !d.ahead.empty() && !found) {
-                        DeviceState::Ahead& a = d.ahead.front();
-                        found = a.n == m && a.stride == stride && (uint64_t)a.first + (uint64_t)a.taken * a.n * a.stride == (uint64_t)f;
-                        set = a.set;
-                        part = a.taken;
-                        if (!found || ++a.taken == a.calls) d.ahead.pop_front();
-                    }
-                    if (!found) {
-                        part = 0;
-                        set = pick_set();
-                        launch_on_set(set, f, m, 1);
-                        if (rc != PTMI_OK || e != hipSuccess) break;
-                    }
-                    e = hipStreamWaitEvent(d.stream, d.rendered[set], 0);
-                    if (e != hipSuccess) break;
-                } else {
-                    if (d.reuse_after[0]) e = hipStreamWaitEvent(d.stream, d.reuse_after[0], 0);  // (a short launch nobody adopted)
-                    if (e != hipSuccess || (staged && !set_holds(0, m))) break;
-                    rc = KERNELS_OF(ctx, launch_render_wavefront)(d.ds, d.d_scene, f, m, stride, d.d_job_counter, ctx->stack_levels, stats_build,
-                                                                  staged ? d.d_stage[0] : nullptr, staged ? stats_of(0) : nullptr, d.stream, &err);
-                    if (rc != PTMI_OK) break;
-                    d.launches_issued++;
+    // both events on the MAIN stream, [previous launch accumulated, this one accumulated]: the intervals tile the time line
+    HIP_TRY(ctx, hipEventRecord(ev.first, d.stream));
+    if (megakernel) {
+        if (int rc = KERNELS_OF(ctx, launch_render)(d.ds, first, n, stride, d.stream, &err)) return fail(ctx, rc, err);
+    } else {
+        for (const Step& s : d.schedule.steps()) {
+            if (s.kind != Step::kAdopt)
+                if (int rc = launch(ctx, d, s.kind == Step::kMain, staged, s.set, s.first, s.n, stride)) return rc;
+            if (s.kind != Step::kMain) HIP_TRY(ctx, hipStreamWaitEvent(d.stream, d.rendered[s.set], 0));
+            float* const stage = staged ? d.d_stage[s.set] + (size_t)s.part * s.n * npix * 4 : nullptr;
+            uint32_t* const stage_stats = staged && stats_of(ctx, d, s.set) ? stats_of(ctx, d, s.set) + (size_t)s.part * s.n * npix : nullptr;
+            if (!plan) {
+                if (int rc = KERNELS_OF(ctx, launch_accumulate_staged)(d.ds, s.first, s.n, stage, stage_stats, true, d.stream, &err))
+                    return fail(ctx, rc, err);
+            } else {
+                // one accumulation per iteration, each followed by the snapshots of the global iterations up to it
+                for (uint32_t j = 0; j < s.n; j++) {
+                    const uint32_t id = s.first + j * stride;
+                    if (int rc = snapshots_up_to(ctx, d, *plan, id - plan->first)) return rc;  // images before this device's next own one
+                    if (int rc = KERNELS_OF(ctx, launch_accumulate_staged)(d.ds, id, 1, stage + (size_t)j * npix * 4,
+                                                                           stage_stats ? stage_stats + (size_t)j * npix : nullptr, false, d.stream, &err))
+                        return fail(ctx, rc, err);
+                    plan->changed = true;
+                    if (int rc = snapshots_up_to(ctx, d, *plan, id - plan->first + 1)) return rc;
                 }
-                float* const stage = staged ? d.d_stage[set] + (size_t)part * m * npix * 4 : nullptr;
-                uint32_t* const stage_stats = staged && stats_of(set) ? stats_of(set) + (size_t)part * m * npix : nullptr;
-                if (!plan) {
-                    rc = KERNELS_OF(ctx, launch_accumulate_staged)(d.ds, f, m, stage, stage_stats, true, d.stream, &err);
-                } else {
-                    // one accumulation per iteration, each followed by the snapshots of the global iterations up to it
-                    for (uint32_t j = 0; j < m && rc == PTMI_OK; j++) {
-                        const uint32_t id = first + (done + j) * stride;
-                        rc = snapshots_up_to(ctx, d, *plan, id - plan->first);  // images before this device's next own one
-                        if (rc != PTMI_OK) break;
-                        rc = KERNELS_OF(ctx, launch_accumulate_staged)(d.ds, id, 1, stage + (size_t)j * npix * 4,
-                                                                       stage_stats ? stage_stats + (size_t)j * npix : nullptr, false, d.stream, &err);
-                        plan->changed = true;
-                        if (rc == PTMI_OK) rc = snapshots_up_to(ctx, d, *plan, id - plan->first + 1);
-                    }
-                    if (rc == PTMI_OK && stage_stats)
-                        rc = KERNELS_OF(ctx, launch_histogram_staged)(d.ds, m, stage_stats, d.stream, &err);
-                    if (rc != PTMI_OK && err.empty()) err = ctx->err;
-                }
-                if (rc != PTMI_OK) break;
-                if (on_own_stream) rc = launch_add_counters(d.d_counters, d.d_set_counters[set] + (size_t)part * C_COUNT, C_COUNT, d.stream, &err);
-                if (rc != PTMI_OK) break;
-                if (staged && may_overlap) {  // (also behind a launch on the main stream: a later short launch may take set 0)
-                    e = hipEventRecord(d.stage_free[set], d.stream);
-                    d.reuse_after[set] = d.stage_free[set];
-                }
-                done += m;
+                if (int rc = stage_stats ? KERNELS_OF(ctx, launch_histogram_staged)(d.ds, s.n, stage_stats, d.stream, &err) : PTMI_OK)
+                    return fail(ctx, rc, err);
             }
-            // keep the next launches of a caller that comes back for one short call after the other in flight
-            // ... and only ahead of a caller that WAITS: if what the previous call asked for was still running when this call
-            // came, the caller keeps the GPU busy by itself (launches queued ahead of its readbacks) and more launches in
-            // flight would only be in its way
-            const bool caller_waits = d.previous_call_done == nullptr || hipEventQuery(d.previous_call_done) == hipSuccess;
-            (void)hipGetLastError();  // (hipErrorNotReady is not an error)
-            d.streak = continues ? d.streak + 1 : 0;
-            if (can_run_ahead && continues && caller_waits && rc == PTMI_OK && e == hipSuccess) {
-                uint64_t next = d.ahead.empty() ? (uint64_t)first + (uint64_t)n * stride
-                                                : (uint64_t)d.ahead.back().first + (uint64_t)d.ahead.back().calls * n * stride;
-                // (a launch whose calls have begun to come no longer counts: what replaces it starts as soon as it has ended)
-                const int untouched = (int)d.ahead.size() - (!d.ahead.empty() && d.ahead.front().taken != 0u ? 1 : 0);
-                // (Tried: the two launches ahead side by side with HALF of the persistent grid each, so that one's steady state fills
-                // the other's ragged end - 1M triangles 149.9 -> 132.4 Mpaths/s, Cornell box 1080p 1352 -> 1211: two persistent
-                // grids do not share the CUs evenly.  They take turns with whole grids.)
-                for (int have = untouched; have < render_ahead_depth() && rc == PTMI_OK && e == hipSuccess; have++) {
-                    // one launch for the next `calls` calls: 1, 2, 4 as the caller keeps coming back, four iterations at most
-                    // (the statistics build counts per launch: one call each)
-                    uint32_t calls = stats_build ? 1u : render_ahead_calls();
-                    if (calls > kAheadIterations / n) calls = kAheadIterations / n;
-                    if (calls * n > ctx->iterations_per_launch) calls = ctx->iterations_per_launch / n;
-                    if (d.streak < 4 && calls > (1u << (d.streak - 1))) calls = 1u << (d.streak - 1);
-                    while (calls > 1 && next + ((uint64_t)calls * n - 1) * stride > 0xFFFFFFFFull) calls--;
-                    if (calls < 1 || next + (uint64_t)(n - 1) * stride > 0xFFFFFFFFull) break;
-                    const int set = pick_set();
-                    if ((size_t)n * calls > d.stage_cap[set]) calls = (uint32_t)(d.stage_cap[set] / n);
-                    if (calls < 1) break;
-                    launch_on_set(set, (uint32_t)next, n * calls, calls);
-                    if (rc == PTMI_OK && e == hipSuccess) d.ahead.push_back({(uint32_t)next, n, stride, set, calls, 0u});
-                    next += (uint64_t)calls * n * stride;
-                }
+            if (s.kind != Step::kMain)
+                if (int rc = launch_add_counters(d.d_counters, d.d_set_counters[s.set] + (size_t)s.part * C_COUNT, C_COUNT, d.stream, &err))
+                    return fail(ctx, rc, err);
+            if (may_overlap) {  // (also behind a launch on the main stream: a later short launch may take set 0)
+                d.reuse_after[s.set] = d.stage_free[s.set];
+                HIP_TRY(ctx, hipEventRecord(d.stage_free[s.set], d.stream));
             }
         }
-        if (e == hipSuccess && rc == PTMI_OK && plan) rc = snapshots_up_to(ctx, d, *plan, plan->n);  // images after its last own one
-        if (e == hipSuccess) e = hipEventRecord(ev.second, d.stream);
+        // launches ahead only of a caller that WAITS: one whose previous call was still running keeps the GPU busy by itself
+        const bool caller_waits = d.previous_call_done == nullptr || hipEventQuery(d.previous_call_done) == hipSuccess;
+        (void)hipGetLastError();  // (hipErrorNotReady is not an error)
+        for (const LaunchSchedule::Ahead& a : d.schedule.launches_ahead(caller_waits, d.stage_cap))
+            if (int rc = launch(ctx, d, false, true, a.set, a.first, a.n * a.calls, stride, a.calls)) return rc;
     }
-    if (e != hipSuccess || rc != PTMI_OK) {
-        d.free_events.push_back(ev);  // never timed: back to the pool
-        if (rc != PTMI_OK) return fail(ctx, rc, err);
-        return fail(ctx, PTMI_ERR_HIP, std::string("launch sequencing: ") + hipGetErrorString(e));
-    }
+    if (int rc = plan ? snapshots_up_to(ctx, d, *plan, plan->n) : PTMI_OK) return rc;  // images after its last own one
+    HIP_TRY(ctx, hipEventRecord(ev.second, d.stream));
+    d.free_events.pop_back();
     d.pending_events.push_back(ev);
     d.previous_call_done = ev.second;  // (stays valid in the pool: fold_events only moves the pair to free_events)
-    d.have_last = true;
-    d.last_first = first; d.last_n = n; d.last_stride = stride;
+    d.schedule.commit();
     return PTMI_OK;
 }
 
@@ -1483,6 +1350,11 @@ int ptmi_bind_accumulators(ptmi_ctx* ctx, void* d_color, void* d_count)
         return fail(ctx, PTMI_ERR_INVALID_ARGUMENT, "bind both accumulators or neither");
     DeviceState& d = ctx->dev[0];
     ON_DEVICE(ctx, d);
+    // a launch ahead may still be reading the stage sets' scene records that upload_scene_records rewrites: drop them all (and
+    // the last call, as every forget does: rendering ahead resumes once the caller has been seen to continue again)
+    d.schedule.forget();
+    for (int i = 0; i < DeviceState::kStageSets; i++)
+        if (d.launch_stream[i]) HIP_TRY(ctx, hipStreamSynchronize(d.launch_stream[i]));
     HIP_TRY(ctx, hipStreamSynchronize(d.stream));
     d.ds.image_color = d_color ? (float*)d_color : d.d_color;
     d.ds.image_ray_nb = d_count ? (float*)d_count : d.d_count;

@@ -3,7 +3,7 @@
 ptmi_setup_context caps the iterations of one launch so that its staging stays within 4 GiB: 32 up to about 6.7 M pixels,
 3 or fewer from about 53.7 M pixels on (8192 x 8192: 3, 16384 x 8192: 1).  Below a cap of four every launch of a call is
 SHORT - on a stream and a stage set of its own - which is where the stage sets used to be left unallocated
-(csrc/stage_sets.h, tests/test_stage_sets_model.py).  PTMI_ITERATIONS_PER_LAUNCH lowers the cap of a small image to reach
+(csrc/stage_sets.h, csrc/launch_schedule.h, tests/test_launch_schedule_model.py).  PTMI_ITERATIONS_PER_LAUNCH lowers the cap of a small image to reach
 those plans cheaply; the last two tests render at the sizes that take them without it.
 
 Every iteration's paths are deterministic and staged results are added in iteration order, so image bits, counts, histograms

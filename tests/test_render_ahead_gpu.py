@@ -124,6 +124,44 @@ def test_rendering_ahead_of_paths_that_are_given_up(monkeypatch):
     _same(_play(wild, w, h, d, long_run, DA, monkeypatch, ahead=2), _play(wild, w, h, d, long_run, DA, monkeypatch, ahead=0))
 
 
+def test_rendering_ahead_across_a_re_binding_of_the_accumulators(scene_factory, monkeypatch):
+    """ptmi_bind_accumulators in the middle of an in-order run of one image per call drops what ran ahead before it rewrites the
+    stage sets' scene records: the context's own accumulators before the binding, the torch-owned ones after it, the counters
+    and the own ones again after unbinding equal the run without rendering ahead, bit for bit."""
+    import torch
+    from opencl_pathtracer_amd.distributed import FusedAccumulators
+    scene, sampler, w, h, d = cases.CASES["cornell_64x48_d4"]
+    sc = scene_factory(scene, w, h)
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+
+    def run(ahead):
+        monkeypatch.setenv("PTMI_RENDER_AHEAD", str(ahead))
+        monkeypatch.delenv("PTMI_RENDER_AHEAD_CALLS", raising=False)
+        be = Backend().setup_context(w, h, d, sc.lightsSize, S.JITTERED, flags=DA)
+        try:
+            be.initialize_memory(sc)
+            for k in range(9):
+                be.render(k, 1)
+                be.synchronize()
+            before = be.read_image()
+            fb = FusedAccumulators(w, h, dev)
+            fb.bind(be)
+            for k in range(9, 20):
+                be.render(k, 1)
+                be.synchronize()
+            bound, counters = fb.images(), be.counters()
+            be.bind_accumulators(0, 0)
+            return before, bound, counters, be.read_image()
+        finally:
+            be.release()
+
+    a, b = run(2), run(0)
+    for x, y in ((a[0], b[0]), (a[1], b[1]), (a[3], b[3])):
+        assert np.array_equal(x[0].view(np.uint32), y[0].view(np.uint32)) and np.array_equal(x[1], y[1])
+    assert a[2] == b[2]
+
+
 @pytest.mark.parametrize("devices", [[0, 0], [0, 0, 0]], ids=["two", "three"])
 def test_rendering_ahead_per_device_in_a_multi_device_context(devices, scene_factory, monkeypatch):
     """A context of G devices gives device k the ids = k (mod G): a caller that asks for one image per call comes to each device
