@@ -3,14 +3,22 @@
 // merges - run on the host, one node after another.  tests/test_bvh_device_model.py compiles it with g++ and checks its
 // trees against ptmi_bvh_create, and where it flags a stale split.
 //
-//   int model_bvh_build(tris, n, nodes, perm, &size, &max_depth)
+//   int model_bvh_build_ex(tris, n, nodes, perm, &size, &max_depth, slot_seed, &levels)
+//   int model_bvh_build(tris, n, nodes, perm, &size, &max_depth)        (slot_seed 0, levels not reported)
 //     0: built - nodes[0 .. size) in pre-order; perm[i] = the input index of the triangle at position i
 //     1: a split whose axis was skipped at its node (the host builder uses an earlier node's scans there)
 //     2: a condition the host builder refuses the scene for (bin out of range, empty side, too deep)
 //     3: records the device does not fold (a NaN w, a box marked empty)
 // Like the device it stops at the first level that flags anything, a stale split ahead of an error.
+//
+// slot_seed: on the device a splitting node takes its two child slots from an atomic counter, so the order of a level's
+// nodes in the workspace is the order in which their workgroups got there.  slot_seed != 0 visits the open nodes of every
+// level in a shuffled order (and so hands out the slots in that order); 0 visits them in slot order.  The output must not
+// depend on it: the sizes and pre-order passes below are the device's (k_sizes, k_preorder, k_emit), level by level over
+// the slot-indexed arrays.  levels: the number of k_level launches the device makes (ptmi_bvh_build_info.levels).
 #include <cmath>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "bvh_build_common.h"
@@ -42,10 +50,25 @@ PBox fold_centroids(const ptmi_float4* cen, const std::vector<uint32_t>& perm, u
     return red[0];
 }
 
+constexpr uint32_t kThreads = 256;  // k_level's workgroup: the partition ranks positions in batches of this many
+
+// the order in which the open nodes [begin, end) of a level get to their child slots
+std::vector<size_t> visit_order(size_t begin, size_t end, uint64_t* rng)
+{
+    std::vector<size_t> order(end - begin);
+    for (size_t i = 0; i < order.size(); i++) order[i] = begin + i;
+    if (*rng == 0) return order;
+    for (size_t i = order.size(); i > 1; i--) {  // Fisher-Yates on a 64-bit LCG
+        *rng = *rng * 6364136223846793005ull + 1442695040888963407ull;
+        std::swap(order[i - 1], order[(size_t)((*rng >> 33) % i)]);
+    }
+    return order;
+}
+
 }  // namespace
 
-extern "C" int model_bvh_build(const ptmi_triangle* tris, uint32_t n, ptmi_node* out, uint32_t* perm_out, uint32_t* size_out,
-                               uint32_t* depth_out)
+extern "C" int model_bvh_build_ex(const ptmi_triangle* tris, uint32_t n, ptmi_node* out, uint32_t* perm_out, uint32_t* size_out,
+                                  uint32_t* depth_out, uint32_t slot_seed, uint32_t* levels_out)
 {
     std::vector<ptmi_float4> pmin(n), pmax(n), cen(n);
     PBox full_tri = pbox_empty(), full_cen = pbox_empty();
@@ -62,10 +85,14 @@ extern "C" int model_bvh_build(const ptmi_triangle* tris, uint32_t n, ptmi_node*
     nodes.push_back({ full_tri, full_cen, 0, n, 0, 0, -1, 0 });
     uint32_t max_depth = 0;
 
+    uint64_t rng = slot_seed ? 0x9E3779B97F4A7C15ull * slot_seed : 0;
+    std::vector<size_t> level_begin{ 0 };
+    uint32_t levels = 0;
     size_t begin = 0, end = 1;
     while (begin < end) {
         int flags = 0;
-        for (size_t self = begin; self < end; self++) {
+        levels++;
+        for (size_t self : visit_order(begin, end, &rng)) {
             MNode N = nodes[self];
             if (N.depth > kMaxBuildDepth) { flags |= 2; continue; }
             const int early = early_leaf(N.count, N.cen.p_min, N.cen.p_max);
@@ -114,20 +141,37 @@ extern "C" int model_bvh_build(const ptmi_triangle* tris, uint32_t n, ptmi_node*
             int lc, rc;
             split_sides(bins[axis], counts[axis], index, &lt, &lc, &rt, &rc);
             if (lc <= 0 || rc <= 0 || (uint32_t)lc + (uint32_t)rc != N.count) { flags |= 2; continue; }
-            // partition: the k-th right-going position in [first, mid) swaps with the k-th left-going one from the end
-            const uint32_t mid = first + (uint32_t)lc;
-            uint32_t pairs = 0;
-            for (uint32_t q = last + 1; q-- > mid;)
-                if (goes_left(scaled_pos(k1[axis], axis_of(cen[perm[q]], axis), lo[axis]), index)) scratch[first + pairs++] = q;
-            uint32_t rank = 0;
-            for (uint32_t p = first; p < mid; p++)
-                if (!goes_left(scaled_pos(k1[axis], axis_of(cen[perm[p]], axis), lo[axis]), index)) {
+            // partition, as k_level ranks it: the positions of the left-going triangles in [mid, last], counted from the end in
+            // batches of kThreads ...
+            const uint32_t mid = first + (uint32_t)lc, n_right = last - mid + 1, L = (uint32_t)lc;
+            uint32_t running = 0;
+            for (uint32_t off = 0; off < n_right; off += kThreads) {
+                uint32_t total = 0;
+                for (uint32_t t = 0; t < kThreads; t++) {
+                    const uint32_t k_off = off + t;
+                    if (k_off >= n_right) continue;
+                    const uint32_t q = last - k_off;
+                    if (goes_left(scaled_pos(k1[axis], axis_of(cen[perm[q]], axis), lo[axis]), index)) scratch[first + running + total++] = q;
+                }
+                running += total;
+            }
+            const uint32_t pairs = running;
+            // ... and the k-th right-going triangle in [first, mid) swaps with the k-th of them
+            running = 0;
+            for (uint32_t off = 0; off < L; off += kThreads) {
+                uint32_t total = 0;
+                for (uint32_t t = 0; t < kThreads; t++) {
+                    if (off + t >= L) continue;
+                    const uint32_t p = first + off + t, id = perm[p];
+                    if (goes_left(scaled_pos(k1[axis], axis_of(cen[id], axis), lo[axis]), index)) continue;
+                    const uint32_t rank = running + total++;
                     if (rank >= pairs) return 2;
-                    const uint32_t q = scratch[first + rank++];
-                    const uint32_t id = perm[p];
+                    const uint32_t q = scratch[first + rank];
                     perm[p] = perm[q];
                     perm[q] = id;
                 }
+                running += total;
+            }
             const PBox lcen = fold_centroids(cen.data(), perm, first, mid - 1, false);
             const PBox rcen = fold_centroids(cen.data(), perm, mid, last, true);
             nodes[self].cut_axis = (uint32_t)axis;
@@ -139,18 +183,23 @@ extern "C" int model_bvh_build(const ptmi_triangle* tris, uint32_t n, ptmi_node*
         if (flags & 2) return 2;
         begin = end;
         end = nodes.size();
+        level_begin.push_back(begin);
     }
 
-    // numbering: subtree sizes bottom-up, pre-order top-down
+    // numbering, level by level over the slot-indexed arrays: subtree sizes from the deepest level up (k_sizes), pre-order
+    // numbers from the root down (k_preorder: son1 = parent + 1, son2 = son1 + size(son1))
     const size_t total = nodes.size();
-    std::vector<uint32_t> size(total), pre(total, 0);
-    for (size_t i = total; i-- > 0;)
-        size[i] = nodes[i].leaf >= 0 ? 1u : 1u + size[nodes[i].child] + size[nodes[i].child + 1];
-    for (size_t i = 0; i < total; i++)
-        if (nodes[i].leaf < 0) {
-            pre[nodes[i].child] = pre[i] + 1;
-            pre[nodes[i].child + 1] = pre[i] + 1 + size[nodes[i].child];
-        }
+    std::vector<uint32_t> size(total), pre(total);
+    for (size_t l = level_begin.size() - 1; l-- > 0;)
+        for (size_t i = level_begin[l]; i < level_begin[l + 1]; i++)
+            size[i] = nodes[i].leaf >= 0 ? 1u : 1u + size[nodes[i].child] + size[nodes[i].child + 1];
+    pre[0] = 0;
+    for (size_t l = 0; l + 1 < level_begin.size(); l++)
+        for (size_t i = level_begin[l]; i < level_begin[l + 1]; i++)
+            if (nodes[i].leaf < 0) {
+                pre[nodes[i].child] = pre[i] + 1;
+                pre[nodes[i].child + 1] = pre[i] + 1 + size[nodes[i].child];
+            }
     for (size_t i = 0; i < total; i++) {
         const MNode& d = nodes[i];
         ptmi_node& o = out[pre[i]];
@@ -171,5 +220,12 @@ extern "C" int model_bvh_build(const ptmi_triangle* tris, uint32_t n, ptmi_node*
     std::memcpy(perm_out, perm.data(), sizeof(uint32_t) * n);
     *size_out = (uint32_t)total;
     *depth_out = max_depth;
+    if (levels_out) *levels_out = levels;
     return 0;
+}
+
+extern "C" int model_bvh_build(const ptmi_triangle* tris, uint32_t n, ptmi_node* out, uint32_t* perm_out, uint32_t* size_out,
+                               uint32_t* depth_out)
+{
+    return model_bvh_build_ex(tris, n, out, perm_out, size_out, depth_out, 0, nullptr);
 }

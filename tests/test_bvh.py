@@ -6,6 +6,12 @@
   (tests/golden/bvh_reference_trees.json);
 * everywhere: committed digests of trees that were checked against the reference when they were made
   (tests/golden/bvh_digests.json).  Generator of both: this file run as a script where libref_bvh.so exists.
+
+The small cases of bvh_stress_cases.py (ties, lattices, duplicates, sorted input, clusters, chains) go through all three:
+the device builder is compared with this builder, so this builder is compared with the reference's on the same geometry.
+One of them is a tree of 300 levels.  The reference's builder knows no depth limit and builds it; the product's refuses
+trees deeper than 8 x PTMI_BVH_MAX_DEPTH.  bvh_reference_trees.json records such a case as {"refused": <the product's
+error code>, "reference_max_depth": <the depth of the reference's tree>} instead of a digest.
 """
 import hashlib
 import json
@@ -16,6 +22,7 @@ import numpy as np
 import pytest
 
 sys.path[:0] = [os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__))]
+import bvh_stress_cases as stress
 import oracle_ffi as O
 from opencl_pathtracer_amd import scenes, bvh_create, structs as S, PtmiError
 
@@ -166,6 +173,39 @@ def test_fuzzed_scenes_match_reference_builder(seed, built):
         assert_same_as_reference(ref, sc)
 
 
+def stress_key(case):
+    return "stress_" + stress.case_id(case)
+
+
+def _stress_scene(case):
+    sc = scenes.cornell_box(8, 8)
+    sc.triangulation = stress.make(*case)
+    return sc
+
+
+@pytest.mark.parametrize("case", [c for c in stress.SMALL if c[0] != stress.REFUSED], ids=stress.case_id)
+def test_stress_cases_match_reference_builder(case, built):
+    """Tied and structured geometry: the reference builder's tree (or its digest), and the committed digest."""
+    sc = _stress_scene(case)
+    ref = reference_tree(stress_key(case), sc.triangulation)
+    bvh_create(sc)
+    assert_same_as_reference(ref, sc)
+    assert digest(sc) == json.load(open(GOLDEN))[stress_key(case)]
+
+
+@pytest.mark.parametrize("case", [c for c in stress.SMALL if c[0] == stress.REFUSED], ids=stress.case_id)
+def test_stress_case_deeper_than_the_limit_is_refused(case, built):
+    """A chain of 300 levels: the reference builds it, that deep; the product refuses it with PTMI_ERR_BAD_SCENE."""
+    sc = _stress_scene(case)
+    recorded = json.load(open(REF_TREES))[stress_key(case)]
+    assert recorded["refused"] == -5 and recorded["reference_max_depth"] == 300
+    if O.have_ref_bvh():
+        assert O.ref_bvh_create(sc.triangulation)[2] == recorded["reference_max_depth"]
+    with pytest.raises(PtmiError, match="too large to build a tree from") as e:
+        bvh_create(sc)
+    assert e.value.code == recorded["refused"]
+
+
 @pytest.mark.parametrize("value", [np.nan, np.inf, -np.inf, 3e38])
 def test_boxes_that_are_not_numbers_are_an_error_not_a_fault(value, built):
     """The reference's builder ASSERTs on them (BVH.cpp:199: a bin index out of range; without assertions it writes out of
@@ -255,6 +295,15 @@ if __name__ == "__main__":  # regenerate the digests (only meaningful where the 
             assert_same_tree(*ref, sc)
         out[name] = digest(sc)
         print(name, out[name])
+    for case in stress.SMALL:
+        if case[0] != stress.REFUSED:
+            sc = _stress_scene(case)
+            if O.have_ref_bvh():
+                ref = O.ref_bvh_create(sc.triangulation)
+            bvh_create(sc)
+            if O.have_ref_bvh():
+                assert_same_tree(*ref, sc)
+            out[stress_key(case)] = digest(sc)
     json.dump(out, open(GOLDEN, "w"), indent=1, sort_keys=True)
     if O.have_ref_bvh():  # the reference builder's own trees, hashed (each one checked against the product's first)
         import warnings
@@ -263,6 +312,7 @@ if __name__ == "__main__":  # regenerate the digests (only meaningful where the 
         inputs += [("coincident40", _coincident_stack)]
         inputs += [(f"fuzz{s}{x}_l1", lambda s=s, x=x: scenes.build(f"fuzz{s}{x}_l1", 64, 64).triangulation)
                    for s in range(0, 60, 3) for x in ("", "h", "r", "hr")]
+        inputs += [(stress_key(case), lambda case=case: stress.make(*case)) for case in stress.SMALL if case[0] != stress.REFUSED]
         trees = {}
         for key, make in inputs:
             with warnings.catch_warnings():
@@ -275,4 +325,11 @@ if __name__ == "__main__":  # regenerate the digests (only meaningful where the 
             assert_same_tree(*ref, sc)
             trees[key] = tree_digest(*ref)
             assert tree_digest(sc.bvh, sc.triangulation, sc.bvhMaxDepth) == trees[key], key
+        for case in stress.SMALL:
+            if case[0] == stress.REFUSED:  # the reference builds it; the product refuses trees that deep
+                sc = _stress_scene(case)
+                depth = O.ref_bvh_create(sc.triangulation)[2]
+                with pytest.raises(PtmiError) as e:
+                    bvh_create(sc)
+                trees[stress_key(case)] = {"refused": e.value.code, "reference_max_depth": int(depth)}
         json.dump(trees, open(REF_TREES, "w"), indent=1, sort_keys=True)

@@ -7,8 +7,9 @@ import numpy as np
 import pytest
 
 from opencl_pathtracer_amd import backend, scenes, structs as S, bvh_create
-from test_bvh_device_model import (FUZZ_NAMES, WALL_SEEDS, MODEL_STALE, cloud_wall, signed_zero_tris, small_tris,
-                                   coincident_stack, host_build, model)  # noqa: F401  (model: a fixture)
+import bvh_stress_cases as stress
+from test_bvh_device_model import (FUZZ_NAMES, WALL_SEEDS, MODEL_STALE, MODEL_BUILT, cloud_wall, signed_zero_tris, small_tris,
+                                   coincident_stack, host_build, assert_case_hits_its_target, model)  # noqa: F401  (model: a fixture)
 
 pytestmark = pytest.mark.gpu
 DEVICE = 0
@@ -27,9 +28,10 @@ def device_build(tris, device=DEVICE):
     return rc, msg, nodes[:size.value], t, depth.value, info
 
 
-def assert_same(tris, what, on_device=True):
+def assert_same(tris, what, on_device=True, host=None):
+    """`host`: host_build(tris), where the caller has it already"""
     rc, msg, nodes, t, depth, info = device_build(tris)
-    hrc, hmsg, hnodes, ht, hdepth = host_build(tris)
+    hrc, hmsg, hnodes, ht, hdepth = host or host_build(tris)
     assert (rc, msg) == (hrc, hmsg), what
     if on_device:
         assert info.built_on_device == 1 and info.fallback == backend.BVH_FALLBACK_NONE, (what, info.as_dict())
@@ -73,6 +75,120 @@ def test_cloud_and_wall_fall_back_exactly_where_the_model_flags(model):
         assert (info.built_on_device == 1) == (info.fallback == backend.BVH_FALLBACK_NONE), seed
         stale.append(flagged)
     assert any(stale)
+
+
+STRESS_BUILT = [c for c in stress.SMALL + stress.MID + stress.BIG if c[0] != stress.REFUSED]
+STRESS_REFUSED = [c for c in stress.SMALL + stress.MID + stress.BIG if c[0] == stress.REFUSED]
+
+
+def test_stress_table_has_a_device_built_case_in_every_row():
+    """Every case of STRESS_BUILT must be built on the device (the test below): a fallback would compare the host builder
+    with itself.  So no row of the family table may be missing from it."""
+    assert {stress.ROWS[c[0]] for c in STRESS_BUILT} == set(stress.ROWS.values())
+    for sizes in (stress.SMALL, stress.MID, stress.BIG):
+        assert {c[0] for c in sizes} == set(stress.FAMILIES)
+
+
+@pytest.mark.parametrize("case", STRESS_BUILT, ids=stress.case_id)
+def test_device_tree_equals_host_tree_on_stress_cases(case, model):
+    """Tied, structured and lopsided geometry at three sizes: built on the device with no fallback, the host's bytes, one
+    launch per level of the tree - and, at the small size, as many levels as the model takes."""
+    tris = stress.make(*case)
+    host = host_build(tris)
+    assert host[0] == 0, (case, host[1])
+    assert_case_hits_its_target(case, host[2], host[4])
+    info = assert_same(tris, case, host=host)
+    assert info.levels == host[4] + 1, (case, info.as_dict())
+    if case in stress.SMALL:
+        rc, nodes, perm, depth, levels = model(np.ascontiguousarray(tris), with_levels=True)
+        assert rc == MODEL_BUILT and info.levels == levels, (case, rc, levels, info.as_dict())
+
+
+@pytest.mark.parametrize("case", STRESS_REFUSED, ids=stress.case_id)
+def test_device_and_host_refuse_a_chain_deeper_than_the_limit(case):
+    """300 levels: the kernel flags the node past 8 x PTMI_BVH_MAX_DEPTH, the call hands the scene to the host builder, and the
+    caller gets the host builder's status and message."""
+    tris = stress.make(*case)
+    host = host_build(tris)
+    assert host[0] == -5 and "too large to build a tree from" in host[1], host[:2]
+    info = assert_same(tris, case, on_device=False, host=host)
+    assert info.built_on_device == 0 and info.fallback == backend.BVH_FALLBACK_HOST_ERROR, info.as_dict()
+
+
+@pytest.mark.parametrize("case", stress.STALE, ids=stress.case_id)
+def test_wide_flat_lattices_fall_back_exactly_where_the_model_flags(case, model):
+    """The two stress cases the device cannot build (bvh_stress_cases.STALE): the stale-axis fallback, as the model
+    flags it, and the host builder's status and message."""
+    tris = stress.make(*case)
+    info = assert_same(tris, case, on_device=False)
+    assert model(np.ascontiguousarray(tris))[0] == MODEL_STALE
+    assert info.built_on_device == 0 and info.fallback == backend.BVH_FALLBACK_STALE_AXIS, info.as_dict()
+
+
+def _repeat_cases():
+    return [("lattice", lambda: stress.make("grid3d", 1, 28 ** 3)), ("clusters", lambda: stress.make("clusters_exp", 0, 24000)),
+            ("random 300000", lambda: scenes.random_triangles(300000, 32, 32).triangulation)]
+
+
+@pytest.mark.parametrize("what,make", _repeat_cases(), ids=[w for w, _ in _repeat_cases()])
+def test_repeated_device_builds_give_the_same_bytes(what, make):
+    """The child slots of a level go to whichever workgroup asks first, so two builds of one scene lay their workspace out
+    differently.  Five builds in a row, and one more while a render is in flight on the same device: the same nodes, depth
+    and triangle order every time (and the host's)."""
+    tris = make()
+    host = host_build(tris)
+    assert host[0] == 0
+
+    def build():
+        rc, msg, nodes, t, depth, info = device_build(tris)
+        assert rc == 0 and info.built_on_device == 1 and info.fallback == backend.BVH_FALLBACK_NONE, (what, msg, info.as_dict())
+        return nodes.tobytes(), t.tobytes(), depth, info.levels
+
+    first = build()
+    assert first[:3] == (host[2].tobytes(), host[3].tobytes(), host[4]), what
+    for k in range(4):
+        assert build() == first, (what, k)
+    w, h = 96, 64
+    sc = bvh_create(scenes.build("matmix", w, h))
+    be = backend.Backend().setup_context(w, h, 6, len(sc.lights), device=DEVICE)
+    try:
+        be.initialize_memory(sc)
+        be.render(0, 8)
+        during = build()
+        be.synchronize()
+    finally:
+        be.release()
+    assert during == first, what
+
+
+def _before_the_largest_cluster(tris):
+    """four radii in front of the last (largest, radius 2^20) cluster of clusters_exp in construction order"""
+    return tris["AABB"]["centroid"][-(len(tris) // 41):, :3].astype(np.float64).mean(0) - [4 * 2.0 ** 20, 0, 0]
+
+
+@pytest.mark.parametrize("family,seed,n,eye", [("grid3d", 1, 28 ** 3, lambda tris: (-30.0, 13.5, 13.5)),
+                                               ("clusters_exp", 0, 24000, _before_the_largest_cluster)],
+                         ids=["grid3d", "clusters_exp"])
+def test_image_of_a_device_built_stress_scene_is_the_host_built_one(family, seed, n, eye):
+    """4 spp at 96 x 64 of a lattice and of the clusters, once with the device-built tree and once with the host-built one:
+    image, sample counts, histograms and counters are the same bytes."""
+    w, h, d, spp = 96, 64, 6, 4
+
+    def scene():
+        sc = scenes.random_triangles(16, w, h)  # its material, light and sky
+        sc.triangulation = stress.make(family, seed, n)
+        sc.cameraPosition, sc.cameraDirection, sc.cameraRight, sc.cameraUp = scenes.camera(eye(sc.triangulation), (1, 0, 0), (0, 1, 0), (0, 0, h / w))
+        return sc
+
+    on_host, on_device = bvh_create(scene()), bvh_create(scene(), device=DEVICE)
+    assert on_device.bvh_build_info.built_on_device == 1 and on_device.bvh_build_info.fallback == backend.BVH_FALLBACK_NONE
+    assert on_host.bvhMaxDepth < S.BVH_MAX_DEPTH  # (a tree the integrator takes)
+    a = backend.render_scene(on_host, w, h, d, spp, device=DEVICE)
+    b = backend.render_scene(on_device, w, h, d, spp, device=DEVICE)
+    assert a[3]["surface_hits"] > 100  # (an image of the geometry, not of the sky)
+    for x, y in zip(a[:2] + tuple(a[2]), b[:2] + tuple(b[2])):
+        assert np.asarray(x).tobytes() == np.asarray(y).tobytes()
+    assert a[3] == b[3]
 
 
 @pytest.mark.parametrize("value", [np.nan, np.inf, -np.inf, 3e38, -3e38])

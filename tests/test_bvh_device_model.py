@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from opencl_pathtracer_amd import backend, scenes, bvh_create, structs as S, PtmiError
+import bvh_stress_cases as stress
 import test_bvh
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -102,16 +103,20 @@ def model(tmp_path_factory):
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     lib = C.CDLL(so)
-    lib.model_bvh_build.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    lib.model_bvh_build_ex.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                       C.c_uint32, C.POINTER(C.c_uint32)]
 
-    def run(tris):
+    def run(tris, slot_seed=0, with_levels=False):
+        """slot_seed: the order in which a level's nodes take their child slots (0: in slot order); with_levels: also
+        return the number of levels, ptmi_bvh_build_info.levels of the device build."""
         n = len(tris)
         nodes = np.zeros(max(2 * n - 1, 1), dtype=S.Node)
         perm = np.zeros(n, np.uint32)
-        size, depth = C.c_uint32(0), C.c_uint32(0)
-        rc = lib.model_bvh_build(tris.ctypes.data_as(C.c_void_p), n, nodes.ctypes.data_as(C.c_void_p),
-                                 perm.ctypes.data_as(C.c_void_p), C.byref(size), C.byref(depth))
-        return rc, nodes[:size.value], perm, depth.value
+        size, depth, levels = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        rc = lib.model_bvh_build_ex(tris.ctypes.data_as(C.c_void_p), n, nodes.ctypes.data_as(C.c_void_p),
+                                    perm.ctypes.data_as(C.c_void_p), C.byref(size), C.byref(depth), slot_seed, C.byref(levels))
+        out = (rc, nodes[:size.value], perm, depth.value)
+        return out + (levels.value,) if with_levels else out
     return run
 
 
@@ -148,6 +153,71 @@ def test_model_equals_host_builder_on_small_counts(model, built):
     assert_model_equals_host(model, coincident_stack(), "coincident stack")
 
 
+STRESS_SMALL = [c for c in stress.SMALL if c[0] != stress.REFUSED]
+STRESS_REFUSED = [c for c in stress.SMALL if c[0] == stress.REFUSED]
+SLOT_SEEDS = (1, 2, 3, 5, 8, 13)
+
+
+def root_counts(nodes):
+    """(left, right) triangle counts of the root's split"""
+    left = int(nodes[int(nodes[0]["son2Id"])]["triangleStartIndex"])
+    return left, int(nodes[0]["nbTriangles"]) - left
+
+
+def assert_case_hits_its_target(case, nodes, depth):
+    """A stress case that promises a count or a depth must really have it: checked on the host builder's tree."""
+    family, seed, n = case
+    target = stress.sized_target(family)
+    if target:
+        assert nodes[0]["isLeaf"] == 0 and root_counts(nodes)[0 if target[0] == "L" else 1] == target[1], (case, root_counts(nodes))
+    if family.startswith("deep_chain_"):
+        assert depth == int(family.split("_")[2]), (case, depth)
+
+
+@pytest.mark.parametrize("case", STRESS_SMALL, ids=stress.case_id)
+def test_model_equals_host_builder_on_stress_cases(model, built, case):
+    """Tied, structured and lopsided geometry (bvh_stress_cases.py): the model builds every case (no stale split, no error),
+    its tree is the host's, and it takes as many levels as the tree is deep."""
+    tris = stress.make(*case)
+    assert_model_equals_host(model, tris, case)
+    rc, nodes, perm, depth, levels = model(tris, with_levels=True)
+    assert levels == depth + 1, (case, levels, depth)
+    assert_case_hits_its_target(case, nodes, depth)
+
+
+@pytest.mark.parametrize("case", STRESS_SMALL, ids=stress.case_id)
+def test_model_does_not_depend_on_slot_order(model, built, case):
+    """The device hands a level's child slots out in the order the workgroups ask for them.  Whatever that order, the nodes
+    (numbered in pre-order at the end) and the triangle order are the same bytes."""
+    tris = stress.make(*case)
+    rc0, nodes0, perm0, depth0, levels0 = model(tris, with_levels=True)
+    assert rc0 == MODEL_BUILT
+    for seed in SLOT_SEEDS:
+        rc, nodes, perm, depth, levels = model(tris, slot_seed=seed, with_levels=True)
+        assert (rc, depth, levels) == (rc0, depth0, levels0), (case, seed)
+        assert nodes.tobytes() == nodes0.tobytes() and perm.tobytes() == perm0.tobytes(), (case, seed)
+
+
+@pytest.mark.parametrize("case", STRESS_REFUSED, ids=stress.case_id)
+def test_model_and_host_refuse_a_chain_deeper_than_the_limit(model, built, case):
+    """300 levels: the host builder refuses past 8 x PTMI_BVH_MAX_DEPTH, and the model flags the same condition, in every
+    slot order."""
+    tris = stress.make(*case)
+    hrc, msg, hnodes, htris, hdepth = host_build(tris)
+    assert hrc == -5 and "too large to build a tree from" in msg, (hrc, msg)  # PTMI_ERR_BAD_SCENE
+    for seed in (0,) + SLOT_SEEDS:
+        assert model(tris, slot_seed=seed)[0] == MODEL_ERROR, seed
+
+
+@pytest.mark.parametrize("case", stress.STALE, ids=stress.case_id)
+def test_model_flags_the_stale_axis_of_wide_flat_lattices(model, built, case):
+    """Flat lattices so wide that every real cost at the root is above the INT_MAX of the skipped axis: the model flags the
+    stale split (the host builder, splitting with scans it never made, refuses the scene)."""
+    tris = stress.make(*case)
+    assert model(tris)[0] == MODEL_STALE
+    assert host_build(tris)[0] == -5
+
+
 def test_model_flags_the_stale_splits_of_cloud_and_wall(model, built):
     """Where the model does not flag a seed, its tree is the host's (or both refuse the scene); it flags some seeds, and
     among them the host builds some and refuses others."""
@@ -167,7 +237,8 @@ def test_model_flags_the_stale_splits_of_cloud_and_wall(model, built):
 
 
 def test_model_under_sanitizers(tmp_path, built):
-    """The model compiled with -fsanitize=address,undefined, run once over the fuzzed scenes and a cloud + wall scene."""
+    """The model compiled with -fsanitize=address,undefined, run once over the fuzzed scenes, a cloud + wall scene, the signed
+    zeros and the small stress cases (the refused chain among them)."""
     gxx = shutil.which("g++")
     if not gxx:
         pytest.skip("g++ not installed")
@@ -203,7 +274,8 @@ int main(int argc, char** argv) {
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     files = []
-    for i, t in enumerate([scenes.build(nm, 32, 32).triangulation for nm in FUZZ_NAMES[::5]] + [cloud_wall(0), signed_zero_tris()]):
+    for i, t in enumerate([scenes.build(nm, 32, 32).triangulation for nm in FUZZ_NAMES[::5]] + [cloud_wall(0), signed_zero_tris()] +
+                          [stress.make(*case) for case in stress.SMALL]):
         p = tmp_path / f"s{i}.bin"
         p.write_bytes(np.ascontiguousarray(t).tobytes())
         files.append(str(p))

@@ -585,7 +585,7 @@ def _record_north_star(case, spp, rms, floor):
     out_dir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
     if not os.path.isdir(out_dir):
         return
-    path = os.path.join(out_dir, "r03_north_star_rms.json")
+    path = os.path.join(out_dir, "north_star_rms.json")
     data = json.load(open(path)) if os.path.exists(path) else {}
     data[case] = {"spp": spp, "rms_default_arithmetic_mode_vs_reference_default_build": [float(x) for x in rms],
                   "rms_strict_mode_vs_reference_default_build": None if floor is None else [float(x) for x in floor]}
