@@ -1,9 +1,9 @@
-// bvh_build_common.h - the per-node arithmetic of the binned-SAH builder, shared by the device builder
-// (bvh_build_device.hip) and its serial model (tests/bvh_device_model.cpp).
+// bvh_build_common.h - the per-node arithmetic of the binned-SAH builder, shared by the host builder (bvh_build.cpp), the
+// device builder (bvh_build_device.hip) and its serial model (tests/bvh_device_model.cpp).
 //
-// Every function here makes the decision Builder::build (bvh_build.cpp) makes at one node, operation for operation: the
-// same float / double mix, the same order of the box unions.  What the level-synchronous schedule adds on top is the
-// order in which partial results are combined, and that is what PBox is for:
+// Every function here makes the decision the reference's BVH_BuildStructure makes at one node, operation for operation:
+// the same float / double mix, the same order of the box unions.  The three builders differ in their schedule only: the
+// order in which they visit nodes and combine partial results, and that is what PBox is for:
 //
 //   std::min<float>(a, b) is (b < a) ? b : a - of values that compare equal (-0 and +0) it keeps the one it saw first.  A
 //   fold of boxes in a fixed index order is therefore "the first occurrence of the minimum", which is associative: partial
@@ -20,6 +20,7 @@
 #define PTMI_BVH_BUILD_COMMON_H
 
 #include <climits>
+#include <cmath>
 #include <cstdint>
 
 #include "ptmi_scene.h"
@@ -105,6 +106,15 @@ PTMI_HD PBox pbox_merge(const PBox& first, const PBox& second)
 
 // the centroid the serial fold leaves: the single box's own, else the midpoint of the corners
 PTMI_HD ptmi_float4 pbox_centroid(const PBox& b) { return b.n == 1 ? b.centroid : mid4(b.p_min, b.p_max); }
+
+// A folded box as the BoundingBox the serial fold leaves (the fields only: the caller zeroes the padding).  A box that took
+// nothing is marked empty and keeps the corners and centroid it holds, as BoundingBox_Reset does.
+PTMI_HD void pbox_store(const PBox& b, ptmi_bounding_box* out)
+{
+    out->p_min = b.p_min; out->p_max = b.p_max;
+    out->centroid = b.n == 0 ? b.centroid : pbox_centroid(b);
+    out->is_empty = b.n == 0;
+}
 
 // BoundingBox_Area: float products and sums, widened on return
 PTMI_HD double half_area(const ptmi_float4& p_min, const ptmi_float4& p_max)
@@ -192,6 +202,33 @@ PTMI_HD void best_split(const float* sah, int* best_axis, int* best_index, float
 PTMI_HD bool sah_leaf(float best_sah, uint32_t nb_triangles, const ptmi_float4& tri_min, const ptmi_float4& tri_max)
 {
     return kKI * best_sah + kKT > nb_triangles * half_area(tri_min, tri_max);
+}
+
+// The record screen and the root of every builder, in one walk over the triangles in index order (BVH_Create: UniteWith
+// into the triangles' box - a box marked empty is skipped -, AddPoint into the centroids').  The walk ends at the first
+// record with a non-finite number among the nine the builders read: no builder takes such a scene.  each(i, aabb) is
+// called for every record before that.
+struct RootFold {
+    PBox tri, cen;
+    bool refused;    // record `index` is not finite; tri and cen stop short of it
+    uint32_t index;
+    bool unfolded;   // a record walked is one the device does not fold: a box marked empty, a NaN w
+};
+template <class Each>
+inline RootFold fold_records(const ptmi_triangle* tris, uint32_t n, Each each)
+{
+    RootFold r = { pbox_empty(), pbox_empty(), false, 0, false };
+    for (uint32_t i = 0; i < n; i++) {
+        const ptmi_bounding_box& a = tris[i].aabb;
+        const float v[9] = { a.p_min.x, a.p_min.y, a.p_min.z, a.p_max.x, a.p_max.y, a.p_max.z, a.centroid.x, a.centroid.y, a.centroid.z };
+        for (float f : v)
+            if (!std::isfinite(f)) { r.refused = true; r.index = i; return r; }
+        if (a.is_empty || std::isnan(a.p_min.w) || std::isnan(a.p_max.w) || std::isnan(a.centroid.w)) r.unfolded = true;
+        if (!a.is_empty) pbox_unite(r.tri, a.p_min, a.p_max, a.centroid);
+        pbox_add_point(r.cen, a.centroid);
+        each(i, a);
+    }
+    return r;
 }
 
 }  // namespace ptmi_bvh

@@ -534,27 +534,20 @@ extern "C" int ptmi_bvh_create_device(int32_t device, ptmi_triangle* triangulati
         return finish(PTMI_ERR_NO_DEVICE);
     }
 
-    // The boxes the device folds, and the root (BVH_Create: unite / add_point over the triangles in order).  Records the
-    // host builder refuses go to it for its message; records the device does not fold go to it for the tree.
+    // The boxes the device folds, and the root.  Records the host builder refuses go to it for its message; records the
+    // device does not fold go to it for the tree; whichever comes first in index order.
     std::vector<ptmi_float4> boxes(3 * (size_t)n);
-    PBox full_tri = pbox_empty(), full_cen = pbox_empty();
-    for (uint32_t i = 0; i < n; i++) {
-        const ptmi_bounding_box& a = triangulation[i].aabb;
-        const float v[9] = { a.p_min.x, a.p_min.y, a.p_min.z, a.p_max.x, a.p_max.y, a.p_max.z, a.centroid.x, a.centroid.y, a.centroid.z };
-        for (float f : v)
-            if (!std::isfinite(f)) return on_host(PTMI_BVH_FALLBACK_HOST_ERROR);
-        if (a.is_empty || std::isnan(a.p_min.w) || std::isnan(a.p_max.w) || std::isnan(a.centroid.w))
-            return on_host(PTMI_BVH_FALLBACK_RECORDS);
+    const RootFold fold = fold_records(triangulation, n, [&](uint32_t i, const ptmi_bounding_box& a) {
         boxes[3 * (size_t)i] = a.p_min;
         boxes[3 * (size_t)i + 1] = a.p_max;
         boxes[3 * (size_t)i + 2] = a.centroid;
-        pbox_unite(full_tri, a.p_min, a.p_max, a.centroid);
-        pbox_add_point(full_cen, a.centroid);
-    }
+    });
+    if (fold.unfolded) return on_host(PTMI_BVH_FALLBACK_RECORDS);
+    if (fold.refused) return on_host(PTMI_BVH_FALLBACK_HOST_ERROR);
     DevNode root;
     std::memset(&root, 0, sizeof root);
-    root.t_min = full_tri.p_min; root.t_max = full_tri.p_max; root.t_cen = pbox_centroid(full_tri);
-    root.c_min = full_cen.p_min; root.c_max = full_cen.p_max; root.c_cen = pbox_centroid(full_cen);
+    root.t_min = fold.tri.p_min; root.t_max = fold.tri.p_max; root.t_cen = pbox_centroid(fold.tri);
+    root.c_min = fold.cen.p_min; root.c_max = fold.cen.p_max; root.c_cen = pbox_centroid(fold.cen);
     root.start = 0; root.count = n; root.leaf = -1;
 
     DeviceBuild b;

@@ -7,7 +7,7 @@
 //   int model_bvh_build(tris, n, nodes, perm, &size, &max_depth)        (slot_seed 0, levels not reported)
 //     0: built - nodes[0 .. size) in pre-order; perm[i] = the input index of the triangle at position i
 //     1: a split whose axis was skipped at its node (the host builder uses an earlier node's scans there)
-//     2: a condition the host builder refuses the scene for (bin out of range, empty side, too deep)
+//     2: a condition the host builder refuses the scene for (a box that is not finite, bin out of range, empty side, too deep)
 //     3: records the device does not fold (a NaN w, a box marked empty)
 // Like the device it stops at the first level that flags anything, a stale split ahead of an error.
 //
@@ -16,7 +16,6 @@
 // level in a shuffled order (and so hands out the slots in that order); 0 visits them in slot order.  The output must not
 // depend on it: the sizes and pre-order passes below are the device's (k_sizes, k_preorder, k_emit), level by level over
 // the slot-indexed arrays.  levels: the number of k_level launches the device makes (ptmi_bvh_build_info.levels).
-#include <cmath>
 #include <cstring>
 #include <utility>
 #include <vector>
@@ -71,18 +70,15 @@ extern "C" int model_bvh_build_ex(const ptmi_triangle* tris, uint32_t n, ptmi_no
                                   uint32_t* depth_out, uint32_t slot_seed, uint32_t* levels_out)
 {
     std::vector<ptmi_float4> pmin(n), pmax(n), cen(n);
-    PBox full_tri = pbox_empty(), full_cen = pbox_empty();
-    for (uint32_t i = 0; i < n; i++) {
-        const ptmi_bounding_box& a = tris[i].aabb;
-        if (a.is_empty || std::isnan(a.p_min.w) || std::isnan(a.p_max.w) || std::isnan(a.centroid.w)) return 3;
+    const RootFold fold = fold_records(tris, n, [&](uint32_t i, const ptmi_bounding_box& a) {
         pmin[i] = a.p_min; pmax[i] = a.p_max; cen[i] = a.centroid;
-        pbox_unite(full_tri, a.p_min, a.p_max, a.centroid);
-        pbox_add_point(full_cen, a.centroid);
-    }
+    });
+    if (fold.unfolded) return 3;
+    if (fold.refused) return 2;
     std::vector<uint32_t> perm(n), scratch(n);
     for (uint32_t i = 0; i < n; i++) perm[i] = i;
     std::vector<MNode> nodes;
-    nodes.push_back({ full_tri, full_cen, 0, n, 0, 0, -1, 0 });
+    nodes.push_back({ fold.tri, fold.cen, 0, n, 0, 0, -1, 0 });
     uint32_t max_depth = 0;
 
     uint64_t rng = slot_seed ? 0x9E3779B97F4A7C15ull * slot_seed : 0;
@@ -204,8 +200,8 @@ extern "C" int model_bvh_build_ex(const ptmi_triangle* tris, uint32_t n, ptmi_no
         const MNode& d = nodes[i];
         ptmi_node& o = out[pre[i]];
         std::memset(&o, 0, sizeof o);
-        o.triangles_aabb.p_min = d.tri.p_min; o.triangles_aabb.p_max = d.tri.p_max; o.triangles_aabb.centroid = pbox_centroid(d.tri);
-        o.centroids_aabb.p_min = d.cen.p_min; o.centroids_aabb.p_max = d.cen.p_max; o.centroids_aabb.centroid = pbox_centroid(d.cen);
+        pbox_store(d.tri, &o.triangles_aabb);
+        pbox_store(d.cen, &o.centroids_aabb);
         o.triangle_start_index = d.start;
         o.nb_triangles = d.count;
         if (d.leaf >= 0) {

@@ -50,12 +50,12 @@ def assert_same_tree(ref_nodes, ref_tris, ref_depth, sc):
     assert len(ref_nodes) == len(sc.bvh) and ref_depth == sc.bvhMaxDepth
     for f in NODE_FIELDS:
         assert np.array_equal(ref_nodes[f], sc.bvh[f]), f
+    bits = lambda x: np.ascontiguousarray(x).view(np.uint32) if x.dtype == np.float32 else x  # (a zero-area triangle's N is NaN)
     for bb in ("trianglesAABB", "centroidsAABB"):
-        for f in ("pMin", "pMax", "centroid", "isEmpty"):
-            assert np.array_equal(ref_nodes[bb][f], sc.bvh[bb][f]), (bb, f)
+        for f in ("pMin", "pMax", "centroid", "isEmpty"):  # (bit for bit: a NaN w reaches the boxes, and -0 is not +0)
+            assert np.array_equal(bits(ref_nodes[bb][f]), bits(sc.bvh[bb][f])), (bb, f)
     leaf = ref_nodes["isLeaf"] != 0
     assert np.array_equal(ref_nodes["comments"][leaf], sc.bvh["comments"][leaf])
-    bits = lambda x: np.ascontiguousarray(x).view(np.uint32) if x.dtype == np.float32 else x  # (a zero-area triangle's N is NaN)
     for f in S.Triangle.names:  # field-wise: the reference's member-wise swap does not move padding bytes
         a, b = ref_tris[f], sc.triangulation[f]
         if a.dtype.names:
@@ -206,6 +206,89 @@ def test_stress_case_deeper_than_the_limit_is_refused(case, built):
     assert e.value.code == recorded["refused"]
 
 
+# cloud + wall scenes (test_bvh_device_model.cloud_wall) in which the SAH picks an axis that was skipped at its node, and
+# which the host builder builds: it splits there with k1 and the scans an earlier node left behind (BVH.cpp:154-161).
+STALE_AXIS_SEEDS = (4, 7, 14, 27, 30, 36)
+
+
+@pytest.fixture(scope="module")
+def device_model(tmp_path_factory):
+    import test_bvh_device_model as M  # (it imports this module: not at the top)
+    return M.build_model(tmp_path_factory.mktemp("bvh_model"))
+
+
+def _build_and_compare(key, tris):
+    sc = scenes.cornell_box(8, 8)
+    sc.triangulation = tris
+    ref = reference_tree(key, tris)
+    bvh_create(sc)
+    assert_same_as_reference(ref, sc)
+    return sc
+
+
+@pytest.mark.parametrize("seed", STALE_AXIS_SEEDS)
+def test_stale_axis_splits_match_reference_builder(seed, built, device_model):
+    """Only the host builder implements the split on a skipped axis (the device and the model hand such scenes to it): the
+    reference builder's tree, field for field.  The model must flag the scene, so that the case cannot stop taking that path."""
+    import test_bvh_device_model as M
+    tris = M.cloud_wall(seed)
+    assert device_model(np.ascontiguousarray(tris))[0] == M.MODEL_STALE
+    _build_and_compare(f"cloud_wall{seed}", tris)
+
+
+def _empty_twins():
+    """150 triangles, and the first 40 again with their boxes marked empty: a twin falls into its original's bin at every
+    node, so no side of any split holds empty boxes alone."""
+    t = _random_soup(150, 901)
+    twins = t[:40].copy()
+    twins["AABB"]["isEmpty"] = 1
+    return scenes._concat_tris([t, twins])
+
+
+def _nan_w():
+    t = _random_soup(300, 903)
+    rs = np.random.RandomState(4)
+    for f in ("pMin", "pMax", "centroid"):
+        t["AABB"][f][rs.choice(300, 25, replace=False), 3] = np.nan
+    return t
+
+
+def _empty_third():
+    t = _random_soup(300, 902)
+    t["AABB"]["isEmpty"][np.random.RandomState(3).rand(300) < 0.3] = 1
+    return t
+
+
+RECORD_CASES = {"records_empty_twins": _empty_twins, "records_nan_w": _nan_w}
+
+
+@pytest.mark.parametrize("key", sorted(RECORD_CASES))
+def test_records_the_device_refuses_match_reference_builder(key, built, device_model):
+    """Boxes marked empty (counted in their bin, never united) and NaN w components (they stop a min / max fold where it
+    stands): the device builder hands both to the host builder, whose tree must be the reference builder's."""
+    import test_bvh_device_model as M
+    tris = RECORD_CASES[key]()
+    assert device_model(np.ascontiguousarray(tris))[0] == M.MODEL_RECORDS
+    sc = _build_and_compare(key, tris)
+    if key == "records_nan_w":
+        assert np.isnan(sc.bvh["trianglesAABB"]["pMin"][:, 3]).any() and np.isnan(sc.bvh["centroidsAABB"]["pMax"][:, 3]).any()
+    else:
+        assert (sc.bvh["trianglesAABB"]["isEmpty"] == 0).all()
+
+
+def test_child_of_empty_boxes_alone_keeps_its_bytes(built):
+    """Three boxes in ten marked empty: some splits leave a side that holds such boxes alone.  Its node box is marked empty,
+    and its corners are whatever the bin after (or before) the split plane held the last time a box was united into it - at an
+    earlier node.  In the reference's builder those arrays are function-level statics that outlive a call, so its bytes there
+    depend on the builds the process made before; the product's scratch starts at zero in every call.  Pinned here: the
+    product's own tree, as the builder wrote it before it was moved onto bvh_build_common.h."""
+    sc = scenes.cornell_box(8, 8)
+    sc.triangulation = _empty_third()
+    bvh_create(sc)
+    assert (sc.bvh["trianglesAABB"]["isEmpty"] != 0).sum() == 4 and len(sc.bvh) == 193
+    assert tree_digest(sc.bvh, sc.triangulation, sc.bvhMaxDepth) == "3bc3f3abde81d8b80b05d1631a64dc6a5150beb94b1ad47eceddfa57d228a094"
+
+
 @pytest.mark.parametrize("value", [np.nan, np.inf, -np.inf, 3e38])
 def test_boxes_that_are_not_numbers_are_an_error_not_a_fault(value, built):
     """The reference's builder ASSERTs on them (BVH.cpp:199: a bin index out of range; without assertions it writes out of
@@ -313,6 +396,9 @@ if __name__ == "__main__":  # regenerate the digests (only meaningful where the 
         inputs += [(f"fuzz{s}{x}_l1", lambda s=s, x=x: scenes.build(f"fuzz{s}{x}_l1", 64, 64).triangulation)
                    for s in range(0, 60, 3) for x in ("", "h", "r", "hr")]
         inputs += [(stress_key(case), lambda case=case: stress.make(*case)) for case in stress.SMALL if case[0] != stress.REFUSED]
+        import test_bvh_device_model as M
+        inputs += [(f"cloud_wall{seed}", lambda seed=seed: M.cloud_wall(seed)) for seed in STALE_AXIS_SEEDS]
+        inputs += sorted(RECORD_CASES.items())
         trees = {}
         for key, make in inputs:
             with warnings.catch_warnings():

@@ -93,12 +93,11 @@ def host_build(tris):
     return rc, msg, nodes[:size.value], t, depth.value
 
 
-@pytest.fixture(scope="module")
-def model(tmp_path_factory):
+def build_model(tmp_dir):
     gxx = shutil.which("g++")
     if not gxx:
         pytest.skip("g++ not installed")
-    so = str(tmp_path_factory.mktemp("bvh_model") / "libbvh_model.so")
+    so = str(tmp_dir / "libbvh_model.so")
     r = subprocess.run([gxx, "-std=c++17", "-O2", "-fPIC", "-shared", *FP_FLAGS, *INCLUDES, MODEL_SRC, "-o", so],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -118,6 +117,11 @@ def model(tmp_path_factory):
         out = (rc, nodes[:size.value], perm, depth.value)
         return out + (levels.value,) if with_levels else out
     return run
+
+
+@pytest.fixture(scope="module")
+def model(tmp_path_factory):
+    return build_model(tmp_path_factory.mktemp("bvh_model"))
 
 
 def assert_model_equals_host(model, tris, what):
