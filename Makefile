@@ -2,12 +2,13 @@
 #   make lib      -> opencl_pathtracer_amd/lib/libptmi.so      (hipcc, cross-compiles without a GPU)
 #   make oracle   -> oracle/build/libpt_oracle.so              (gcc, CPU checker; test infrastructure)
 #   make ref      -> oracle/_ref/*                             (only where /root/reference exists)
+#   make lib LIBDIR=<dir> EXTRA="-DPTMI_WF_QUEUES=16"  -> <dir>/libptmi.so, a variant with tuning macros (tools/build_variants.sh)
 HIPCC      ?= /opt/rocm/bin/hipcc
 ARCH       ?= gfx950
 CSRC       := opencl_pathtracer_amd/csrc
 LIBDIR     := opencl_pathtracer_amd/lib
 # -ffp-contract=off: the numerics contract forbids fused multiply-add
-HIPFLAGS   := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Iinclude -I$(CSRC) -Wall -Wno-unused-function
+HIPFLAGS   := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Iinclude -I$(CSRC) -Wall -Wno-unused-function $(EXTRA)
 LIB_HDRS   := $(wildcard include/*.h) $(wildcard $(CSRC)/*.h) $(wildcard $(CSRC)/*.hpp) $(wildcard $(CSRC)/*.inc)
 OBJDIR     := $(LIBDIR)/obj
 # The integrator's device code is compiled once per arithmetic mode (ptmi_device.hpp): strict, and `_da` = the
@@ -52,4 +53,4 @@ clean:
 
 # register / LDS budget of both kernels (occupancy is VGPR-bound: read this after every kernel edit)
 resources:
-	@for f in kernels kernel_wavefront; do for m in 0 1; do $(HIPCC) $(HIPFLAGS) $(EXTRA) -DPTMI_DEFAULT_ARITHMETIC=$$m --cuda-device-only -c $(CSRC)/$$f.hip -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs:|ScratchSize|Occupancy|LDS Size|Spill" | sed 's/.*remark: *//' | tr '\n' ' '; echo; done; done
+	@for f in kernels kernel_wavefront; do for m in 0 1; do $(HIPCC) $(HIPFLAGS) -DPTMI_DEFAULT_ARITHMETIC=$$m --cuda-device-only -c $(CSRC)/$$f.hip -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs:|ScratchSize|Occupancy|LDS Size|Spill" | sed 's/.*remark: *//' | tr '\n' ' '; echo; done; done

@@ -78,12 +78,7 @@ namespace ptmi_internal {
 int launch_add_counters(unsigned long long* dst, const unsigned long long* src, uint32_t n, void* stream, std::string* err)
 {
     hipLaunchKernelGGL(ptmi_dev::add_counters_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, dst, src, n);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        if (err) *err = std::string("add_counters_kernel launch: ") + hipGetErrorString(e);
-        return PTMI_ERR_HIP;
-    }
-    return PTMI_OK;
+    return launch_status(hipGetLastError(), "add_counters_kernel", err);
 }
 
 int launch_sum_images(float* out, const float* const* parts, uint32_t n_parts, size_t n_floats, void* stream, std::string* err)
@@ -97,12 +92,7 @@ int launch_sum_images(float* out, const float* const* parts, uint32_t n_parts, s
     const size_t n_quads = n_floats / 4;
     hipLaunchKernelGGL(ptmi_dev::sum_images_kernel, dim3((unsigned)((n_quads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, ip,
                        n_parts, n_quads);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        if (err) *err = std::string("sum_images_kernel launch: ") + hipGetErrorString(e);
-        return PTMI_ERR_HIP;
-    }
-    return PTMI_OK;
+    return launch_status(hipGetLastError(), "sum_images_kernel", err);
 }
 
 int launch_display_bgr(const float* image_color, const float* image_ray_nb, uint8_t* out, uint32_t width, uint32_t height,
@@ -111,12 +101,7 @@ int launch_display_bgr(const float* image_color, const float* image_ray_nb, uint
     const dim3 grid((width + 255u) / 256u, height), block(256);
     hipLaunchKernelGGL(ptmi_dev::display_bgr_kernel, grid, block, 0, (hipStream_t)stream, image_color, image_ray_nb, out, width,
                        height, row_stride);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        if (err) *err = std::string("display_bgr_kernel launch: ") + hipGetErrorString(e);
-        return PTMI_ERR_HIP;
-    }
-    return PTMI_OK;
+    return launch_status(hipGetLastError(), "display_bgr_kernel", err);
 }
 
 }  // namespace ptmi_internal

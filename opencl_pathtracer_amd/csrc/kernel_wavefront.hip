@@ -29,8 +29,8 @@
 //    waiting leaves are dealt out one per lane to ALL lanes of the wave, whatever their own state; the owner's ray
 //    comes through the cross-lane network (ds_bpermute), the results go back through one 64-bit LDS minimum per
 //    owner.  Triangle tests run at 96 % lane utilisation (a leaf of 3 triangles: one pass instead of three trips
-//    under a 30 % exec mask); node trips at 66 %.  (PTMI_WF_LEAF_PASS=0 builds round 1's mixed trips, where every
-//    traversing lane takes one step per trip, node or triangle.)
+//    under a 30 % exec mask); node trips at 66 %.  (Round 1 ran MIXED trips instead, in which every traversing lane took
+//    one step per trip, node or triangle: what they measured stands beside the wait-debt table, launch_render_wavefront.)
 //  * Per ray the visit sequence is exactly the reference's (near child first, far child pushed, leaf
 //    triangles in index order, limit updated between tests, FullKernel.cl:620-702): only WHEN a lane
 //    takes its next step changes, never WHICH tests it makes or what they see (see leaf_pass for the one place
@@ -68,19 +68,6 @@ constexpr int kWfBlock = 256;  // lanes per workgroup: trees of up to 22 levels 
 // waves either way) 976 / 931 / 938 - so the narrow form is only launched where the wide one does not get its five workgroups.
 constexpr int kWfBlockNarrow = 64;
 constexpr int kWfStack = PTMI_BVH_MAX_DEPTH;
-#ifndef PTMI_WF_WAIT_DEBT
-// lane-trips of waiting a wave tolerates before it spends a pass on path logic: a launch parameter (DWarm::wait_debt),
-// 768 from tree depth 16 on, below that 512 (general path logic) or 320 (plain scenes: the cheaper a pass, the sooner it
-// pays); PTMI_WF_WAIT_DEBT > 0 fixes it at build time for sweeps.
-// Measured on MI355X (Msamples/s: 1M triangles 1080p depth 22 / Cornell box 1080p d8 depth 5 / material mix 4K d16):
-//   round 2, plain-scene specialisation (first two scenes):  192: - / 6360 / 2193    256: - / 6620 / 2317    320: - / 6670 / 2403
-//                           384: - / 6600 / 2442    512: 960 / 6430 / 2491    640: 963 / 6190 / -    768: 976 / - / -    1024: 959 / - / -
-//   round 2, leaf passes:   512: 885 / 5388 / 2344    768: 895 / 5172 / 2314    1024: 895 / 5121 / 2235
-//   round 1, mixed trips:   256: - / 4883 / 1876    384: 733 / - / 1969    512: 740 / 4804 / 1986    768: 742 / 4896 / 1944
-//                           1024: 737 / 4845 / 1872    2048: - / 4840 / 1718
-// (a fixed threshold of 8 waiting lanes instead of a debt measured 474 / 743 with an early build)
-#define PTMI_WF_WAIT_DEBT 0
-#endif
 #ifndef PTMI_WF_MIN_WAVES
 // waves per SIMD the register allocator must fit (5 -> 96 VGPRs, the overflow spills to scratch inside the path-logic
 // code, which is ~1 % of the loop trips).  Measured on MI355X, same box (Msamples/s, 1M triangles / Cornell / material
@@ -103,28 +90,14 @@ constexpr int kQueueStride = PTMI_WF_QUEUE_STRIDE;  // dwords between two queue 
 // word 1 of the job-counter block is the launch's "a path was given up" flag (redo_poisoned_kernel): free only while the
 // queue counters are at least two words apart
 static_assert(kQueueStride >= 2, "job_counter[1] is the given-up flag: queue counters must not be adjacent words");
-constexpr int kWaitDebtFixed = PTMI_WF_WAIT_DEBT;
-#ifndef PTMI_WF_HIT_WORDS
-// LDS words of the closest-hit record per lane.  8: hit point (4), s, t, triangle | front, found.  4: the ray parameter
-// instead of the point - path logic rebuilds the point from the ray it still holds with the very operations of the
-// triangle test, bit for bit - s, t, and one word triangle | front | found.  LDS per workgroup = (tree depth + 1 + words)
-// KB + 4 KB of leaf-pass keys and items (kLeafPassWords) = (depth + 9) KB with 4 words, plus the static counter block (8 * C_COUNT bytes): trees up to depth 22 keep five
-// workgroups per CU (160 KB); the 4M-triangle scene (depth 24: 33 KB) and the 16M one (depth 27) run four.
-// Measured on MI355X, same box, 1M triangles 1080p: 4 words 759-761, 8 words 751-753 Msamples/s.
-#define PTMI_WF_HIT_WORDS 4
-#endif
-constexpr int kHitWords = PTMI_WF_HIT_WORDS;
-static_assert(kHitWords == 4 || kHitWords == 8, "closest-hit record: 4 or 8 words");
-#ifndef PTMI_WF_LEAF_PASS
-// 1: LEAF PASSES.  A lane that reaches a leaf does not test its triangles itself, one per trip, under whatever exec mask the
-// trip happens to have; it waits, and when enough lanes wait the wave runs one pass in which the triangles of ALL waiting
-// leaves are dealt out as work items, one per lane, to all 64 lanes (the ray of an item's owner travels through the
-// cross-lane network).  A leaf of 3 triangles costs one pass at full lane utilisation instead of three trips at ~30 %.
-// Same tests, same order of acceptance per ray (see leaf_pass): results bit-identical.
-#define PTMI_WF_LEAF_PASS 1
-#endif
-constexpr bool kLeafPass = PTMI_WF_LEAF_PASS != 0;
-static_assert(!kLeafPass || kHitWords == 4, "leaf passes write the 4-word closest-hit record");
+// LDS words of the closest-hit record per lane: the ray parameter of the hit - path logic rebuilds the point from the ray it
+// still holds with the very operations of the triangle test, bit for bit -, s, t, and one word triangle | front | found.
+// LDS per workgroup = (tree depth + 1 + these words) KB + 4 KB of leaf-pass keys and items (kPassWordsPerLane) = (depth + 9) KB,
+// plus the static counter block (8 * C_COUNT bytes): trees up to depth 22 keep five workgroups per CU (160 KB); the
+// 4M-triangle scene (depth 24: 33 KB) and the 16M one (depth 27) run four.
+// (The earlier record of 8 words - the hit point itself (4), s, t, triangle | front, found - went with the mixed trips; it
+// measured, on MI355X, same box, 1M triangles 1080p, 751-753 Msamples/s against 759-761 with 4 words.)
+constexpr int kHitRecordWords = 4;
 #ifndef PTMI_WF_LEAF_LANES
 #define PTMI_WF_LEAF_LANES 19
 #endif
@@ -134,18 +107,7 @@ static_assert(!kLeafPass || kHitWords == 4, "leaf passes write the 4-word closes
 // a pass (up to 64 triangles, one per lane) runs when this many lanes wait at a leaf (3 triangles each on average), or when
 // the waiting triangles are kLeafRatio times as many as the lanes left to take node steps
 constexpr int kLeafLanes = PTMI_WF_LEAF_LANES, kLeafRatio = PTMI_WF_LEAF_RATIO;
-constexpr int kLeafPassWordsPerLane = kLeafPass ? 4 : 0;  // LDS: one 64-bit key per lane + 64 items of 8 bytes per wave
-#ifndef PTMI_WF_TOS
-// The top entry of a lane's traversal stack ALSO in a register (round 4): a pop takes the register and the LDS read that refills
-// it is not needed before the lane's NEXT pop, instead of an LDS round trip on the critical path of every node step.
-// 0: never, 1: every instantiation, 2: the general shading instantiations only.  Measured on MI355X, same box, two rounds,
-// Msamples/s (1M triangles plain / 1M triangles general shading forced / Cornell box 1080p d8 plain / material mix 4K d16 general /
-// configs[4] stand-in 4K d16 general, four workgroups per CU / 4M triangles plain, four workgroups per CU):
-//   0: 973.9 / 916.2 / 7197 / 2511 / 1161 / 517.1      1: 965.7 / 943.1 / 7215 / 2658 / 1211 / 510.7      2: 973.6 / 941.8 / 7263 / 2659 / 1214 / 516.9
-// The general instantiations gain 3-6 % (their spilled registers also fall from 67 to 30: the allocator's doing), the plain one
-// loses 0.8 %: hence 2.
-#define PTMI_WF_TOS 2
-#endif
+constexpr int kPassWordsPerLane = 4;  // LDS: one 64-bit key per lane + 64 items of 8 bytes per wave
 
 // Scene fields by value (SGPRs): what the traversal trips and EVERY path-logic trip need.  The rarely used
 // rest of DScene (sky: only when a path escapes; histogram / RANDOM-sampler / SUPER_SAMPLING buffers; counters)
@@ -170,7 +132,7 @@ struct DWarm {
     uint32_t wide_records;  // the record array is 4 GB or more: 64-bit addressing
     uint32_t russian_roulette;  // PTMI_FLAG_RUSSIAN_ROULETTE (non-parity mode)
     uint32_t source_seed;       // PTMI_FLAG_SOURCE_SEED (non-parity mode)
-    uint32_t wait_debt;         // see PTMI_WF_WAIT_DEBT
+    uint32_t wait_debt;         // lane-trips of waiting before a path-logic pass (launch_render_wavefront chooses it)
     uint32_t split_paths;       // DScene::split_paths
 };
 
@@ -225,6 +187,30 @@ __device__ __forceinline__ void decode_leaf(const DWarm& sc, uint32_t ref, uint3
     tri_end = start + count;
 }
 
+// The totals of a path the literal loops have traced again, into a counter block: the launch that gave the path up counted
+// one path, one segment, no hit (two's complement: that segment is taken back; C_PATHS here counts paths traced again).
+__device__ __forceinline__ void add_retraced_totals(unsigned long long* totals, uint32_t depth, uint32_t n_seg, uint32_t n_shadow,
+                                                    const PathCounters& pc)
+{
+    atomicAdd(&totals[C_PATHS], 1ull);
+    atomicAdd(&totals[C_SEGMENTS], (unsigned long long)n_seg - 1ull);
+    atomicAdd(&totals[C_HITS], (unsigned long long)depth);
+    atomicAdd(&totals[C_SHADOW], (unsigned long long)n_shadow);
+    atomicAdd(&totals[C_BBX], (unsigned long long)pc.bbx);
+    atomicAdd(&totals[C_TRI], (unsigned long long)pc.tri);
+}
+
+// What a path of the wavefront kernel becomes when it is given up (a ray, or an accepted distance, that is not a number): marked
+// radiance, transfer 1, counters back to zero.  The caller ends the lane's query as a miss and raises the launch's flag
+// (job_counter[1]) for redo_poisoned_kernel / redo_random_kernel.
+__device__ __forceinline__ void give_path_up(V4& radiance, V4& transfer, uint32_t& reflection, uint32_t& p_bbx, uint32_t& p_tri)
+{
+    const float m = __uint_as_float(kPoisonMarker);
+    radiance = v4(m, m, m, m);
+    transfer = v4(1, 1, 1, 1);
+    reflection = 0; p_bbx = 0; p_tri = 0;
+}
+
 // PLAIN: path logic for scenes of plain-colour MAT_STANDART materials and ONE LIGHT_POINT (DScene::plain_shading) rendered
 // with the JITTERED sampler and without Russian roulette: the same operations for those renders, without the code - and
 // the registers - of the other material types, light types, samplers and of the light loop (1M triangles +4.9 %, Cornell
@@ -255,7 +241,17 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
     if (PLAIN) { sc.sampler = PTMI_SAMPLER_JITTERED; sc.russian_roulette = 0; sc.n_lights = 1; }  // ... and ONE light
     constexpr bool kOneLight = PLAIN;  // (nothing gathered across shadow queries, no light index: five registers fewer per lane)
     constexpr int kWfBlock = BLOCK;  // (shadows the namespace's: every LDS stride below is the workgroup's own width)
-    constexpr bool kTos = PTMI_WF_TOS == 1 || (PTMI_WF_TOS == 2 && !PLAIN);
+    // The top entry of a lane's traversal stack ALSO in a register (round 4): a pop takes the register and the LDS read that refills
+    // it is not needed before the lane's NEXT pop, instead of an LDS round trip on the critical path of every node step.  Only in
+    // the general shading instantiations.  Round 4 measured it never / in every instantiation / in the general ones only, on
+    // MI355X, same box, two rounds, Msamples/s (1M triangles plain / 1M triangles general shading forced / Cornell box 1080p d8
+    // plain / material mix 4K d16 general / configs[4] stand-in 4K d16 general, four workgroups per CU / 4M triangles plain, four
+    // workgroups per CU):
+    //   never: 973.9 / 916.2 / 7197 / 2511 / 1161 / 517.1      every: 965.7 / 943.1 / 7215 / 2658 / 1211 / 510.7
+    //   general only: 973.6 / 941.8 / 7263 / 2659 / 1214 / 516.9
+    // The general instantiations gain 3-6 % (their spilled registers also fall from 67 to 30: the allocator's doing), the plain one
+    // loses 0.8 %.
+    constexpr bool kTos = !PLAIN;
     extern __shared__ __attribute__((aligned(16))) uint32_t stack_mem[];
     // (the statistics build: one block with every counter, its launches never render for several calls)
     constexpr uint32_t kBlockCounters = STATS ? (uint32_t)C_COUNT : PTMI_COUNTER_SPLITS * kSplitWords;
@@ -270,7 +266,7 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
     // hit record, its address minus one level cannot wrap below zero).  Pushes write the slot above the top for
     // every lane and move the top only for pushing lanes; an inner node at depth k has at most k pending entries
     // above it, so that slot is always inside the `stack_levels` = tree depth levels.
-    uint32_t* const stack_floor = &stack_mem[kHitWords * kWfBlock + tid];
+    uint32_t* const stack_floor = &stack_mem[kHitRecordWords * kWfBlock + tid];
     *stack_floor = REF_NONE;
     // the rare fields: pointer re-derived through an opaque asm so the loads stay where they are used
     auto cold_scene = [&]() -> const DScene& {
@@ -282,9 +278,9 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
     // only by path logic: it lives in LDS in front of the stack, [field][lane], not in registers of the hot loop.
     uint32_t* const hit_mem = &stack_mem[tid];
     // the record's triangle word = triangle record index (< 2^27) | kHitFront when the ray met the front side (N . dir < 0)
-    // (| kHitFound in the 4-word record, whose last word it is; the 8-word record keeps "found" in a word of its own)
+    // | kHitFound: the query has found a triangle
     constexpr uint32_t kHitFront = 0x80000000u, kHitFound = 0x40000000u;
-    constexpr int kWordS = kHitWords == 8 ? 4 : 1, kWordT = kHitWords == 8 ? 5 : 2, kWordTri = kHitWords == 8 ? 6 : 3;
+    constexpr int kWordS = 1, kWordT = 2, kWordTri = 3;  // (word 0: the ray parameter)
     const uint32_t tiles_x = (sc.width + 7u) >> 3;
     const bool owns_pixel = sc.sampler != PTMI_SAMPLER_RANDOM;
     const uint32_t n_tiles = (n_jobs / n_iterations) >> 6;
@@ -314,20 +310,17 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
     uint32_t cur = REF_IDLE, tri_i = 0, tri_end = 0;
     uint32_t dir_signs = 0;  // bit k: direction component k > 0 (which child of a node cut along k is the near one)
     uint32_t* sp = stack_floor;  // the top entry (the sentinel when the stack is empty)
-    uint32_t tos = REF_NONE;     // kTos: ... and its value (PTMI_WF_TOS); invariant tos == *sp
+    uint32_t tos = REF_NONE;     // kTos: ... and its value; invariant tos == *sp
     // the point of the closest hit, as path logic needs it when a query has finished
     auto load_hit_point = [&]() {
-        if (kHitWords == 8)
-            return v4(__uint_as_float(hit_mem[0 * kWfBlock]), __uint_as_float(hit_mem[1 * kWfBlock]),
-                      __uint_as_float(hit_mem[2 * kWfBlock]), __uint_as_float(hit_mem[3 * kWfBlock]));
-        // 4-word record.  After a shadow query the lane's ray still starts at the hit point (:932-936 shoot from it without
+        // After a shadow query the lane's ray still starts at the hit point (:932-936 shoot from it without
         // an offset); after a closest-hit query the ray is the one that found the hit, and the point is
         // origin + direction * parameter evaluated as Triangle_Intersects does (FullKernel.cl:536).
         if (shadow) return r.o;
         return mad(r.d, __uint_as_float(hit_mem[0 * kWfBlock]), r.o);
     };
     auto query_found = [&]() {
-        return kHitWords == 8 ? (hit_mem[7 * kWfBlock] & 2u) != 0 : (hit_mem[kWordTri * kWfBlock] & kHitFound) != 0;
+        return (hit_mem[kWordTri * kWfBlock] & kHitFound) != 0;
     };
     // saved across the shadow rays of one surface hit: the direction the surface was reached along and the light gathered
     // so far.  The surface itself (normals, colour, material) is NOT kept: it is a pure function of the hit record in LDS
@@ -335,8 +328,9 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
     V4 cam_d = v4(0, 0, 0, 0), direct = v4(0, 0, 0, 0);
     uint32_t light_idx = 0;
     // wave-uniform scheduler statistics (scalar registers): trips and active lanes per step kind
-    uint32_t trips_i = 0, trips_t = 0, trips_p = 0;
-    unsigned long long lanes_i = 0, lanes_t = 0, lanes_p = 0;
+    // (the leaf passes count their own: pass_rounds, pass_items)
+    uint32_t trips_i = 0, trips_p = 0;
+    unsigned long long lanes_i = 0, lanes_p = 0;
     unsigned long long cycles_p = 0;
     const unsigned long long loop_start = STATS ? __builtin_amdgcn_s_memtime() : 0ull;
 
@@ -366,11 +360,8 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
         check(p_bbx < PTMI_MAX_INTERSECTION_NUMBER && p_tri < PTMI_MAX_INTERSECTION_NUMBER, C_CHK_STATS_RANGE);  // cl:1325,1330
         const bool given_up = !owns_pixel && (slot & kGivenUp) != 0u;  // (RANDOM sampler: redo_random_kernel adds this path)
         if (sc.histograms && stage_stats == nullptr && !given_up) {
-            // RANDOM sampler / very deep paths: the three statistics atomics as the reference issues them (:1319-1331)
-            const DScene& cs = cold_scene();
-            atomicAdd(&cs.hist_depths[reflection], 1u);
-            if (p_bbx < PTMI_MAX_INTERSECTION_NUMBER) atomicAdd(&cs.hist_bbx[p_bbx], 1u);
-            if (p_tri < PTMI_MAX_INTERSECTION_NUMBER) atomicAdd(&cs.hist_tri[p_tri], 1u);
+            // RANDOM sampler / very deep paths: the three statistics atomics as the reference issues them
+            count_path_in_histograms(cold_scene(), reflection, p_bbx, p_tri);
         }
         if (owns_pixel) {
             // JITTERED / UNIFORM: the sample lands on the work-item's own pixel (:1333-1336); stage it
@@ -383,35 +374,13 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
         } else if (!given_up) {
             // RANDOM sampler: the sample lands on an arbitrary pixel; the reference races there (:1339-1345).  The sample
             // position is drawn again from the path's seed (the first two draws, :1137-1141) instead of being kept.
-            const uint32_t n_pixels = sc.width * sc.height;
-            const uint32_t it_local = slot / n_pixels, pixel = slot - it_local * n_pixels;
-            const uint32_t gy = pixel / sc.width, gx = pixel - gy * sc.width;
-            const uint32_t it = first_iteration + it_local * iteration_stride;
+            uint32_t gx, gy, it;
+            decode_slot(slot, sc.width, sc.width * sc.height, first_iteration, iteration_stride, gx, gy, it);
             int seed0 = lcg_seed(gx, gy, sc.width, sc.height, it, sc.source_seed != 0);
             float sample_x, sample_y;
             draw_sample(sc, gx, gy, it, seed0, sample_x, sample_y);
             const uint32_t off = sample_pixel(sc, sample_x, sample_y);
-            const DScene& cs = cold_scene();
-            // (the atomics return what the accumulators held before: sumBefore / nRayBefore of :1339-1342)
-            const V4 before = v4(atomicAdd(&cs.image_color[4 * off + 0], radiance.x), atomicAdd(&cs.image_color[4 * off + 1], radiance.y),
-                                 atomicAdd(&cs.image_color[4 * off + 2], radiance.z), atomicAdd(&cs.image_color[4 * off + 3], radiance.w));
-            const float n_before = atomicAdd(&cs.image_ray_nb[off], 1.f);
-            if (SS) {
-                // SUPER_SAMPLING with the RANDOM sampler (:1346-1349): the reference read-modify-writes the variance of a pixel
-                // other work-items may be updating too; here every update is an atomic add.  As in the reference, a pixel whose
-                // first sample arrives after iteration 0 divides 0 by 0 here, keeps a NaN variance and is never skipped (:1168:
-                // the comparison with NaN is false) - with this sampler 29 % of the pixels get no sample in iteration 0, so that
-                // quirk decides how many samples a render takes and is kept (the staged form guards its one such case instead).
-                float* const vp = &cs.image_v[4 * off];
-                if (it != 0u) {
-                    const V4 after = before + radiance;
-                    const float n_after = n_before + 1.f;
-                    atomicAdd(&vp[0], (radiance.x - fdiv(before.x, n_before)) * (radiance.x - fdiv(after.x, n_after)));
-                    atomicAdd(&vp[1], (radiance.y - fdiv(before.y, n_before)) * (radiance.y - fdiv(after.y, n_after)));
-                    atomicAdd(&vp[2], (radiance.z - fdiv(before.z, n_before)) * (radiance.z - fdiv(after.z, n_after)));
-                    atomicAdd(&vp[3], (radiance.w - fdiv(before.w, n_before)) * (radiance.w - fdiv(after.w, n_after)));
-                }
-            }
+            add_random_sample(cold_scene(), off, radiance, SS, it);
         }
         need_path = true;
         cur = REF_NONE; tri_i = tri_end = 0;
@@ -424,8 +393,7 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
         cur = sc.root_ref; sp = stack_floor; tri_i = tri_end = 0;
         if (kTos) tos = REF_NONE;
         // "found" of THIS query (a shadow query leaves the rest of the closest hit's record alone)
-        if (kHitWords == 8) hit_mem[7 * kWfBlock] = 0;
-        else if (shadow) atomicAnd(&hit_mem[kWordTri * kWfBlock], ~kHitFound);
+        if (shadow) atomicAnd(&hit_mem[kWordTri * kWfBlock], ~kHitFound);
         else hit_mem[kWordTri * kWfBlock] = 0;
         exact_boxes = !(sc.boxes_ordered && ray_slabs_are_ordered(r));
         if (cur & REF_LEAF) {  // the whole scene is one leaf
@@ -434,7 +402,7 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
         }
     };
 
-    // ---- leaf passes (kLeafPass) -----------------------------------------------------------------------------------
+    // ---- leaf passes -----------------------------------------------------------------------------------------------
     // Per wave: items = the next (up to 4) triangles of every lane that waits at a leaf, numbered owner by owner (prefix sum
     // of the counts from three ballots); a pass takes the first 64 and lane k tests item k with the OWNER's ray, limit and
     // mode (an owner whose triangles did not all fit offers the rest to the next pass).
@@ -446,8 +414,8 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
     //   shadow: the FIRST triangle that passes ends the query (:724-727) and only the tests up to it are counted:
     //     a minimum over the index.
     // All LDS traffic of a pass stays inside the wave (LDS operations of one wave execute in order): no barrier.
-    unsigned long long* const key_mem = reinterpret_cast<unsigned long long*>(&stack_mem[(kHitWords + 1 + stack_levels) * kWfBlock]);
-    uint2* const item_mem = reinterpret_cast<uint2*>(&stack_mem[(kHitWords + 3 + stack_levels) * kWfBlock]) + (tid & ~63u);
+    unsigned long long* const key_mem = reinterpret_cast<unsigned long long*>(&stack_mem[(kHitRecordWords + 1 + stack_levels) * kWfBlock]);
+    uint2* const item_mem = reinterpret_cast<uint2*>(&stack_mem[(kHitRecordWords + 3 + stack_levels) * kWfBlock]) + (tid & ~63u);
     const uint32_t lane = tid & 63u, wave_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid & ~63u));  // (a scalar)
     uint32_t pass_rounds = 0, pass_items = 0, item_violations = 0;
     const uint32_t n_records = STATS ? cold_scene().n_records : 0u;
@@ -523,12 +491,8 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
             const uint32_t won = (uint32_t)(key_mem[tid] >> 32);
             if (NANSAFE && !shadow && won == 0u) {
                 // a triangle of this leaf was accepted with a NaN distance: the path is given up (as where path logic meets
-                // a ray that is not a number, below) - marked radiance, counters back to zero, the query ends as a miss -
-                // and redo_poisoned_kernel traces it again
-                const float m = __uint_as_float(kPoisonMarker);
-                radiance = v4(m, m, m, m);
-                transfer = v4(1, 1, 1, 1);
-                reflection = 0; p_bbx = 0; p_tri = 0;
+                // a ray that is not a number, below), the query ends as a miss, and redo_poisoned_kernel traces it again
+                give_path_up(radiance, transfer, reflection, p_bbx, p_tri);
                 hit_mem[kWordTri * kWfBlock] = 0;
                 cur = REF_NONE; tri_i = tri_end = 0; sp = stack_floor;
                 if (kTos) tos = REF_NONE;
@@ -553,9 +517,9 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
             }
         }
     };
-    // one inner-node step of the calling lanes (:660-697): the same code as in the mixed trip below
-    // (always the 64-bit address form here: one instruction more than the 32-bit offset of the mixed trip, measured
-    // faster - 851 vs 837 Msamples/s - than choosing between the two)
+    // one inner-node step of the calling lanes (:660-697)
+    // (always the 64-bit address form: one instruction more than a scalar base + 32-bit byte offset, which only serves a record
+    // array below 4 GB; measured faster - 851 vs 837 Msamples/s - than choosing between the two)
     auto node_step = [&]() {
         const float4* const rec = reinterpret_cast<const float4*>(&sc.tris[cur & REF_INDEX_MASK_INNER]);
         const float4 a = rec[0], b = rec[1], c = rec[2], d = rec[3];
@@ -644,13 +608,13 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
         // multiplies.  Going further - the two decisions as integer max / min arithmetic the loop branches on - measured
         // slower, 924 -> 916 Msamples/s: the scalar unit of a CU is ~45 % busy in this kernel and a scalar instruction more
         // per trip costs more than a plain vector one, tools/microbench/pk_rate.hip and DESIGN.md 5.)
-        if (kLeafPass) asm volatile("" : "+s"(n_t), "+s"(n_i));
+        asm volatile("" : "+s"(n_t), "+s"(n_i));
         wait_debt += n_p;
     };
     // path logic is due / nothing can traverse (then every waiting lane is served)
     // (Tried: a wait debt of its own for the lanes whose shadow query has finished - the expensive kind of path logic - so
     // that each kind is served at a higher lane count: 809 -> 685-700 Msamples/s; lanes kept waiting are lanes that do not traverse.)
-    const int wait_debt_bound = kWaitDebtFixed > 0 ? kWaitDebtFixed : (int)sc.wait_debt;
+    const int wait_debt_bound = (int)sc.wait_debt;
     auto path_logic_due = [&]() { return n_p > 0 && wait_debt >= wait_debt_bound; };
     auto nothing_traverses = [&]() { return n_t == 0 && n_i == 0; };
     // Loop nest: path logic in the outer loop, traversal trips in an inner loop of their own, so that the traversal
@@ -660,129 +624,24 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
     for (;;) {
         survey();
         if (!any_lane) break;
-        if (kLeafPass) {
-            // node trips for the lanes at inner nodes; a leaf pass when enough lanes wait at leaves (or as many as run)
-            // (node trips in a loop of their own: their state is carried through one small loop without copies)
-            auto to_path_logic = [&]() { return path_logic_due() || nothing_traverses(); };
-            auto pass_is_due = [&]() { return n_t >= kLeafLanes || (n_t > 0 && 3 * n_t >= kLeafRatio * n_i); };
-            // (One loop for both kinds of trip.  Tried: node trips in an inner loop of their own - same schedule, 851 -> 807
-            // Msamples/s; the node step of the lanes at inner nodes in the same trip as a pass, its record loads in flight
-            // during the pass - 894 -> 791, the sixteen registers held across the pass spill; requesting the record of a lane's
-            // next node as soon as the step has chosen it, before the wave has counted its lanes and decided what the next trip
-            // is - 895 -> 724: the requests of lanes that turn out to wait are extra L1 traffic, and the loop-carried
-            // registers cost sixteen copies per trip.)
-            while (!to_path_logic()) {
-                if (pass_is_due()) {
-                    leaf_pass(pending);
-                    survey();
-                    continue;
-                }
-                if (STATS) { trips_i++; lanes_i += n_i; }
-                if (want_inner) node_step();
+        // node trips for the lanes at inner nodes; a leaf pass when enough lanes wait at leaves (or as many as run)
+        auto to_path_logic = [&]() { return path_logic_due() || nothing_traverses(); };
+        auto pass_is_due = [&]() { return n_t >= kLeafLanes || (n_t > 0 && 3 * n_t >= kLeafRatio * n_i); };
+        // (One loop for both kinds of trip.  Tried: node trips in an inner loop of their own - same schedule, 851 -> 807
+        // Msamples/s; the node step of the lanes at inner nodes in the same trip as a pass, its record loads in flight
+        // during the pass - 894 -> 791, the sixteen registers held across the pass spill; requesting the record of a lane's
+        // next node as soon as the step has chosen it, before the wave has counted its lanes and decided what the next trip
+        // is - 895 -> 724: the requests of lanes that turn out to wait are extra L1 traffic, and the loop-carried
+        // registers cost sixteen copies per trip.)
+        while (!to_path_logic()) {
+            if (pass_is_due()) {
+                leaf_pass(pending);
                 survey();
+                continue;
             }
-        } else
-        if (!(path_logic_due() || nothing_traverses())) {
-            for (;;) {
-                // ===================== traversal trip: EVERY traversing lane takes one step ====================
-                // A DNode and a DTri are both one aligned 64-byte record, so node lanes and triangle lanes issue
-                // the same four dwordx4 loads and the wave pays the memory latency once for both kinds.
-                if (STATS) {
-                    trips_i += n_i ? 1u : 0u; lanes_i += n_i;
-                    trips_t += n_t ? 1u : 0u; lanes_t += n_t;
-                }
-                const bool is_tri = pending;
-                if (pending || want_inner) {
-                    // nodes and triangles live in one array of 64-byte records (nodes == tris): scalar base + 32-bit
-                    // byte offset while the array is below 4 GB (the shift drops a node reference's flag bits)
-                    // Every lane loads the two quads a triangle lane can reject with (see tri_test); node lanes load
-                    // the other two as well, triangle lanes only if the distance tests pass.
-                    const float4* rec;
-                    if (!sc.wide_records) {
-                        const uint32_t off = (is_tri ? tri_i : cur) << 6;
-                        rec = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(sc.tris) + off);
-                    } else {
-                        rec = reinterpret_cast<const float4*>(&sc.tris[is_tri ? tri_i : (cur & REF_INDEX_MASK_INNER)]);
-                    }
-                    constexpr int kE1 = PRE ? 1 : 3, kL0 = PRE ? 2 : 1, kL1 = PRE ? 3 : 2;
-                    const float4 e0 = rec[0], e1 = rec[kE1];
-                    bool need_pop = false;
-                    if (is_tri) {
-                        // ---- one triangle test (Triangle_Intersects inside the leaf loop, FullKernel.cl:638-646)
-                        p_tri++;
-                        tri_test<PRE>(e0, e1, [&](float4& l0, float4& l1) { l0 = rec[kL0]; l1 = rec[kL1]; }, r, limit,
-                                      [&](const V4& q, float ray_t, float s, float t, bool front, float nsd) {
-                            limit = nsd;
-                            if (!shadow) {  // closest hit so far: the record path logic will shade from
-                                if (kHitWords == 8) {
-                                    hit_mem[0 * kWfBlock] = __float_as_uint(q.x); hit_mem[1 * kWfBlock] = __float_as_uint(q.y);
-                                    hit_mem[2 * kWfBlock] = __float_as_uint(q.z); hit_mem[3 * kWfBlock] = __float_as_uint(q.w);
-                                    hit_mem[6 * kWfBlock] = tri_i | (front ? kHitFront : 0u); hit_mem[7 * kWfBlock] = 2u;
-                                } else {
-                                    hit_mem[0 * kWfBlock] = __float_as_uint(ray_t);
-                                    hit_mem[kWordTri * kWfBlock] = tri_i | (front ? kHitFront : 0u) | kHitFound;
-                                }
-                                hit_mem[kWordS * kWfBlock] = __float_as_uint(s); hit_mem[kWordT * kWfBlock] = __float_as_uint(t);
-                            } else {
-                                // any hit ends a shadow query (:724-727): empty the triangle range, drop the pending
-                                // node.  Written as in-place moves (tied asm operands) so that these two registers
-                                // are not merged back through the early exits with a select on every trip.
-                                if (kHitWords == 8) hit_mem[7 * kWfBlock] = 2u;
-                                else atomicOr(&hit_mem[kWordTri * kWfBlock], kHitFound);
-                                asm volatile("v_mov_b32 %0, %1" : "+v"(tri_end) : "v"(tri_i));
-                                asm volatile("v_mov_b32 %0, -1" : "+v"(cur));
-                            }
-                        });
-                        tri_i++;
-                    } else {
-                        // ---- one inner-node step (:660-697)
-                        const float4 l0 = rec[kL0], l1 = rec[kL1];
-                        const float4 a = e0, b = PRE ? e1 : l0, c = PRE ? l0 : l1, d = PRE ? l1 : e1;
-                        const float lo1[3] = {a.x, a.y, a.z}, hi1[3] = {a.w, b.x, b.y};
-                        const float lo2[3] = {b.z, b.w, c.x}, hi2[3] = {c.y, c.z, c.w};
-                        const uint32_t ref1 = __float_as_uint(d.x), ref2 = __float_as_uint(d.y), axis = __float_as_uint(d.z);
-                        // dir[cutAxis] > 0 (:663) from the three sign masks the box tests need anyway: lane-mask logic
-                        const bool a0 = axis == 0, a1 = axis == 1;
-                        const bool fwd = (a0 & (r.d.x > 0)) | (a1 & (r.d.y > 0)) | (!(a0 | a1) & (r.d.z > 0));
-                        bool h1, h2;
-                        if (!wave_exact) {  // wave-uniform: nearly always
-                            // (an empty child needs no flag test here: the upload stores it as an inverted infinite box)
-                            h1 = box_hit_ordered(lo1, hi1, r, limit);
-                            h2 = box_hit_ordered(lo2, hi2, r, limit);
-                        } else {
-                            h1 = box_hit(lo1, hi1, (ref1 & REF_EMPTY) != 0, r, limit);
-                            h2 = box_hit(lo2, hi2, (ref2 & REF_EMPTY) != 0, r, limit);
-                        }
-                        p_bbx += 2;
-                        // near child = fwd ? son1 : son2 (:663-666); descend into the near one if it was hit, else into the
-                        // far one; push the far one when both were hit.  In terms of son1/son2:
-                        const uint32_t far_ref = fwd ? ref2 : ref1;
-                        const bool both = h1 & h2;
-                        // push without a branch (see the LDS layout above)
-                        sp[kWfBlock] = far_ref;
-                        sp += both ? kWfBlock : 0;
-                        cur = fwd ? (h1 ? ref1 : ref2) : (h2 ? ref2 : ref1);  // near child if it was hit, else the far one
-                        need_pop = !(h1 | h2);
-                    }
-                    // ---- common tail of both step kinds, branch-free pops (an LDS read every lane can afford)
-                    {
-                        const uint32_t popped = *sp;
-                        uint32_t* const below = sp - kWfBlock;
-                        cur = need_pop ? popped : cur;
-                        sp = need_pop ? (below < stack_floor ? stack_floor : below) : sp;
-                    }
-                    // the triangle range is free and the next node is a leaf: its triangles come next, and the node
-                    // after them is whatever is pending on the stack  (kept as a branch: the select form measured -1 %)
-                    if (tri_i >= tri_end && cur != REF_NONE && (cur & REF_LEAF)) {
-                        decode_leaf(sc, cur, tri_i, tri_end);
-                        cur = *sp;
-                        uint32_t* const below = sp - kWfBlock;
-                        sp = below < stack_floor ? stack_floor : below;
-                    }
-                }
-                survey();
-                if (path_logic_due() || nothing_traverses()) break;
-            }
+            if (STATS) { trips_i++; lanes_i += n_i; }
+            if (want_inner) node_step();
+            survey();
         }
         wait_debt = 0;
         // ================================ P: path logic ========================================
@@ -993,10 +852,7 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
                     }
                 }
                 if (__builtin_expect(bad, 0)) {
-                    const float m = __uint_as_float(kPoisonMarker);
-                    radiance = v4(m, m, m, m);
-                    transfer = v4(1, 1, 1, 1);
-                    reflection = 0; p_bbx = 0; p_tri = 0;
+                    give_path_up(radiance, transfer, reflection, p_bbx, p_tri);
                     shadow = false;
                     job_counter[1] = 1u;  // (the block is zeroed before every launch)
                 }
@@ -1013,8 +869,8 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
     if (STATS && (tid & 63u) == 0) {  // one lane per wave: the scheduler counters are wave-uniform
         atomicAdd(&block_counters[C_TRIPS_I], (unsigned long long)trips_i);
         atomicAdd(&block_counters[C_LANES_I], lanes_i);
-        atomicAdd(&block_counters[C_TRIPS_T], (unsigned long long)(kLeafPass ? pass_rounds : trips_t));
-        atomicAdd(&block_counters[C_LANES_T], kLeafPass ? (unsigned long long)pass_items : lanes_t);
+        atomicAdd(&block_counters[C_TRIPS_T], (unsigned long long)(pass_rounds));
+        atomicAdd(&block_counters[C_LANES_T], (unsigned long long)pass_items);
         atomicAdd(&block_counters[C_TRIPS_P], (unsigned long long)trips_p);
         atomicAdd(&block_counters[C_LANES_P], lanes_p);
         atomicAdd(&block_counters[C_CYCLES_P], cycles_p);
@@ -1060,9 +916,8 @@ __global__ void __launch_bounds__(kBlock) redo_poisoned_kernel(const DScene sc, 
     __syncthreads();
     const uint32_t n_pixels = sc.width * sc.height, n_slots = n_pixels * n_iterations;
     auto trace_slot = [&](const uint32_t slot) {
-        const uint32_t it_local = slot / n_pixels, pixel = slot - it_local * n_pixels;
-        const uint32_t gy = pixel / sc.width, gx = pixel - gy * sc.width;
-        const uint32_t it = first_iteration + it_local * iteration_stride;
+        uint32_t gx, gy, it;
+        decode_slot(slot, sc.width, n_pixels, first_iteration, iteration_stride, gx, gy, it);
         float sx, sy;
         uint32_t depth = 0, n_seg = 0, n_shadow = 0;
         PathCounters pc;
@@ -1070,20 +925,11 @@ __global__ void __launch_bounds__(kBlock) redo_poisoned_kernel(const DScene sc, 
         reinterpret_cast<float4*>(stage)[slot] = make_float4(radiance.x, radiance.y, radiance.z, radiance.w);
         if (stage_stats != nullptr) {
             stage_stats[slot] = pack_path_statistics(depth, pc.bbx, pc.tri);
-        } else if (sc.hist_depths) {  // FullKernel.cl:1319-1331; the launch counted the path in the three zero bins
+        } else if (sc.hist_depths) {  // the launch counted the path in the three zero bins
             atomicSub(&sc.hist_depths[0], 1u); atomicSub(&sc.hist_bbx[0], 1u); atomicSub(&sc.hist_tri[0], 1u);
-            atomicAdd(&sc.hist_depths[depth], 1u);
-            if (pc.bbx < PTMI_MAX_INTERSECTION_NUMBER) atomicAdd(&sc.hist_bbx[pc.bbx], 1u);
-            if (pc.tri < PTMI_MAX_INTERSECTION_NUMBER) atomicAdd(&sc.hist_tri[pc.tri], 1u);
+            count_path_in_histograms(sc, depth, pc.bbx, pc.tri);
         }
-        // (the launch counted: one path, one segment, no hit)
-        unsigned long long* const totals = &block_counters[counter_split_of(slot, sc.split_paths) * kSplitWords];
-        atomicAdd(&totals[C_PATHS], 1ull);  // (here: paths traced again)
-        atomicAdd(&totals[C_SEGMENTS], (unsigned long long)n_seg - 1ull);
-        atomicAdd(&totals[C_HITS], (unsigned long long)depth);
-        atomicAdd(&totals[C_SHADOW], (unsigned long long)n_shadow);
-        atomicAdd(&totals[C_BBX], (unsigned long long)pc.bbx);
-        atomicAdd(&totals[C_TRI], (unsigned long long)pc.tri);
+        add_retraced_totals(&block_counters[counter_split_of(slot, sc.split_paths) * kSplitWords], depth, n_seg, n_shadow, pc);
     };
     uint32_t* const queue = queues[tid >> 6];
     uint32_t queued = 0;  // wave-uniform: slots waiting in this wave's queue (< 64 between two steps)
@@ -1136,40 +982,16 @@ __global__ void __launch_bounds__(kBlock) redo_random_kernel(const DScene sc, co
     const uint32_t listed = job_counter[2], n = listed < kGiveUpListCap ? listed : kGiveUpListCap;
     const uint32_t n_pixels = sc.width * sc.height;
     for (uint32_t i = blockIdx.x * kBlock + tid; i < n; i += gridDim.x * kBlock) {
-        const uint32_t slot = job_counter[kGiveUpListFirst + i];
-        const uint32_t it_local = slot / n_pixels, pixel = slot - it_local * n_pixels;
-        const uint32_t gy = pixel / sc.width, gx = pixel - gy * sc.width;
-        const uint32_t it = first_iteration + it_local * iteration_stride;
+        uint32_t gx, gy, it;
+        decode_slot(job_counter[kGiveUpListFirst + i], sc.width, n_pixels, first_iteration, iteration_stride, gx, gy, it);
         float sx, sy;
         uint32_t depth = 0, n_seg = 0, n_shadow = 0;
         PathCounters pc;
         const bool ss = sc.super_sampling != 0;
         const V4 radiance = trace_path<PRE>(sc, gx, gy, it, &stack_mem[tid], sx, sy, depth, n_seg, n_shadow, pc, ss && it > 5u);
-        if (sc.hist_depths) {  // FullKernel.cl:1319-1331
-            atomicAdd(&sc.hist_depths[depth], 1u);
-            if (pc.bbx < PTMI_MAX_INTERSECTION_NUMBER) atomicAdd(&sc.hist_bbx[pc.bbx], 1u);
-            if (pc.tri < PTMI_MAX_INTERSECTION_NUMBER) atomicAdd(&sc.hist_tri[pc.tri], 1u);
-        }
-        const uint32_t off = sample_pixel(sc, sx, sy);
-        const V4 before = v4(atomicAdd(&sc.image_color[4 * off + 0], radiance.x), atomicAdd(&sc.image_color[4 * off + 1], radiance.y),
-                             atomicAdd(&sc.image_color[4 * off + 2], radiance.z), atomicAdd(&sc.image_color[4 * off + 3], radiance.w));
-        const float n_before = atomicAdd(&sc.image_ray_nb[off], 1.f);
-        if (ss && it != 0u) {  // cl:1346-1349, as finish_path's RANDOM branch
-            float* const vp = &sc.image_v[4 * off];
-            const V4 after = before + radiance;
-            const float n_after = n_before + 1.f;
-            atomicAdd(&vp[0], (radiance.x - fdiv(before.x, n_before)) * (radiance.x - fdiv(after.x, n_after)));
-            atomicAdd(&vp[1], (radiance.y - fdiv(before.y, n_before)) * (radiance.y - fdiv(after.y, n_after)));
-            atomicAdd(&vp[2], (radiance.z - fdiv(before.z, n_before)) * (radiance.z - fdiv(after.z, n_after)));
-            atomicAdd(&vp[3], (radiance.w - fdiv(before.w, n_before)) * (radiance.w - fdiv(after.w, n_after)));
-        }
-        // (the launch counted: one path, one segment, no hit)
-        atomicAdd(&block_counters[C_PATHS], 1ull);
-        atomicAdd(&block_counters[C_SEGMENTS], (unsigned long long)n_seg - 1ull);
-        atomicAdd(&block_counters[C_HITS], (unsigned long long)depth);
-        atomicAdd(&block_counters[C_SHADOW], (unsigned long long)n_shadow);
-        atomicAdd(&block_counters[C_BBX], (unsigned long long)pc.bbx);
-        atomicAdd(&block_counters[C_TRI], (unsigned long long)pc.tri);
+        if (sc.hist_depths) count_path_in_histograms(sc, depth, pc.bbx, pc.tri);
+        add_random_sample(sc, sample_pixel(sc, sx, sy), radiance, ss, it);
+        add_retraced_totals(block_counters, depth, n_seg, n_shadow, pc);
     }
     __syncthreads();
     if (tid > C_PATHS && tid <= C_TRI && block_counters[tid] != 0ull) atomicAdd(&sc.counters[tid], block_counters[tid]);
@@ -1284,12 +1106,7 @@ int launch_precompute_denominators_da(DTri* records, const uint32_t* tri_ids, ui
     if (n_records == 0) return PTMI_OK;
     hipLaunchKernelGGL(PTMI_DEV_NS::precompute_denominators_kernel, dim3((n_records + 255u) / 256u), dim3(256), 0, (hipStream_t)stream,
                        records, tri_ids, n_records);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        if (err) *err = std::string("precompute_denominators_kernel launch: ") + hipGetErrorString(e);
-        return PTMI_ERR_HIP;
-    }
-    return PTMI_OK;
+    return launch_status(hipGetLastError(), "precompute_denominators_kernel", err);
 }
 #endif
 
@@ -1304,7 +1121,7 @@ static size_t wavefront_lds_bytes(uint32_t stack_levels, int block)
 {
     stack_levels = clamp_levels(stack_levels);
     // closest-hit record + sentinel + stack (+ the keys and items of the leaf passes), per lane of the workgroup
-    return (size_t)(stack_levels + 1 + PTMI_DEV_NS::kHitWords + PTMI_DEV_NS::kLeafPassWordsPerLane) * block * sizeof(uint32_t);
+    return (size_t)(stack_levels + 1 + PTMI_DEV_NS::kHitRecordWords + PTMI_DEV_NS::kPassWordsPerLane) * block * sizeof(uint32_t);
 }
 
 // workgroups of instantiation `kernel` the current device holds at once (the persistent grid): registers and LDS decide
@@ -1330,6 +1147,83 @@ void PTMI_ARITH(last_wavefront_grid)(int device, uint32_t* lanes, uint32_t* resi
     *resident = v & 0xFFFFFu;
 }
 
+namespace {
+
+// what a wavefront launch passes to whichever instantiation it gets
+struct WavefrontLaunch {
+    int device;          // the current device, and whether it has a place in the per-device caches below
+    bool cached_device;
+    uint32_t lv, n_jobs;  // stack levels (clamped), jobs
+    hipStream_t st;
+    const DScene* scene_in_device_memory;
+    PTMI_DEV_NS::DWarm warm;
+    uint32_t first_iteration, n_iterations, iteration_stride;
+    uint32_t* job_counter;
+    float* stage;
+    uint32_t* stage_stats;
+};
+constexpr int kMaxCachedDevices = 64;
+
+// Deep trees (23 levels and more): the wide workgroup's LDS no longer fits five times into a CU; the two production
+// instantiations are then launched in their narrow form (kWfBlockNarrow).  Asked once per device and depth.
+static bool five_wide_workgroups_fit(const WavefrontLaunch& w)
+{
+    static std::atomic<int> wide_fits[kMaxCachedDevices][PTMI_BVH_MAX_DEPTH + 1];  // 0 = not asked, 1 = they fit, 2 = they do not
+    int fits = w.cached_device ? wide_fits[w.device][w.lv].load(std::memory_order_relaxed) : 0;
+    if (fits == 0) {
+        int n_cu = 0;
+        const int wide = resident_blocks_of(PTMI_DEV_NS::render_wavefront_kernel<false, true, false, true, false>, w.lv, PTMI_DEV_NS::kWfBlock);
+        const bool known = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, w.device) == hipSuccess && n_cu > 0 && wide > 0;
+        fits = known && wide < 5 * n_cu ? 2 : 1;
+        if (w.cached_device) wide_fits[w.device][w.lv].store(fits, std::memory_order_relaxed);
+    }
+    return fits == 1;
+}
+
+// Launches one instantiation on its persistent grid on the CURRENT device (instantiations differ in registers, devices in CUs and
+// partition mode, hence in workgroups held at once): asked once per (instantiation, device, stack levels); host threads that
+// drive contexts of their own may race for an entry, and then write the same value.
+template <bool S, bool P, bool A, bool L, bool N, int B>
+static void launch_instance(const WavefrontLaunch& w)
+{
+    auto kernel = PTMI_DEV_NS::render_wavefront_kernel<S, P, A, L, N, B>;
+    static std::atomic<int> resident_cache[kMaxCachedDevices][PTMI_BVH_MAX_DEPTH + 1];
+    int resident = w.cached_device ? resident_cache[w.device][w.lv].load(std::memory_order_relaxed) : 0;
+    if (resident == 0) {
+        resident = resident_blocks_of(kernel, w.lv, B);
+        if (w.cached_device) resident_cache[w.device][w.lv].store(resident, std::memory_order_relaxed);
+    }
+    if (w.cached_device) g_last_grid[w.device].store((uint32_t)B << 20 | (uint32_t)resident, std::memory_order_relaxed);
+    uint32_t nb = (w.n_jobs + B - 1) / B;
+    if (resident > 0 && nb > (uint32_t)resident) nb = (uint32_t)resident;
+    hipLaunchKernelGGL(kernel, dim3(nb), dim3(B), wavefront_lds_bytes(w.lv, B), w.st, w.scene_in_device_memory, w.warm, w.first_iteration,
+                       w.n_iterations, w.iteration_stride, w.n_jobs, w.job_counter, w.lv, w.stage, w.stage_stats);
+}
+
+// Which instantiation a launch gets - the twelve that exist.  The common case (no statistics, no adaptive sampling, records
+// that cannot yield NaN distances) pays for none of them; the statistics and SUPER_SAMPLING builds always carry the NaN check
+// (two instructions per accepted triangle).  `plain`: see the kernel's PLAIN (it implies precomputed records).  `narrow`: the
+// two production instantiations in workgroups of kWfBlockNarrow lanes (deep trees).
+using LaunchInstance = void (*)(const WavefrontLaunch&);
+static LaunchInstance instance_for(const DScene& sc, bool scheduler_stats, bool plain, bool narrow)
+{
+    constexpr int kWide = PTMI_DEV_NS::kWfBlock, kNarrow = PTMI_DEV_NS::kWfBlockNarrow;
+    const bool pre = sc.tris_precomputed != 0;
+    //                                               STATS  PRE    SS     PLAIN  NANSAFE
+    if (sc.super_sampling) return pre ? launch_instance<true, true, true, false, true, kWide> : launch_instance<true, false, true, false, true, kWide>;
+    if (scheduler_stats) return pre ? launch_instance<true, true, false, false, true, kWide> : launch_instance<true, false, false, false, true, kWide>;
+    if (sc.nan_safe) {
+        if (plain) return launch_instance<false, true, false, true, true, kWide>;
+        return pre ? launch_instance<false, true, false, false, true, kWide> : launch_instance<false, false, false, false, true, kWide>;
+    }
+    if (plain)  // the common case, BASELINE's untextured scenes among them
+        return narrow ? launch_instance<false, true, false, true, false, kNarrow> : launch_instance<false, true, false, true, false, kWide>;
+    if (pre) return narrow ? launch_instance<false, true, false, false, false, kNarrow> : launch_instance<false, true, false, false, false, kWide>;
+    return launch_instance<false, false, false, false, false, kWide>;
+}
+
+}  // namespace
+
 int PTMI_ARITH(launch_render_wavefront)(const DScene& sc, const DScene* scene_in_device_memory, uint32_t first_iteration,
                             uint32_t n_iterations, uint32_t iteration_stride, uint32_t* job_counter, uint32_t stack_levels,
                             bool scheduler_stats, float* stage, uint32_t* stage_stats, void* stream, std::string* err)
@@ -1351,9 +1245,14 @@ int PTMI_ARITH(launch_render_wavefront)(const DScene& sc, const DScene* scene_in
             e = hipMemsetD32Async((hipDeviceptr_t)(job_counter + 2), (int)PTMI_DEV_NS::kGiveUpListCap, 1, (hipStream_t)stream);
     }
     if (e == hipSuccess) {
-        const uint32_t lv = clamp_levels(stack_levels);
-        hipStream_t st = (hipStream_t)stream;
-        PTMI_DEV_NS::DWarm warm{};
+        WavefrontLaunch w{};
+        w.lv = clamp_levels(stack_levels); w.n_jobs = n_jobs; w.st = (hipStream_t)stream;
+        w.scene_in_device_memory = scene_in_device_memory;
+        w.first_iteration = first_iteration; w.n_iterations = n_iterations; w.iteration_stride = iteration_stride;
+        w.job_counter = job_counter; w.stage = stage; w.stage_stats = stage_stats;
+        w.cached_device = hipGetDevice(&w.device) == hipSuccess && w.device >= 0 && w.device < kMaxCachedDevices;
+        const uint32_t lv = w.lv;
+        PTMI_DEV_NS::DWarm& warm = w.warm;
         warm.nodes = sc.nodes; warm.tris = sc.tris; warm.big_leaves = sc.big_leaves; warm.tri_ids = sc.tri_ids; warm.shade = sc.shade;
         warm.mats = sc.mats; warm.lights = sc.lights; warm.textures = sc.textures; warm.texels = sc.texels;
         warm.root_ref = sc.root_ref; warm.width = sc.width; warm.height = sc.height; warm.max_depth = sc.max_depth;
@@ -1364,95 +1263,38 @@ int PTMI_ARITH(launch_render_wavefront)(const DScene& sc, const DScene* scene_in
         warm.russian_roulette = sc.russian_roulette;
         warm.source_seed = sc.source_seed;
         warm.split_paths = sc.split_paths;
-        constexpr int kMaxCachedDevices = 64;
-        int device = 0;
-        const bool cached_device = hipGetDevice(&device) == hipSuccess && device >= 0 && device < kMaxCachedDevices;
         const bool plain = sc.tris_precomputed && sc.plain_shading && sc.sampler == PTMI_SAMPLER_JITTERED && !sc.russian_roulette &&
                            sc.n_lights == 1 && !sc.super_sampling && !scheduler_stats;
-        warm.wait_debt = lv >= 16u ? 768u : (plain ? 320u : 512u);  // (the cheaper a path-logic pass, the sooner it pays)
-        // the persistent grid of the chosen instantiation on the CURRENT device (instantiations differ in registers, devices in
-        // CUs and partition mode, hence in workgroups held at once): asked once per (instantiation, device, stack levels);
-        // host threads that drive contexts of their own may race for an entry, and then write the same value
-#define PTMI_LAUNCH_WF_BLOCK(S, P, A, L, N, B)                                                                             \
-    do {                                                                                                                  \
-        auto kernel = PTMI_DEV_NS::render_wavefront_kernel<S, P, A, L, N, B>;                                              \
-        static std::atomic<int> resident_cache[kMaxCachedDevices][PTMI_BVH_MAX_DEPTH + 1];                                 \
-        int resident = cached_device ? resident_cache[device][lv].load(std::memory_order_relaxed) : 0;                     \
-        if (resident == 0) {                                                                                               \
-            resident = resident_blocks_of(kernel, lv, B);                                                                  \
-            if (cached_device) resident_cache[device][lv].store(resident, std::memory_order_relaxed);                      \
-        }                                                                                                                  \
-        if (cached_device) g_last_grid[device].store((uint32_t)(B) << 20 | (uint32_t)resident, std::memory_order_relaxed); \
-        uint32_t nb = (n_jobs + (B) - 1) / (B);                                                                           \
-        if (resident > 0 && nb > (uint32_t)resident) nb = (uint32_t)resident;                                             \
-        hipLaunchKernelGGL(kernel, dim3(nb), dim3(B), wavefront_lds_bytes(lv, B), st, scene_in_device_memory, warm,        \
-                           first_iteration, n_iterations, iteration_stride, n_jobs, job_counter, lv, stage, stage_stats); \
-    } while (0)
-#define PTMI_LAUNCH_WF_IMPL(S, P, A, L, N) PTMI_LAUNCH_WF_BLOCK(S, P, A, L, N, PTMI_DEV_NS::kWfBlock)
-#define PTMI_LAUNCH_WF(S, P, A, N) PTMI_LAUNCH_WF_IMPL(S, P, A, false, N)
-        // Deep trees (23 levels and more): the wide workgroup's LDS no longer fits five times into a CU; the two production
-        // instantiations are then launched in their narrow form (kWfBlockNarrow).  Asked once per device and depth.
-        static std::atomic<int> wide_fits[kMaxCachedDevices][PTMI_BVH_MAX_DEPTH + 1];  // 0 = not asked, 1 = five wide workgroups fit, 2 = they do not
-        int fits = cached_device ? wide_fits[device][lv].load(std::memory_order_relaxed) : 0;
-        if (fits == 0) {
-            int n_cu = 0;
-            const int wide = resident_blocks_of(PTMI_DEV_NS::render_wavefront_kernel<false, true, false, true, false>, lv, PTMI_DEV_NS::kWfBlock);
-            const bool known = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && n_cu > 0 && wide > 0;
-            fits = known && wide < 5 * n_cu ? 2 : 1;
-            if (cached_device) wide_fits[device][lv].store(fits, std::memory_order_relaxed);
-        }
-        const bool narrow = fits == 2 && std::getenv("PTMI_WIDE_WORKGROUPS") == nullptr;  // (developer switch: A/B runs)
-        // instantiations: the common case (no statistics, no adaptive sampling, records that cannot yield NaN distances) pays
-        // for none of them; the statistics and SUPER_SAMPLING builds always carry the NaN check (two instructions per
-        // accepted triangle)
-        if (sc.super_sampling) {
-            if (sc.tris_precomputed) PTMI_LAUNCH_WF(true, true, true, true); else PTMI_LAUNCH_WF(true, false, true, true);
-        } else if (scheduler_stats) {
-            if (sc.tris_precomputed) PTMI_LAUNCH_WF(true, true, false, true); else PTMI_LAUNCH_WF(true, false, false, true);
-        } else if (sc.nan_safe) {
-            if (plain) PTMI_LAUNCH_WF_IMPL(false, true, false, true, true);
-            else if (sc.tris_precomputed) PTMI_LAUNCH_WF(false, true, false, true);
-            else PTMI_LAUNCH_WF(false, false, false, true);
-        } else {
-            if (plain) {  // the common case, BASELINE's untextured scenes among them
-                if (narrow) PTMI_LAUNCH_WF_BLOCK(false, true, false, true, false, PTMI_DEV_NS::kWfBlockNarrow);
-                else PTMI_LAUNCH_WF_IMPL(false, true, false, true, false);
-            } else if (sc.tris_precomputed) {
-                if (narrow) PTMI_LAUNCH_WF_BLOCK(false, true, false, false, false, PTMI_DEV_NS::kWfBlockNarrow);
-                else PTMI_LAUNCH_WF(false, true, false, false);
-            }
-            else PTMI_LAUNCH_WF(false, false, false, false);
-        }
-#undef PTMI_LAUNCH_WF
-#undef PTMI_LAUNCH_WF_IMPL
-#undef PTMI_LAUNCH_WF_BLOCK
+        // lane-trips of waiting a wave tolerates before it spends a pass on path logic: 768 from tree depth 16 on, below that
+        // 512 (general path logic) or 320 (plain scenes: the cheaper a pass, the sooner it pays).  A launch parameter since
+        // round 2; the sweeps that chose it, on MI355X (Msamples/s: 1M triangles 1080p depth 22 / Cornell box 1080p d8 depth 5 /
+        // material mix 4K d16):
+        //   round 2, plain-scene specialisation (first two scenes):  192: - / 6360 / 2193    256: - / 6620 / 2317    320: - / 6670 / 2403
+        //                           384: - / 6600 / 2442    512: 960 / 6430 / 2491    640: 963 / 6190 / -    768: 976 / - / -    1024: 959 / - / -
+        //   round 2, leaf passes:   512: 885 / 5388 / 2344    768: 895 / 5172 / 2314    1024: 895 / 5121 / 2235
+        //   round 1's mixed trips (every traversing lane one step per trip, node or triangle: what leaf passes replaced):
+        //                           256: - / 4883 / 1876    384: 733 / - / 1969    512: 740 / 4804 / 1986    768: 742 / 4896 / 1944
+        //                           1024: 737 / 4845 / 1872    2048: - / 4840 / 1718
+        // (a fixed threshold of 8 waiting lanes instead of a debt measured 474 / 743 with an early build)
+        warm.wait_debt = lv >= 16u ? 768u : (plain ? 320u : 512u);
+        const bool narrow = !five_wide_workgroups_fit(w) && std::getenv("PTMI_WIDE_WORKGROUPS") == nullptr;  // (developer switch: A/B runs)
+        instance_for(sc, scheduler_stats, plain, narrow)(w);
         e = hipGetLastError();
-        if (e == hipSuccess && stage == nullptr && sc.sampler == PTMI_SAMPLER_RANDOM) {
-            // RANDOM sampler: behind the launch, the paths on its give-up list (returns at once when there is none)
-            if (sc.tris_precomputed)
-                hipLaunchKernelGGL(PTMI_DEV_NS::redo_random_kernel<true>, dim3(64), dim3(PTMI_DEV_NS::kBlock), 0, st, sc, first_iteration,
-                                   n_iterations, iteration_stride, job_counter);
-            else
-                hipLaunchKernelGGL(PTMI_DEV_NS::redo_random_kernel<false>, dim3(64), dim3(PTMI_DEV_NS::kBlock), 0, st, sc, first_iteration,
-                                   n_iterations, iteration_stride, job_counter);
+        // behind the launch, on its stream: the paths it gave up, if any, traced again (both return at once when there is none)
+        const dim3 redo_block(PTMI_DEV_NS::kBlock);
+        if (e == hipSuccess && stage == nullptr && sc.sampler == PTMI_SAMPLER_RANDOM) {  // the paths on the give-up list
+            const auto redo_random = sc.tris_precomputed ? PTMI_DEV_NS::redo_random_kernel<true> : PTMI_DEV_NS::redo_random_kernel<false>;
+            hipLaunchKernelGGL(redo_random, dim3(64), redo_block, 0, w.st, sc, first_iteration, n_iterations, iteration_stride, job_counter);
             e = hipGetLastError();
         }
-        if (e == hipSuccess && stage != nullptr) {
-            // behind the launch, on its stream: the paths it gave up, if any (returns at once otherwise)
-            if (sc.tris_precomputed)
-                hipLaunchKernelGGL(PTMI_DEV_NS::redo_poisoned_kernel<true>, dim3(1024), dim3(PTMI_DEV_NS::kBlock), 0, st, sc, first_iteration,
-                                   n_iterations, iteration_stride, stage, stage_stats, job_counter);
-            else
-                hipLaunchKernelGGL(PTMI_DEV_NS::redo_poisoned_kernel<false>, dim3(1024), dim3(PTMI_DEV_NS::kBlock), 0, st, sc, first_iteration,
-                                   n_iterations, iteration_stride, stage, stage_stats, job_counter);
+        if (e == hipSuccess && stage != nullptr) {  // the staging slots it marked
+            const auto redo_poisoned = sc.tris_precomputed ? PTMI_DEV_NS::redo_poisoned_kernel<true> : PTMI_DEV_NS::redo_poisoned_kernel<false>;
+            hipLaunchKernelGGL(redo_poisoned, dim3(1024), redo_block, 0, w.st, sc, first_iteration, n_iterations, iteration_stride, stage,
+                               stage_stats, job_counter);
             e = hipGetLastError();
         }
     }
-    if (e != hipSuccess) {
-        if (err) *err = std::string("render_wavefront_kernel launch: ") + hipGetErrorString(e);
-        return PTMI_ERR_HIP;
-    }
-    return PTMI_OK;
+    return launch_status(e, "render_wavefront_kernel", err);
 }
 
 // What follows a wavefront launch of a sampler that owns its pixels: the staged radiances into the accumulators (per pixel,
@@ -1469,11 +1311,8 @@ int PTMI_ARITH(launch_accumulate_staged)(const DScene& sc, uint32_t first_iterat
     else
         hipLaunchKernelGGL(PTMI_DEV_NS::accumulate_staged_kernel, dim3((n_pixels + 255u) / 256u), dim3(256), 0,
                            (hipStream_t)stream, sc.image_color, sc.image_ray_nb, stage, n_pixels, n_iterations);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        if (err) *err = std::string("accumulate_staged_kernel launch: ") + hipGetErrorString(e);
-        return PTMI_ERR_HIP;
-    }
+    const int status = launch_status(hipGetLastError(), "accumulate_staged_kernel", err);
+    if (status != PTMI_OK) return status;
     if (with_histograms && stage_stats != nullptr) return PTMI_ARITH(launch_histogram_staged)(sc, n_iterations, stage_stats, stream, err);
     return PTMI_OK;
 }
@@ -1486,12 +1325,7 @@ int PTMI_ARITH(launch_histogram_staged)(const DScene& sc, uint32_t n_iterations,
     if (hb > 512u) hb = 512u;
     hipLaunchKernelGGL(PTMI_DEV_NS::histogram_staged_kernel, dim3(hb), dim3(1024), 0, (hipStream_t)stream, sc.hist_depths,
                        sc.hist_bbx, sc.hist_tri, stage_stats, sc.super_sampling ? sc.stage_flag : nullptr, n_slots);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        if (err) *err = std::string("histogram_staged_kernel launch: ") + hipGetErrorString(e);
-        return PTMI_ERR_HIP;
-    }
-    return PTMI_OK;
+    return launch_status(hipGetLastError(), "histogram_staged_kernel", err);
 }
 
 }  // namespace ptmi_internal

@@ -57,23 +57,14 @@ __global__ void __launch_bounds__(kBlock) render_kernel(const DScene sc, const u
             n_bbx += pc.bbx;
             n_tri += pc.tri;
             n_hits += depth;
-            if (sc.hist_depths) {  // FullKernel.cl:1319-1331
-                atomicAdd(&sc.hist_depths[depth], 1u);
-                if (pc.bbx < PTMI_MAX_INTERSECTION_NUMBER) atomicAdd(&sc.hist_bbx[pc.bbx], 1u);
-                if (pc.tri < PTMI_MAX_INTERSECTION_NUMBER) atomicAdd(&sc.hist_tri[pc.tri], 1u);
-            }
+            if (sc.hist_depths) count_path_in_histograms(sc, depth, pc.bbx, pc.tri);
             if (owns_pixel) {
                 // JITTERED / UNIFORM: the sample always lands on the work-item's own pixel
                 sum = sum + radiance;  // :1340
                 count = count + 1.f;   // :1342
             } else {
-                // RANDOM: samples land anywhere; the reference races here (:1339-1345), we add atomically
-                const uint32_t off = sample_pixel(sc, sx, sy);
-                atomicAdd(&sc.image_color[4 * off + 0], radiance.x);
-                atomicAdd(&sc.image_color[4 * off + 1], radiance.y);
-                atomicAdd(&sc.image_color[4 * off + 2], radiance.z);
-                atomicAdd(&sc.image_color[4 * off + 3], radiance.w);
-                atomicAdd(&sc.image_ray_nb[off], 1.f);
+                // RANDOM: samples land anywhere (this kernel does not render with SUPER_SAMPLING: no variance)
+                add_random_sample(sc, sample_pixel(sc, sx, sy), radiance, false, it);
             }
         }
         if (owns_pixel) {
@@ -100,18 +91,9 @@ int PTMI_ARITH(launch_render)(const DScene& sc, uint32_t first_iteration, uint32
 {
     if (n_iterations == 0) return PTMI_OK;
     const dim3 grid((sc.width + 15u) / 16u, (sc.height + 15u) / 16u);
-    if (sc.tris_precomputed)
-        hipLaunchKernelGGL(PTMI_DEV_NS::render_kernel<true>, grid, dim3(PTMI_DEV_NS::kBlock), 0, (hipStream_t)stream, sc,
-                           first_iteration, n_iterations, iteration_stride);
-    else
-        hipLaunchKernelGGL(PTMI_DEV_NS::render_kernel<false>, grid, dim3(PTMI_DEV_NS::kBlock), 0, (hipStream_t)stream, sc,
-                           first_iteration, n_iterations, iteration_stride);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        if (err) *err = std::string("render_kernel launch: ") + hipGetErrorString(e);
-        return PTMI_ERR_HIP;
-    }
-    return PTMI_OK;
+    const auto kernel = sc.tris_precomputed ? PTMI_DEV_NS::render_kernel<true> : PTMI_DEV_NS::render_kernel<false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(PTMI_DEV_NS::kBlock), 0, (hipStream_t)stream, sc, first_iteration, n_iterations, iteration_stride);
+    return launch_status(hipGetLastError(), "render_kernel", err);
 }
 
 }  // namespace ptmi_internal

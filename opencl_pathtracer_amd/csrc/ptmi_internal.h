@@ -6,10 +6,24 @@
 #include <string>
 
 #include "ptmi.h"
+#ifdef __HIPCC__  // (host code that is built without HIP reads this header too: it gets everything but launch_status)
+#include <hip/hip_runtime.h>
+#endif
 
 namespace ptmi_internal {
 
 void set_global_error(const std::string& msg);
+
+#ifdef __HIPCC__
+// The tail of a kernel launch (kernel_wavefront.hip, kernels.hip, display.hip): what the launch left, hipGetLastError(), as a
+// status and a message.
+inline int launch_status(hipError_t e, const char* kernel, std::string* err)
+{
+    if (e == hipSuccess) return PTMI_OK;
+    if (err) *err = std::string(kernel) + " launch: " + hipGetErrorString(e);
+    return PTMI_ERR_HIP;
+}
+#endif
 
 // ---- device-side scene layout (see DESIGN.md "Data layout in HBM") ----------
 //

@@ -15,6 +15,49 @@ struct PathCounters {
     uint32_t bbx, tri;  // numIntersectedBBx / numIntersectedTri of the current path
 };
 
+// A staging slot = it_local * W * H + y * W + x of a launch -> the path's pixel and iteration id (n_pixels = W * H).
+__device__ __forceinline__ void decode_slot(uint32_t slot, uint32_t width, uint32_t n_pixels, uint32_t first_iteration,
+                                            uint32_t iteration_stride, uint32_t& gx, uint32_t& gy, uint32_t& iteration)
+{
+    const uint32_t it_local = slot / n_pixels, pixel = slot - it_local * n_pixels;
+    gy = pixel / width;
+    gx = pixel - gy * width;
+    iteration = first_iteration + it_local * iteration_stride;
+}
+
+// The three statistics atomics of a finished path as the reference issues them (FullKernel.cl:1319-1331).
+__device__ __forceinline__ void count_path_in_histograms(const DScene& sc, uint32_t depth, uint32_t bbx, uint32_t tri)
+{
+    atomicAdd(&sc.hist_depths[depth], 1u);
+    if (bbx < PTMI_MAX_INTERSECTION_NUMBER) atomicAdd(&sc.hist_bbx[bbx], 1u);
+    if (tri < PTMI_MAX_INTERSECTION_NUMBER) atomicAdd(&sc.hist_tri[tri], 1u);
+}
+
+// A sample of the RANDOM sampler lands on an arbitrary pixel `off`; the reference races there (:1339-1345), here every update
+// is an atomic add.  `super_sampling`: from iteration 1 on also the variance (:1346-1349) - the reference read-modify-writes
+// that of a pixel other work-items may be updating too.  As in the reference, a pixel whose first sample arrives after
+// iteration 0 divides 0 by 0 here, keeps a NaN variance and is never skipped (:1168: the comparison with NaN is false) - with
+// this sampler 29 % of the pixels get no sample in iteration 0, so that quirk decides how many samples a render takes and is
+// kept (the staged form guards its one such case instead).
+__device__ __forceinline__ void add_random_sample(const DScene& sc, uint32_t off, V4 radiance, bool super_sampling, uint32_t iteration)
+{
+    // (the atomics return what the accumulators held before: sumBefore / nRayBefore of :1339-1342)
+    const V4 before = v4(atomicAdd(&sc.image_color[4 * off + 0], radiance.x), atomicAdd(&sc.image_color[4 * off + 1], radiance.y),
+                         atomicAdd(&sc.image_color[4 * off + 2], radiance.z), atomicAdd(&sc.image_color[4 * off + 3], radiance.w));
+    const float n_before = atomicAdd(&sc.image_ray_nb[off], 1.f);
+    if (super_sampling) {
+        float* const vp = &sc.image_v[4 * off];
+        if (iteration != 0u) {
+            const V4 after = before + radiance;
+            const float n_after = n_before + 1.f;
+            atomicAdd(&vp[0], (radiance.x - fdiv(before.x, n_before)) * (radiance.x - fdiv(after.x, n_after)));
+            atomicAdd(&vp[1], (radiance.y - fdiv(before.y, n_before)) * (radiance.y - fdiv(after.y, n_after)));
+            atomicAdd(&vp[2], (radiance.z - fdiv(before.z, n_before)) * (radiance.z - fdiv(after.z, n_after)));
+            atomicAdd(&vp[3], (radiance.w - fdiv(before.w, n_before)) * (radiance.w - fdiv(after.w, n_after)));
+        }
+    }
+}
+
 // BVH_IntersectRay (FullKernel.cl:620-702) when ANY_HIT == false,
 // BVH_IntersectShadowRay (:705-783) when true.  Same visit order as the
 // reference: at an inner node the child on the side the ray comes from
