@@ -255,6 +255,47 @@ int ptmi_clear(ptmi_ctx* ctx);
 /* Replaces the release block at the end of OpenCL_RunKernel (OpenCL.cpp:120-139). */
 void ptmi_release(ptmi_ctx* ctx);
 
+/* ---- updating the loaded scene in place ---------------------------------- */
+
+/* A scene that moves need not be uploaded again: these two calls rewrite, on the device, the part of the scene a context holds
+ * that has changed, and leave everything else where it is.  Both need an initialised context (PTMI_ERR_STATE otherwise), both
+ * synchronise first (launches rendered ahead are dropped and the launch streams waited for before any memory a launch reads is
+ * rewritten), both update every device of a multi-device context, and both check everything on the host before the first
+ * device write: after any error the context renders the scene it held before the call.
+ * NEITHER TOUCHES what has been rendered: accumulators, histograms, counters, snapshots, bound accumulators and the caller's
+ * stream stay as they are.  A caller who wants a fresh image of the new scene calls ptmi_clear; a caller who does not
+ * accumulates over the motion - motion blur.
+ *
+ * ptmi_set_camera: a new camera (kernel arguments 1..4 of the reference), everything else stays.  A camera that is not finite or
+ * beyond 2^21 would change the kernel instantiation chosen at upload (ptmi_literal_kernel_reason): PTMI_ERR_UNSUPPORTED, call
+ * ptmi_initialize_memory instead. */
+int ptmi_set_camera(ptmi_ctx* ctx, const ptmi_float4* position, const ptmi_float4* direction, const ptmi_float4* right,
+                    const ptmi_float4* up);
+
+/* ptmi_update_triangles: new records for the triangles the context holds - triangulation[i] replaces triangle i of the array
+ * ptmi_initialize_memory was given (the builder's order); triangulation_size must be the uploaded count
+ * (PTMI_ERR_INVALID_ARGUMENT otherwise).  The tree keeps its topology (children, leaf ranges, cut axes, empty flags); every box
+ * is refit on the device, bottom-up, from the new triangles' `aabb` - the boxes ptmi_bvh_refit gives, so the context then holds
+ * what ptmi_initialize_memory would upload for (the new triangles, ptmi_bvh_refit's tree).  The triangles pass the checks
+ * ptmi_initialize_memory applies (materials in range, texture coordinates: PTMI_ERR_BAD_SCENE).  PTMI_ERR_UNSUPPORTED, scene
+ * untouched, where an update cannot express the new scene and ptmi_initialize_memory must be called: the scene has, or the new
+ * triangles would give it, a ptmi_literal_kernel_reason; a triangle with unequal w on its vertices where every uploaded one had
+ * equal w; an `aabb` that is marked empty, not finite, or has pMin > pMax; an uploaded tree whose empty flags do not follow
+ * from its triangles.  The first update of a scene allocates a scratch copy of the triangles and the refit's schedule on the
+ * device (kept until ptmi_initialize_memory / ptmi_release); a context that never updates pays nothing.
+ * A refit keeps the tree's topology, so its quality decays as the triangles move far from where they were built: watch
+ * ptmi_counters.box_tests per path and build a new tree when it has grown.  `info` may be NULL. */
+typedef struct ptmi_update_info {
+    uint32_t struct_size; /* set by the library: sizeof(ptmi_update_info) */
+    uint32_t levels;      /* level passes of the refit (the depth of the inner nodes) */
+    double upload_ms;     /* host -> device copies of the new triangles, all devices */
+    double device_ms;     /* device work behind them (HIP events), all devices */
+    double total_ms;      /* the whole call */
+    double validate_ms;   /* the host's checks of the new triangles (and, in the first update, the schedule) */
+} ptmi_update_info;
+
+int ptmi_update_triangles(ptmi_ctx* ctx, const ptmi_triangle* triangulation, uint32_t triangulation_size, ptmi_update_info* info);
+
 /* ---- measurement / plumbing -------------------------------------------- */
 
 int ptmi_get_counters(ptmi_ctx* ctx, ptmi_counters* out);
@@ -366,6 +407,17 @@ typedef struct ptmi_bvh_build_info {
 
 int ptmi_bvh_create_device(int32_t device, ptmi_triangle* triangulation, uint32_t triangulation_size, ptmi_node* bvh,
                            uint32_t* bvh_size, uint32_t* bvh_max_depth, ptmi_bvh_build_info* info);
+
+/* Host only, no device: the refit of ptmi_update_triangles on a tree in the reference's layout (for callers that keep
+ * GlobalVars.bvh in step with the device, and the yardstick of the device refit).  A leaf's trianglesAABB is the union of the
+ * `aabb` of its triangles in ascending index order (boxes marked empty are skipped), its centroidsAABB takes their centroids; an
+ * inner node's boxes are its sons' merged, son1 first; a corner whose new value compares equal to the one the tree holds keeps the
+ * bits it holds (a -0 / +0 tie stays as the builder decided it).  With unchanged triangles ptmi_bvh_create's tree comes out byte
+ * for byte.
+ * son1Id / son2Id, cutAxis and the leaf ranges are not written.  The tree is walked from bvh[0] with ptmi_initialize_memory's
+ * structural checks (a child index out of range, a node reached twice, a leaf range out of bounds): PTMI_ERR_BAD_SCENE, tree
+ * untouched. */
+int ptmi_bvh_refit(const ptmi_triangle* triangulation, uint32_t triangulation_size, ptmi_node* bvh, uint32_t bvh_size);
 
 #ifdef __cplusplus
 }

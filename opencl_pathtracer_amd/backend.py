@@ -78,6 +78,15 @@ class BvhBuildInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class UpdateInfo(C.Structure):
+    """ptmi_update_info: what ptmi_update_triangles did (level passes of the refit, and where the time went)."""
+    _fields_ = [("struct_size", C.c_uint32), ("levels", C.c_uint32), ("upload_ms", C.c_double), ("device_ms", C.c_double),
+                ("total_ms", C.c_double), ("validate_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 BVH_FALLBACK_NONE, BVH_FALLBACK_STALE_AXIS, BVH_FALLBACK_HOST_ERROR, BVH_FALLBACK_RECORDS = 0, 1, 2, 3
 
 
@@ -115,7 +124,7 @@ ABI_SYMBOLS = ["ptmi_setup_context", "ptmi_initialize_memory", "ptmi_render", "p
                "ptmi_set_stream", "ptmi_device_accumulators", "ptmi_bind_accumulators", "ptmi_read_variance",
                "ptmi_device_variance", "ptmi_last_error",
                "ptmi_abi_version", "ptmi_device_count", "ptmi_device_share", "ptmi_bvh_create",
-               "ptmi_bvh_create_device"]
+               "ptmi_bvh_create_device", "ptmi_set_camera", "ptmi_update_triangles", "ptmi_bvh_refit"]
 
 
 def library_path():
@@ -165,6 +174,9 @@ def load_library():
     lib.ptmi_last_error.restype = C.c_char_p
     lib.ptmi_bvh_create.argtypes = [vp, u32, vp, C.POINTER(u32), C.POINTER(u32)]
     lib.ptmi_bvh_create_device.argtypes = [C.c_int32, vp, u32, vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(BvhBuildInfo)]
+    lib.ptmi_set_camera.argtypes = [vp, C.POINTER(Float4), C.POINTER(Float4), C.POINTER(Float4), C.POINTER(Float4)]
+    lib.ptmi_update_triangles.argtypes = [vp, vp, u32, C.POINTER(UpdateInfo)]
+    lib.ptmi_bvh_refit.argtypes = [vp, u32, vp, u32]
     lib.ptmi_device_share.argtypes = [u32, u32, u32, u32, C.POINTER(u32), C.POINTER(u32)]
     lib.ptmi_device_share.restype = None
     _lib = lib
@@ -212,6 +224,23 @@ def bvh_create(scene, device=None):
     # byte-level copy (numpy's .copy() of a padded struct dtype leaves the padding bytes undefined)
     scene.bvh = np.frombuffer(bytearray(nodes[:size.value].tobytes()), dtype=S.Node)
     scene.bvhMaxDepth = depth.value
+    return scene
+
+
+def bvh_refit(scene):
+    """``ptmi_bvh_refit``: the boxes of ``scene.bvh`` recomputed in place from ``scene.triangulation`` (moved vertices, same
+    topology), on the host; what ``Backend.update_triangles`` does to the tree a context holds."""
+    lib = load_library()
+    tris = np.ascontiguousarray(scene.triangulation)
+    bvh = np.ascontiguousarray(scene.bvh)
+    if tris.dtype != S.Triangle or bvh.dtype != S.Node:
+        raise PtmiError(-1, "triangulation / bvh must have the structs.Triangle / structs.Node dtype")
+    if not bvh.flags.writeable:
+        bvh = np.frombuffer(bytearray(bvh.tobytes()), dtype=S.Node)
+    rc = lib.ptmi_bvh_refit(_ptr(tris), len(tris), _ptr(bvh), len(bvh))
+    if rc:
+        raise PtmiError(rc, lib.ptmi_last_error(None).decode())
+    scene.triangulation, scene.bvh = tris, bvh
     return scene
 
 
@@ -289,6 +318,22 @@ class Backend:
         self._check(self._lib.ptmi_initialize_memory(self._ctx, C.byref(d)))
         del keep
         return self
+
+    # -- the loaded scene, updated in place (no counterpart in the reference) --------------
+    def set_camera(self, position, direction, right, up):
+        """A new camera for the scene the context holds.  What has been rendered stays: call clear() for a fresh image."""
+        v = [_f4(x) for x in (position, direction, right, up)]
+        self._check(self._lib.ptmi_set_camera(self._ctx, *[C.byref(x) for x in v]))
+
+    def update_triangles(self, triangulation):
+        """New records for the triangles the context holds (same count, same order); the tree is refit on the device.  Returns
+        the UpdateInfo as a dict.  What has been rendered stays: call clear() for a fresh image."""
+        tris = np.ascontiguousarray(triangulation)
+        if tris.dtype != S.Triangle:
+            raise PtmiError(-1, "triangulation must have the 336-byte structs.Triangle dtype")
+        info = UpdateInfo()
+        self._check(self._lib.ptmi_update_triangles(self._ctx, tris.ctypes.data_as(C.c_void_p), len(tris), C.byref(info)))
+        return info.as_dict()
 
     # -- one launch of the loop body of OpenCL_RunKernel, generalised to a range ----------
     def render(self, first_iteration, n_iterations):

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
+#include <chrono>
 #include <cmath>
 #include <limits>
 #include <cstdlib>
@@ -20,6 +21,7 @@
 #include "ptmi.h"
 #include "ptmi_internal.h"
 #include "scene_layout.h"
+#include "scene_refit.h"
 #include "launch_schedule.h"
 
 using namespace ptmi_internal;
@@ -69,6 +71,10 @@ struct DeviceState {
     hipEvent_t previous_call_done = nullptr;  // the event behind the previous call's work on the main stream
     DScene ds{};
     DScene* d_scene = nullptr;  // device copy of ds (what the wavefront kernel's path logic reads)
+    // ptmi_update_triangles, allocated by the first update of a scene and freed with it: the caller's new triangles, and the
+    // inner records by level (ptmi_ctx::refit)
+    ptmi_triangle* d_update_tris = nullptr;
+    uint32_t* d_refit_nodes = nullptr;
     // ptmi_snapshot ring: float[5*W*H] per slot (colour, then count), allocated on first use
     float* d_snapshot[PTMI_MAX_SNAPSHOT_SLOTS] = {};
     hipEvent_t snapshot_ready[PTMI_MAX_SNAPSHOT_SLOTS] = {};
@@ -104,6 +110,10 @@ struct ptmi_ctx {
     // Why the uploaded scene is rendered by the one-path-per-lane kernel although the context did not ask for it (empty: it is
     // not).  See scene_needs_literal_kernel() in scene_layout.cpp.
     std::string literal_kernel_reason;
+    // ptmi_update_triangles: what it has to know of the uploaded scene, and the schedule of its refit (made by the first update)
+    UpdateFacts update;
+    RefitSchedule refit;
+    bool have_refit = false;
 
     // RCCL communicators, one per device of the context (single process, ncclCommInitAll): the sum of the devices' partial
     // images is an ncclReduce over xGMI where librccl is present and the devices are distinct (rccl_reduce_snapshots)
@@ -177,6 +187,8 @@ void free_scene_memory(ptmi_ctx* ctx)
         d.d_counters = nullptr;
         d.d_job_counter = nullptr;
         d.d_scene = nullptr;
+        d.d_update_tris = nullptr;
+        d.d_refit_nodes = nullptr;
         for (int i = 0; i < DeviceState::kStageSets; i++) {
             if (d.d_stage[i]) (void)hipFree(d.d_stage[i]);
             d.d_stage[i] = nullptr;
@@ -207,6 +219,8 @@ void free_scene_memory(ptmi_ctx* ctx)
     ctx->accum_bound = false;
     ctx->have_scene = false;
     ctx->literal_kernel_reason.clear();
+    ctx->have_refit = false;
+    ctx->refit = RefitSchedule();
 }
 
 template <class T>
@@ -940,6 +954,10 @@ int ptmi_initialize_memory(ptmi_ctx* ctx, const ptmi_scene* sc)
     }
     // a ray holds at most one pending far child per level it has descended
     ctx->stack_levels = lay.max_depth < 1 ? 1 : lay.max_depth;
+    ctx->update.triangulation_size = sc->triangulation_size;
+    ctx->update.n_big_leaves = (uint32_t)lay.big_leaves.size();
+    ctx->update.tris_precomputed = lay.tris_precomputed;
+    ctx->update.material_is_simple_color = lay.material_is_simple_color;
     for (DeviceState& d : ctx->dev)
         if (int rc = upload_scene(ctx, d, lay, sc)) {
             const std::string msg = ctx->err;
@@ -1360,6 +1378,145 @@ int ptmi_bind_accumulators(ptmi_ctx* ctx, void* d_color, void* d_count)
     d.ds.image_ray_nb = d_count ? (float*)d_count : d.d_count;
     ctx->accum_bound = d_color != nullptr;
     if (int rc = upload_scene_records(ctx, d)) return rc;
+    return PTMI_OK;
+}
+
+// Before the scene memory of device `d` is rewritten: a launch ahead may still be reading it (the stage sets' scene records
+// too), so drop them all and wait for their streams, then for the main stream (as ptmi_bind_accumulators does).
+static int quiesce(ptmi_ctx* ctx, DeviceState& d)
+{
+    ON_DEVICE(ctx, d);
+    d.schedule.forget();
+    for (int i = 0; i < DeviceState::kStageSets; i++)
+        if (d.launch_stream[i]) HIP_TRY(ctx, hipStreamSynchronize(d.launch_stream[i]));
+    HIP_TRY(ctx, hipStreamSynchronize(d.stream));
+    return PTMI_OK;
+}
+
+int ptmi_set_camera(ptmi_ctx* ctx, const ptmi_float4* position, const ptmi_float4* direction, const ptmi_float4* right, const ptmi_float4* up)
+{
+    if (!ctx) return PTMI_ERR_INVALID_ARGUMENT;
+    if (!position || !direction || !right || !up) return fail(ctx, PTMI_ERR_INVALID_ARGUMENT, "ptmi_set_camera: a camera vector is NULL");
+    if (!ctx->have_scene) return fail(ctx, PTMI_ERR_STATE, "ptmi_set_camera before ptmi_initialize_memory");
+    const std::string why = camera_needs_literal_kernel(*position, *direction, *right, *up);
+    if (!why.empty())
+        return fail(ctx, PTMI_ERR_UNSUPPORTED, "ptmi_set_camera: " + why + ": the kernel instantiation was chosen at upload, call "
+                                               "ptmi_initialize_memory with the new camera");
+    for (DeviceState& d : ctx->dev)
+        if (int rc = quiesce(ctx, d)) return rc;
+    for (DeviceState& d : ctx->dev) {
+        ON_DEVICE(ctx, d);
+        std::memcpy(d.ds.cam_pos, position, 16);
+        std::memcpy(d.ds.cam_dir, direction, 16);
+        std::memcpy(d.ds.cam_right, right, 16);
+        std::memcpy(d.ds.cam_up, up, 16);
+        if (int rc = upload_scene_records(ctx, d)) return rc;
+    }
+    return PTMI_OK;
+}
+
+int ptmi_update_triangles(ptmi_ctx* ctx, const ptmi_triangle* triangulation, uint32_t triangulation_size, ptmi_update_info* info)
+{
+    using clock = std::chrono::steady_clock;
+    auto ms_since = [](clock::time_point t) { return std::chrono::duration<double, std::milli>(clock::now() - t).count(); };
+    const clock::time_point t_call = clock::now();
+    if (info) {
+        *info = ptmi_update_info{};
+        info->struct_size = sizeof(ptmi_update_info);
+    }
+    if (!ctx) return PTMI_ERR_INVALID_ARGUMENT;
+    if (!triangulation) return fail(ctx, PTMI_ERR_INVALID_ARGUMENT, "ptmi_update_triangles: triangulation is NULL");
+    if (!ctx->have_scene) return fail(ctx, PTMI_ERR_STATE, "ptmi_update_triangles before ptmi_initialize_memory");
+    if (triangulation_size != ctx->update.triangulation_size)
+        return fail(ctx, PTMI_ERR_INVALID_ARGUMENT, "ptmi_update_triangles: " + std::to_string(triangulation_size) + " triangles, the context holds " +
+                                                    std::to_string(ctx->update.triangulation_size) + " (the topology cannot change)");
+    if (!ctx->literal_kernel_reason.empty())
+        return fail(ctx, PTMI_ERR_UNSUPPORTED, "ptmi_update_triangles: the uploaded scene has records that can yield NaN distances (" +
+                                               ctx->literal_kernel_reason + "): call ptmi_initialize_memory with the new scene");
+    // ---- everything that can refuse, before the first device write
+    {
+        std::string err;
+        if (int rc = screen_update(ctx->update, triangulation, triangulation_size, err)) return fail(ctx, rc, "ptmi_update_triangles: " + err);
+    }
+    DeviceState& lead = ctx->dev[0];
+    if (!ctx->have_refit) {
+        // the schedule of the refit, from the records as they were uploaded (every device holds the same)
+        ON_DEVICE(ctx, lead);
+        std::vector<DNode> records(lead.ds.n_records);
+        std::vector<uint32_t> tri_ids(lead.ds.n_records);
+        std::vector<DBigLeaf> big_leaves(ctx->update.n_big_leaves);
+        HIP_TRY(ctx, hipStreamSynchronize(lead.stream));
+        if (!records.empty()) {
+            HIP_TRY(ctx, hipMemcpy(records.data(), lead.ds.nodes, records.size() * sizeof(DNode), hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(tri_ids.data(), lead.ds.tri_ids, tri_ids.size() * 4, hipMemcpyDeviceToHost));
+        }
+        if (!big_leaves.empty())
+            HIP_TRY(ctx, hipMemcpy(big_leaves.data(), lead.ds.big_leaves, big_leaves.size() * sizeof(DBigLeaf), hipMemcpyDeviceToHost));
+        std::string err;
+        if (int rc = build_refit_schedule(records.data(), tri_ids.data(), lead.ds.n_records, big_leaves.data(), ctx->update.n_big_leaves,
+                                          lead.ds.root_ref, triangulation_size, ctx->refit, err)) {
+            ctx->refit = RefitSchedule();
+            return fail(ctx, rc, "ptmi_update_triangles: " + err);
+        }
+        ctx->have_refit = true;
+    }
+    for (DeviceState& d : ctx->dev) {  // (allocations can refuse too)
+        ON_DEVICE(ctx, d);
+        void* p = nullptr;
+        if (!d.d_update_tris) {
+            if (int rc = device_alloc(ctx, d, std::max<size_t>((size_t)triangulation_size * sizeof(ptmi_triangle), 16), &p)) return rc;
+            d.d_update_tris = (ptmi_triangle*)p;
+        }
+        if (!d.d_refit_nodes) {
+            if (int rc = device_alloc(ctx, d, std::max<size_t>(ctx->refit.nodes.size() * 4, 16), &p)) return rc;
+            if (!ctx->refit.nodes.empty())
+                HIP_TRY(ctx, hipMemcpy(p, ctx->refit.nodes.data(), ctx->refit.nodes.size() * 4, hipMemcpyHostToDevice));
+            d.d_refit_nodes = (uint32_t*)p;
+        }
+    }
+    const double validate_ms = ms_since(t_call);
+    for (DeviceState& d : ctx->dev)
+        if (int rc = quiesce(ctx, d)) return rc;
+    // ---- the update: new triangles up, then the records, the shading records and the boxes, level by level from the deepest
+    double upload_ms = 0, device_ms = 0;
+    for (DeviceState& d : ctx->dev) {
+        ON_DEVICE(ctx, d);
+        const clock::time_point t_upload = clock::now();
+        HIP_TRY(ctx, hipMemcpy(d.d_update_tris, triangulation, (size_t)triangulation_size * sizeof(ptmi_triangle), hipMemcpyHostToDevice));
+        upload_ms += ms_since(t_upload);
+        hipEvent_t begin = nullptr, end = nullptr;
+        HIP_TRY(ctx, hipEventCreate(&begin));
+        if (hipEventCreate(&end) != hipSuccess) {
+            (void)hipEventDestroy(begin);
+            return fail(ctx, PTMI_ERR_HIP, "ptmi_update_triangles: hipEventCreate failed");
+        }
+        std::string err;
+        int rc = hipEventRecord(begin, d.stream) == hipSuccess ? (int)PTMI_OK : (int)PTMI_ERR_HIP;
+        DTri* const records = const_cast<DTri*>(d.ds.tris);
+        if (!rc) rc = launch_update_tri_records(records, d.ds.tri_ids, d.ds.n_records, d.d_update_tris, triangulation_size, d.ds.tris_precomputed != 0, d.stream, &err);
+        if (!rc && default_arithmetic(ctx) && d.ds.tris_precomputed)  // the reciprocal determinants of that arithmetic, as at upload
+            rc = launch_precompute_denominators_da(records, d.ds.tri_ids, d.ds.n_records, d.stream, &err);
+        if (!rc) rc = launch_update_shade_records(const_cast<DShade*>(d.ds.shade), d.d_update_tris, triangulation_size, d.stream, &err);
+        for (uint32_t level = ctx->refit.levels(); !rc && level-- > 0;)
+            rc = launch_refit_level(const_cast<DNode*>(d.ds.nodes), d.d_refit_nodes + ctx->refit.first[level],
+                                    ctx->refit.first[level + 1] - ctx->refit.first[level], d.ds.big_leaves, d.ds.tri_ids, d.d_update_tris, d.stream, &err);
+        hipError_t e = hipEventRecord(end, d.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
+        float ms = 0;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, begin, end);
+        (void)hipEventDestroy(begin);
+        (void)hipEventDestroy(end);
+        if (rc) return fail(ctx, rc, "ptmi_update_triangles: " + err);
+        if (e != hipSuccess) return fail(ctx, PTMI_ERR_HIP, std::string("ptmi_update_triangles: ") + hipGetErrorString(e));
+        device_ms += ms;
+    }
+    if (info) {
+        info->levels = ctx->refit.levels();
+        info->upload_ms = upload_ms;
+        info->device_ms = device_ms;
+        info->validate_ms = validate_ms;
+        info->total_ms = ms_since(t_call);
+    }
     return PTMI_OK;
 }
 

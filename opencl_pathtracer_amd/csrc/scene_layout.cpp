@@ -1,5 +1,6 @@
 // scene_layout.cpp - validation and re-layout of a scene for the device (see scene_layout.h).  No device call in this file.
 #include "scene_layout.h"
+#include "scene_refit_common.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -49,38 +50,67 @@ bool texture_ok(const ptmi_texture& t, uint32_t data_size)
 //     (s and t may still overflow for a hit on a corrupted record's plane far outside its triangle; they only gate the
 //     acceptance, they do not enter the order).
 // Returns the reason, or an empty string.
+// The camera's and the lights' part is below; the triangle's part is triangle_needs_literal_kernel (also what an in-place update
+// of the triangles asks, scene_refit_host.cpp).
+constexpr float kCoord = 2097152.0f, kNormal = 16.0f;
+bool within(const ptmi_float4& v, float bound)
+{
+    return std::fabs(v.x) <= bound && std::fabs(v.y) <= bound && std::fabs(v.z) <= bound && std::fabs(v.w) <= bound;  // (false for NaN)
+}
+
 std::string scene_needs_literal_kernel(const ptmi_scene* sc)
 {
-    constexpr float kCoord = 2097152.0f, kNormal = 16.0f;
-    auto ok = [](const ptmi_float4& v, float bound) {
-        return std::fabs(v.x) <= bound && std::fabs(v.y) <= bound && std::fabs(v.z) <= bound && std::fabs(v.w) <= bound;  // (false for NaN)
-    };
-    if (!ok(sc->camera_position, kCoord) || !ok(sc->camera_direction, kCoord) || !ok(sc->camera_right, kCoord) || !ok(sc->camera_up, kCoord))
-        return "the camera is not finite (or beyond 2^21)";
+    const std::string camera = camera_needs_literal_kernel(sc->camera_position, sc->camera_direction, sc->camera_right, sc->camera_up);
+    if (!camera.empty()) return camera;
     for (uint32_t i = 0; i < sc->lights_size; i++)
-        if (!ok(sc->lights[i].position, kCoord) || !ok(sc->lights[i].direction, kCoord))
+        if (!within(sc->lights[i].position, kCoord) || !within(sc->lights[i].direction, kCoord))
             return "light " + std::to_string(i) + " is not finite (or beyond 2^21)";
-    auto dot4 = [](const float a[4], const float b[4]) {
-        return std::fmaf(a[3], b[3], std::fmaf(a[2], b[2], std::fmaf(a[1], b[1], a[0] * b[0])));
-    };
     for (uint32_t i = 0; i < sc->triangulation_size; i++) {
-        const ptmi_triangle& t = sc->triangulation[i];
-        if (!ok(t.s1, kCoord) || !ok(t.s2, kCoord) || !ok(t.s3, kCoord))
-            return "triangle " + std::to_string(i) + " has a vertex that is not finite (or beyond 2^21)";
-        if (!ok(t.n, kNormal) || !ok(t.n1, kNormal) || !ok(t.n2, kNormal) || !ok(t.n3, kNormal))
-            return "triangle " + std::to_string(i) + " has a normal that is not finite (a zero-area triangle of the importer: N = 0/0)";
-        const float u[4] = {t.s2.x - t.s1.x, t.s2.y - t.s1.y, t.s2.z - t.s1.z, t.s2.w - t.s1.w};
-        const float v[4] = {t.s3.x - t.s1.x, t.s3.y - t.s1.y, t.s3.z - t.s1.z, t.s3.w - t.s1.w};
-        const float uv = dot4(u, v), uu = dot4(u, u), vv = dot4(v, v);
-        const float det[2] = {uv * uv - uu * vv, std::fmaf(uv, uv, -(uu * vv))};  // cl:556, strict and default arithmetic
-        for (float d : det)
-            if (!(d != 0.0f) || !std::isfinite(d) || !std::isfinite(1.0f / d))
-                return "triangle " + std::to_string(i) + " has no area (its barycentric determinant is zero or not finite)";
+        const std::string why = triangle_needs_literal_kernel(sc->triangulation[i], i);
+        if (!why.empty()) return why;
     }
     return std::string();
 }
 
 }  // namespace
+
+std::string camera_needs_literal_kernel(const ptmi_float4& position, const ptmi_float4& direction, const ptmi_float4& right, const ptmi_float4& up)
+{
+    if (!within(position, kCoord) || !within(direction, kCoord) || !within(right, kCoord) || !within(up, kCoord))
+        return "the camera is not finite (or beyond 2^21)";
+    return std::string();
+}
+
+std::string triangle_needs_literal_kernel(const ptmi_triangle& t, uint32_t i)
+{
+    if (!within(t.s1, kCoord) || !within(t.s2, kCoord) || !within(t.s3, kCoord))
+        return "triangle " + std::to_string(i) + " has a vertex that is not finite (or beyond 2^21)";
+    if (!within(t.n, kNormal) || !within(t.n1, kNormal) || !within(t.n2, kNormal) || !within(t.n3, kNormal))
+        return "triangle " + std::to_string(i) + " has a normal that is not finite (a zero-area triangle of the importer: N = 0/0)";
+    float u[4], v[4];
+    ptmi_refit::triangle_edges(t, u, v);
+    const float uv = ptmi_refit::dot4(u, v), uu = ptmi_refit::dot4(u, u), vv = ptmi_refit::dot4(v, v);
+    const float det[2] = {uv * uv - uu * vv, std::fmaf(uv, uv, -(uu * vv))};  // cl:556, strict and default arithmetic
+    for (float d : det)
+        if (!(d != 0.0f) || !std::isfinite(d) || !std::isfinite(1.0f / d))
+            return "triangle " + std::to_string(i) + " has no area (its barycentric determinant is zero or not finite)";
+    return std::string();
+}
+
+int check_triangle_materials(const ptmi_triangle& t, uint32_t i, const uint8_t* material_is_simple_color, uint32_t materiaux_size, std::string& err)
+{
+    if (t.mat_pos >= materiaux_size || t.mat_neg >= materiaux_size)
+        return fail(err, PTMI_ERR_BAD_SCENE, "triangle " + std::to_string(i) + " references a material out of range");
+    if (!material_is_simple_color[t.mat_pos] || !material_is_simple_color[t.mat_neg]) {
+        // texture coordinates index texels (header.cl:430-459: u - (int)u, then (uint)(u * (width - 1))): beyond the int range the
+        // wrap does nothing and the index leaves the texture - in the reference as well, which reads whatever is there
+        const float* uv = reinterpret_cast<const float*>(&t.uvp1);
+        for (int k = 0; k < 12; k++)
+            if (!(std::fabs(uv[k]) <= 0x1p+30f))
+                return fail(err, PTMI_ERR_BAD_SCENE, "triangle " + std::to_string(i) + " has texture coordinates that are not finite (or beyond 2^30)");
+    }
+    return PTMI_OK;
+}
 
 int build_layout(const ptmi_config& cfg, const ptmi_scene* sc, Relayout& out, std::string& err)
 {
@@ -125,28 +155,13 @@ int build_layout(const ptmi_config& cfg, const ptmi_scene* sc, Relayout& out, st
 
     out.tris.resize(nt);
     out.shade.resize(nt);
+    out.material_is_simple_color.resize(sc->materiaux_size);
+    for (uint32_t i = 0; i < sc->materiaux_size; i++) out.material_is_simple_color[i] = sc->materiaux[i].is_simple_color ? 1 : 0;
     for (uint32_t i = 0; i < nt; i++) {
         const ptmi_triangle& t = sc->triangulation[i];
-        if (t.mat_pos >= sc->materiaux_size || t.mat_neg >= sc->materiaux_size)
-            return fail(err, PTMI_ERR_BAD_SCENE, "triangle " + std::to_string(i) + " references a material out of range");
-        if (!sc->materiaux[t.mat_pos].is_simple_color || !sc->materiaux[t.mat_neg].is_simple_color) {
-            // texture coordinates index texels (header.cl:430-459: u - (int)u, then (uint)(u * (width - 1))): beyond the int range the
-            // wrap does nothing and the index leaves the texture - in the reference as well, which reads whatever is there
-            const float* uv = reinterpret_cast<const float*>(&t.uvp1);
-            for (int k = 0; k < 12; k++)
-                if (!(std::fabs(uv[k]) <= 0x1p+30f))
-                    return fail(err, PTMI_ERR_BAD_SCENE, "triangle " + std::to_string(i) + " has texture coordinates that are not finite (or beyond 2^30)");
-        }
-        DTri& d = out.tris[i];
-        std::memcpy(d.s1, &t.s1, 16); std::memcpy(d.s2, &t.s2, 16); std::memcpy(d.s3, &t.s3, 16);
-        std::memcpy(d.n, &t.n, 16);
-        DShade& s = out.shade[i];
-        std::memset(&s, 0, sizeof s);
-        std::memcpy(s.n1, &t.n1, 16); std::memcpy(s.n2, &t.n2, 16); std::memcpy(s.n3, &t.n3, 16);
-        std::memcpy(s.uvp, &t.uvp1, 24);
-        std::memcpy(s.uvn, &t.uvn1, 24);
-        s.mat_pos = t.mat_pos;
-        s.mat_neg = t.mat_neg;
+        if (int rc = check_triangle_materials(t, i, out.material_is_simple_color.data(), sc->materiaux_size, err)) return rc;
+        ptmi_refit::make_tri_record(t, &out.tris[i]);
+        ptmi_refit::make_shade_record(t, &out.shade[i]);
     }
 
     out.literal_kernel_reason = scene_needs_literal_kernel(sc);
@@ -155,29 +170,11 @@ int build_layout(const ptmi_config& cfg, const ptmi_scene* sc, Relayout& out, st
     // on its three vertices (then the edge vectors have w = +0 exactly).  Same operations, same order, same
     // rounding as the kernel's generic form: dot() = fma chain over four components (ptmi_device.hpp).
     out.tris_precomputed = std::getenv("PTMI_GENERIC_TRIANGLES") == nullptr;  // developer switch for A/B runs
-    for (uint32_t i = 0; i < nt && out.tris_precomputed; i++) {
-        const ptmi_triangle& t = sc->triangulation[i];
-        if (!(t.s1.w == t.s2.w && t.s1.w == t.s3.w && std::isfinite(t.s1.w))) out.tris_precomputed = false;  // edge vectors need w = +0 exactly
-    }
-    if (out.tris_precomputed) {
-        auto dot4 = [](const float a[4], const float b[4]) {
-            return std::fmaf(a[3], b[3], std::fmaf(a[2], b[2], std::fmaf(a[1], b[1], a[0] * b[0])));
-        };
-        for (uint32_t i = 0; i < nt; i++) {
-            const ptmi_triangle& t = sc->triangulation[i];
-            const float S1[4] = {t.s1.x, t.s1.y, t.s1.z, t.s1.w}, N[4] = {t.n.x, t.n.y, t.n.z, t.n.w};
-            const float u[4] = {t.s2.x - t.s1.x, t.s2.y - t.s1.y, t.s2.z - t.s1.z, t.s2.w - t.s1.w};
-            const float v[4] = {t.s3.x - t.s1.x, t.s3.y - t.s1.y, t.s3.z - t.s1.z, t.s3.w - t.s1.w};
-            const float uv = dot4(u, v), uu = dot4(u, u), vv = dot4(v, v);
-            const float denom = 1 / (uv * uv - uu * vv);
-            DTriPre p;
-            std::memcpy(p.n, N, 16);
-            p.s1d[0] = S1[0]; p.s1d[1] = S1[1]; p.s1d[2] = S1[2]; p.s1d[3] = dot4(N, S1);
-            p.u_den[0] = u[0]; p.u_den[1] = u[1]; p.u_den[2] = u[2]; p.u_den[3] = denom;
-            p.v_s1w[0] = v[0]; p.v_s1w[1] = v[1]; p.v_s1w[2] = v[2]; p.v_s1w[3] = S1[3];
-            std::memcpy(&out.tris[i], &p, sizeof p);
-        }
-    }
+    for (uint32_t i = 0; i < nt && out.tris_precomputed; i++)
+        if (!ptmi_refit::triangle_keeps_equal_w(sc->triangulation[i])) out.tris_precomputed = false;  // edge vectors need w = +0 exactly
+    if (out.tris_precomputed)
+        for (uint32_t i = 0; i < nt; i++)  // (scene_refit_common.h: the one copy of the expressions, the device's too)
+            ptmi_refit::make_tri_record_pre(sc->triangulation[i], reinterpret_cast<DTriPre*>(&out.tris[i]));
 
     // Walk the tree from bvh[0] exactly as the traversal could and emit ONE array of 64-byte records in depth-first
     // order: an inner node's record, then the triangles of its leaf children, then son1's subtree, then son2's.

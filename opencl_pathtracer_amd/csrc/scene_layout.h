@@ -18,6 +18,7 @@ struct Relayout {
     std::vector<DTri> tris;          // per input triangle, only a staging area for recs
     std::vector<DShade> shade;
     std::vector<DMat> mats;
+    std::vector<uint8_t> material_is_simple_color;  // per material: what check_triangle_materials asks
     std::vector<DBigLeaf> big_leaves;
     bool tris_precomputed = false;
     bool plain_shading = false; // every material a plain-colour MAT_STANDART, every light a LIGHT_POINT
@@ -31,6 +32,13 @@ struct Relayout {
     // index; 0xFFFFFFFF: the walk meets no triangle), so that the literal loops can skip it (ptmi_literal_path.hpp).
     uint32_t nan_walk_box_tests = 0, nan_walk_tri_tests = 0, nan_walk_last_tri = 0xFFFFFFFFu;
 };
+
+// The per-record parts of the validation, which an in-place update applies to new cameras and triangles (scene_refit_host.cpp):
+// why the camera / triangle `i` can make a triangle test compute a NaN distance (empty: it cannot; scene_layout.cpp:
+// scene_needs_literal_kernel), and whether the triangle's materials exist and its texture coordinates can index texels.
+std::string camera_needs_literal_kernel(const ptmi_float4& position, const ptmi_float4& direction, const ptmi_float4& right, const ptmi_float4& up);
+std::string triangle_needs_literal_kernel(const ptmi_triangle& t, uint32_t i);
+int check_triangle_materials(const ptmi_triangle& t, uint32_t i, const uint8_t* material_is_simple_color, uint32_t materiaux_size, std::string& err);
 
 // Returns PTMI_OK or an error code with its message in `err`.  cfg: lights_size and sampler are read.
 int build_layout(const ptmi_config& cfg, const ptmi_scene* sc, Relayout& out, std::string& err);

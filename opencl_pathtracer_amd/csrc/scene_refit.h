@@ -1,0 +1,54 @@
+// scene_refit.h - updating a loaded scene in place: the host side without a device call (scene_refit_host.cpp: ptmi_bvh_refit, the
+// screen of new triangles, the schedule of the device refit) and the launches of scene_refit.hip.  See DESIGN.md 1b.
+#pragma once
+
+#include <string>
+#include <vector>
+
+#include "ptmi.h"
+#include "ptmi_internal.h"
+
+namespace ptmi_internal {
+
+// What ptmi_update_triangles has to know about the scene a context holds, kept by ptmi_initialize_memory (a few bytes per
+// material: a context that never updates pays nothing else).
+struct UpdateFacts {
+    uint32_t triangulation_size = 0;
+    uint32_t n_big_leaves = 0;
+    bool tris_precomputed = false;
+    std::vector<uint8_t> material_is_simple_color;
+};
+
+// The screen of ptmi_update_triangles, applied before the first device write: build_layout's checks on triangles (materials,
+// texture coordinates: PTMI_ERR_BAD_SCENE) and what an update cannot express without a new upload (PTMI_ERR_UNSUPPORTED): a record
+// that could yield NaN distances (the kernel instantiation was chosen at upload), unequal w where the records are DTriPre, an
+// aabb that is marked empty, not finite or not ordered (the references' empty flags and boxes_ordered are upload-time facts).
+int screen_update(const UpdateFacts& facts, const ptmi_triangle* triangulation, uint32_t triangulation_size, std::string& err);
+
+// The inner records of the one record array by depth (root = level 0): level k is nodes[first[k] .. first[k + 1]).  A level pass
+// of the refit reads the records of the level below and writes its own, so the passes run from the last level to level 0.
+struct RefitSchedule {
+    std::vector<uint32_t> nodes;
+    std::vector<uint32_t> first;  // levels() + 1 entries
+    uint32_t levels() const { return first.empty() ? 0u : (uint32_t)first.size() - 1u; }
+};
+
+// Walks the records top-down from root_ref and checks everything the refit kernels will index (record and triangle indices,
+// leaf ranges, big_leaves, a record reached twice) and that a reference is flagged empty exactly where nothing lies below it -
+// what ptmi_bvh_refit's tree would say.  PTMI_ERR_UNSUPPORTED where the uploaded tree says otherwise, PTMI_ERR_INTERNAL for
+// an index out of range (the records are the library's own).
+int build_refit_schedule(const DNode* records, const uint32_t* tri_ids, uint32_t n_records, const DBigLeaf* big_leaves,
+                         uint32_t n_big_leaves, uint32_t root_ref, uint32_t triangulation_size, RefitSchedule& out, std::string& err);
+
+// ---- scene_refit.hip: every launch is asynchronous on `stream`; the caller's bounds are the schedule's ---------------------
+// records[r] = the DTri (or DTriPre, strict reciprocal) record of triangulation[tri_ids[r]] where tri_ids[r] < triangulation_size
+// (a node record's is 0xFFFFFFFF)
+int launch_update_tri_records(DTri* records, const uint32_t* tri_ids, uint32_t n_records, const ptmi_triangle* triangulation,
+                              uint32_t triangulation_size, bool tris_precomputed, void* stream, std::string* err);
+// shade[i] = the DShade record of triangulation[i]
+int launch_update_shade_records(DShade* shade, const ptmi_triangle* triangulation, uint32_t triangulation_size, void* stream, std::string* err);
+// one level pass: both child boxes of records[level_nodes[k]], k < n
+int launch_refit_level(DNode* records, const uint32_t* level_nodes, uint32_t n, const DBigLeaf* big_leaves, const uint32_t* tri_ids,
+                       const ptmi_triangle* triangulation, void* stream, std::string* err);
+
+}  // namespace ptmi_internal

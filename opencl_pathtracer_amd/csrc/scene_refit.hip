@@ -1,0 +1,100 @@
+// scene_refit.hip - the device side of ptmi_update_triangles: the records of a loaded scene rewritten from a new triangulation
+// (see scene_refit.h).  Three streaming kernels, one lane per record / triangle / inner node of a level; every
+// value comes from scene_refit_common.h, the header the host's upload path and the serial model (tests/scene_refit_model.cpp)
+// compute it from.  No atomics, nothing shared between lanes: a lane reads the caller's triangles and, in a level pass, records
+// of the level below (written by an earlier launch), and writes the one record that is its own, as whole 16-byte words.
+#include <hip/hip_runtime.h>
+
+#include "scene_refit.h"
+#include "scene_refit_common.h"
+
+namespace ptmi_internal {
+
+namespace {
+
+constexpr uint32_t kBlock = 256;
+
+// `Words` 16-byte words from a lane's own copy of a record to the record array
+template <int Words>
+__device__ __forceinline__ void store_words(void* dst, const void* src)
+{
+    float4* const d = static_cast<float4*>(dst);
+    const float4* const s = static_cast<const float4*>(src);
+#pragma unroll
+    for (int k = 0; k < Words; k++) d[k] = s[k];
+}
+
+template <bool Precomputed>
+__global__ void __launch_bounds__(kBlock) update_tri_records_kernel(DTri* __restrict__ records, const uint32_t* __restrict__ tri_ids,
+                                                                    const uint32_t n_records, const ptmi_triangle* __restrict__ tris,
+                                                                    const uint32_t n_tris)
+{
+    const uint32_t r = blockIdx.x * kBlock + threadIdx.x;
+    if (r >= n_records) return;
+    const uint32_t id = tri_ids[r];
+    if (id >= n_tris) return;  // (a node record's 0xFFFFFFFF)
+    alignas(16) DTri rec;
+    if (Precomputed) ptmi_refit::make_tri_record_pre(tris[id], reinterpret_cast<DTriPre*>(&rec));
+    else ptmi_refit::make_tri_record(tris[id], &rec);
+    store_words<4>(records + r, &rec);
+}
+
+__global__ void __launch_bounds__(kBlock) update_shade_records_kernel(DShade* __restrict__ shade, const ptmi_triangle* __restrict__ tris,
+                                                                      const uint32_t n_tris)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n_tris) return;
+    alignas(16) DShade rec;
+    ptmi_refit::make_shade_record(tris[i], &rec);
+    store_words<sizeof(DShade) / 16>(shade + i, &rec);
+}
+
+// (records: read at the children's indices, written at the lane's own - no __restrict__)
+__global__ void __launch_bounds__(kBlock) refit_level_kernel(DNode* records, const uint32_t* __restrict__ level_nodes, const uint32_t n,
+                                                             const DBigLeaf* __restrict__ big_leaves, const uint32_t* __restrict__ tri_ids,
+                                                             const ptmi_triangle* __restrict__ tris)
+{
+    const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
+    if (k >= n) return;
+    DNode* const mine = records + level_nodes[k];
+    alignas(16) DNode d;
+    store_words<4>(&d, mine);
+    ptmi_refit::refit_record(&d, records, big_leaves, tri_ids, tris);
+    store_words<4>(mine, &d);
+}
+
+dim3 grid_for(uint32_t n) { return dim3((n + kBlock - 1) / kBlock); }
+
+}  // namespace
+
+int launch_update_tri_records(DTri* records, const uint32_t* tri_ids, uint32_t n_records, const ptmi_triangle* triangulation,
+                              uint32_t triangulation_size, bool tris_precomputed, void* stream, std::string* err)
+{
+    if (n_records == 0) return PTMI_OK;
+    if (tris_precomputed)
+        hipLaunchKernelGGL(update_tri_records_kernel<true>, grid_for(n_records), dim3(kBlock), 0, (hipStream_t)stream, records, tri_ids,
+                           n_records, triangulation, triangulation_size);
+    else
+        hipLaunchKernelGGL(update_tri_records_kernel<false>, grid_for(n_records), dim3(kBlock), 0, (hipStream_t)stream, records, tri_ids,
+                           n_records, triangulation, triangulation_size);
+    return launch_status(hipGetLastError(), "update_tri_records_kernel", err);
+}
+
+int launch_update_shade_records(DShade* shade, const ptmi_triangle* triangulation, uint32_t triangulation_size, void* stream, std::string* err)
+{
+    if (triangulation_size == 0) return PTMI_OK;
+    hipLaunchKernelGGL(update_shade_records_kernel, grid_for(triangulation_size), dim3(kBlock), 0, (hipStream_t)stream, shade, triangulation,
+                       triangulation_size);
+    return launch_status(hipGetLastError(), "update_shade_records_kernel", err);
+}
+
+int launch_refit_level(DNode* records, const uint32_t* level_nodes, uint32_t n, const DBigLeaf* big_leaves, const uint32_t* tri_ids,
+                       const ptmi_triangle* triangulation, void* stream, std::string* err)
+{
+    if (n == 0) return PTMI_OK;
+    hipLaunchKernelGGL(refit_level_kernel, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, records, level_nodes, n, big_leaves, tri_ids,
+                       triangulation);
+    return launch_status(hipGetLastError(), "refit_level_kernel", err);
+}
+
+}  // namespace ptmi_internal

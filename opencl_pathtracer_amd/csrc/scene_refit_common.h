@@ -1,0 +1,159 @@
+// scene_refit_common.h - the arithmetic of an in-place scene update, shared by the host (scene_layout.cpp, scene_refit_host.cpp),
+// the device (scene_refit.hip) and the serial model of the device schedule (tests/scene_refit_model.cpp).
+//
+// Two things live here, once:
+//   * a triangle's device records (DTri / DTriPre / DShade) as build_layout writes them at upload, so that a record rewritten on
+//     the device holds the bytes a fresh upload of the same triangle would;
+//   * the refit of a box from the boxes below it: a leaf's box is the fold of its triangles' `aabb` in ascending index order
+//     (pbox_unite: of values that compare equal the first one wins), an inner node's is pbox_merge(son1, son2) - son1's range
+//     precedes son2's, so the merge is the fold over the whole range (bvh_build_common.h).
+//     A corner whose refitted value compares equal to the one the box holds keeps the bits it holds (keep_sel): the only
+//     values that compare equal and differ are -0 and +0, and which of the two a builder's box holds was decided by the order
+//     in which the builder met them (its bins, its triangles before the partition) - an order the finished tree no longer
+//     tells.  So a refit with unchanged triangles changes no byte, and one with moved triangles changes what moved.
+//
+// Compile with -ffp-contract=off (host and device): the products and sums of the DTriPre record are the kernel's own, fused
+// only where fmaf says so.
+#ifndef PTMI_SCENE_REFIT_COMMON_H
+#define PTMI_SCENE_REFIT_COMMON_H
+
+#include <cmath>
+#include <cstdint>
+
+#include "bvh_build_common.h"
+#include "ptmi_internal.h"
+
+namespace ptmi_refit {
+
+using ptmi_bvh::PBox;
+using ptmi_internal::DBigLeaf;
+using ptmi_internal::DNode;
+using ptmi_internal::DShade;
+using ptmi_internal::DTri;
+using ptmi_internal::DTriPre;
+
+// dot() of the kernels: an fma chain over four components (ptmi_device.hpp)
+PTMI_HD float dot4(const float a[4], const float b[4])
+{
+    return fmaf(a[3], b[3], fmaf(a[2], b[2], fmaf(a[1], b[1], a[0] * b[0])));
+}
+
+// the edge vectors S2 - S1 and S3 - S1 of the triangle test (FullKernel.cl:528-529)
+PTMI_HD void triangle_edges(const ptmi_triangle& t, float u[4], float v[4])
+{
+    u[0] = t.s2.x - t.s1.x; u[1] = t.s2.y - t.s1.y; u[2] = t.s2.z - t.s1.z; u[3] = t.s2.w - t.s1.w;
+    v[0] = t.s3.x - t.s1.x; v[1] = t.s3.y - t.s1.y; v[2] = t.s3.z - t.s1.z; v[3] = t.s3.w - t.s1.w;
+}
+
+// The DTriPre form needs the importers' convention of equal w on the three vertices: the edge vectors then have w = +0 exactly.
+PTMI_HD bool triangle_keeps_equal_w(const ptmi_triangle& t)
+{
+    return t.s1.w == t.s2.w && t.s1.w == t.s3.w && std::isfinite(t.s1.w);
+}
+
+PTMI_HD void store4(float d[4], const ptmi_float4& v) { d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w; }
+
+// What the intersection test reads, generic form: the three vertices and the normal.
+PTMI_HD void make_tri_record(const ptmi_triangle& t, DTri* d)
+{
+    store4(d->s1, t.s1); store4(d->s2, t.s2); store4(d->s3, t.s3); store4(d->n, t.n);
+}
+
+// The ray-independent part of Triangle_Intersects (FullKernel.cl:528-556) done once: the same operations, the same order, the
+// same rounding as the kernel's generic form, with the correctly rounded reciprocal of the strict arithmetic (the default
+// arithmetic's reciprocal is a device instruction's: launch_precompute_denominators_da patches u_den[3] afterwards).
+PTMI_HD void make_tri_record_pre(const ptmi_triangle& t, DTriPre* p)
+{
+    const float S1[4] = {t.s1.x, t.s1.y, t.s1.z, t.s1.w}, N[4] = {t.n.x, t.n.y, t.n.z, t.n.w};
+    float u[4], v[4];
+    triangle_edges(t, u, v);
+    const float uv = dot4(u, v), uu = dot4(u, u), vv = dot4(v, v);
+    const float denom = 1 / (uv * uv - uu * vv);
+    p->n[0] = N[0]; p->n[1] = N[1]; p->n[2] = N[2]; p->n[3] = N[3];
+    p->s1d[0] = S1[0]; p->s1d[1] = S1[1]; p->s1d[2] = S1[2]; p->s1d[3] = dot4(N, S1);
+    p->u_den[0] = u[0]; p->u_den[1] = u[1]; p->u_den[2] = u[2]; p->u_den[3] = denom;
+    p->v_s1w[0] = v[0]; p->v_s1w[1] = v[1]; p->v_s1w[2] = v[2]; p->v_s1w[3] = S1[3];
+}
+
+// What only a confirmed surface hit reads.
+PTMI_HD void make_shade_record(const ptmi_triangle& t, DShade* s)
+{
+    store4(s->n1, t.n1); store4(s->n2, t.n2); store4(s->n3, t.n3);
+    s->uvp[0] = t.uvp1.x; s->uvp[1] = t.uvp1.y; s->uvp[2] = t.uvp2.x; s->uvp[3] = t.uvp2.y; s->uvp[4] = t.uvp3.x; s->uvp[5] = t.uvp3.y;
+    s->uvn[0] = t.uvn1.x; s->uvn[1] = t.uvn1.y; s->uvn[2] = t.uvn2.x; s->uvn[3] = t.uvn2.y; s->uvn[4] = t.uvn3.x; s->uvn[5] = t.uvn3.y;
+    s->mat_pos = t.mat_pos;
+    s->mat_neg = t.mat_neg;
+    s->pad[0] = s->pad[1] = 0;
+}
+
+// ---- refit --------------------------------------------------------------------------------------------------------------
+
+// `box` united with the aabb of the triangles tri_at(0), tri_at(1), ... tri_at(count - 1), in that order; boxes marked empty are
+// skipped (BoundingBox_UniteWith), and `cen`, if given, takes their centroids as points (BoundingBox_AddPoint takes all).
+template <class TriAt>
+PTMI_HD void fold_triangles(uint32_t count, TriAt tri_at, PBox* box, PBox* cen)
+{
+    for (uint32_t k = 0; k < count; k++) {
+        const ptmi_bounding_box& a = tri_at(k).aabb;
+        if (!a.is_empty) ptmi_bvh::pbox_unite(*box, a.p_min, a.p_max, a.centroid);
+        if (cen) ptmi_bvh::pbox_add_point(*cen, a.centroid);
+    }
+}
+
+// of a refitted value and the held one: the held one where they compare equal (-0 / +0), else the refitted one
+PTMI_HD float keep_sel(float held, float fresh) { return fresh == held ? held : fresh; }
+PTMI_HD ptmi_float4 keep4(const ptmi_float4& held, const ptmi_float4& fresh)
+{
+    return { keep_sel(held.x, fresh.x), keep_sel(held.y, fresh.y), keep_sel(held.z, fresh.z), keep_sel(held.w, fresh.w) };
+}
+
+PTMI_HD PBox corners_box(const float lo[3], const float hi[3])
+{
+    PBox b;
+    b.p_min = ptmi_float4{lo[0], lo[1], lo[2], 0};
+    b.p_max = ptmi_float4{hi[0], hi[1], hi[2], 0};
+    b.centroid = ptmi_float4{0, 0, 0, 0};
+    b.n = 2;  // (a box of a subtree: its centroid is never asked for, only whether it holds anything)
+    return b;
+}
+
+// The box of the child behind `ref` of an inner record, from what lies below it in the ONE record array: a leaf's triangles
+// (through tri_ids into the caller's new triangulation; a big leaf through big_leaves[]), or the two boxes an inner child's own
+// record holds - which the level below has refitted already; lo / hi come in as the corners the record holds and keep their bits
+// where the value stays (keep_sel).  `ref` is not flagged empty.  Update refuses triangles whose aabb
+// is marked empty, so every triangle counts here and the flags of the references stay what the topology made them.
+PTMI_HD void refit_child_box(uint32_t ref, const DNode* nodes, const DBigLeaf* big_leaves, const uint32_t* tri_ids,
+                             const ptmi_triangle* tris, float lo[3], float hi[3])
+{
+    using namespace ptmi_internal;
+    PBox b = ptmi_bvh::pbox_empty();
+    if (ref & REF_LEAF) {
+        uint32_t count = (ref >> REF_COUNT_SHIFT) & 7u, start = ref & REF_INDEX_MASK_LEAF;
+        if (count == REF_COUNT_BIG) { const DBigLeaf bl = big_leaves[start]; start = bl.start; count = bl.count; }
+        const uint32_t* ids = tri_ids + start;
+        for (uint32_t k = 0; k < count; k++) {
+            const ptmi_bounding_box& a = tris[ids[k]].aabb;
+            ptmi_bvh::pbox_unite(b, a.p_min, a.p_max, a.p_min);
+        }
+    } else {
+        const DNode& c = nodes[ref & REF_INDEX_MASK_INNER];
+        const PBox first = (c.ref1 & REF_EMPTY) ? ptmi_bvh::pbox_empty() : corners_box(c.lo1, c.hi1);
+        const PBox second = (c.ref2 & REF_EMPTY) ? ptmi_bvh::pbox_empty() : corners_box(c.lo2, c.hi2);
+        b = ptmi_bvh::pbox_merge(first, second);
+    }
+    lo[0] = keep_sel(lo[0], b.p_min.x); lo[1] = keep_sel(lo[1], b.p_min.y); lo[2] = keep_sel(lo[2], b.p_min.z);
+    hi[0] = keep_sel(hi[0], b.p_max.x); hi[1] = keep_sel(hi[1], b.p_max.y); hi[2] = keep_sel(hi[2], b.p_max.z);
+}
+
+// One inner record of a level pass: both child boxes refitted; a child flagged empty keeps what it holds (the inverted infinite
+// box where the boxes are ordered).  Reads records of the level below only, writes `d` only: a level's records can be taken in
+// any order.
+PTMI_HD void refit_record(DNode* d, const DNode* nodes, const DBigLeaf* big_leaves, const uint32_t* tri_ids, const ptmi_triangle* tris)
+{
+    if (!(d->ref1 & ptmi_internal::REF_EMPTY)) refit_child_box(d->ref1, nodes, big_leaves, tri_ids, tris, d->lo1, d->hi1);
+    if (!(d->ref2 & ptmi_internal::REF_EMPTY)) refit_child_box(d->ref2, nodes, big_leaves, tri_ids, tris, d->lo2, d->hi2);
+}
+
+}  // namespace ptmi_refit
+
+#endif  // PTMI_SCENE_REFIT_COMMON_H

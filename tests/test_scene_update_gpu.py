@@ -1,0 +1,361 @@
+"""Updating a loaded scene in place: ptmi_set_camera and ptmi_update_triangles against a fresh upload.
+
+The yardstick is always a SECOND context that was given the new scene through ptmi_initialize_memory - the new camera, or the new
+triangles with ptmi_bvh_refit's tree - which is code that existed before the update calls did.  What the two contexts render must
+be bit-equal: image, sample counts, the three histograms and ptmi_counters.  Refused updates must leave the old scene rendering
+as before.
+"""
+import copy
+
+import numpy as np
+import pytest
+
+from opencl_pathtracer_amd import Backend, PtmiError, backend, bvh_create, scenes, structs as S
+import scene_update_cases as U
+
+pytestmark = pytest.mark.gpu
+W, H = 64, 48
+DA = backend.FLAG_DEFAULT_ARITHMETIC
+INVALID_ARGUMENT, BAD_SCENE, STATE, UNSUPPORTED = -1, -5, -6, -7
+_cache = {}
+
+
+def scene(name):
+    if name not in _cache:
+        if name == "big_leaf":
+            sc = bvh_create(U.big_leaf_scene(W, H))
+            assert sc.bvh["nbTriangles"][sc.bvh["isLeaf"] != 0].max() >= 9
+        elif name == "empty_leaves":
+            sc = U.with_empty_leaves(scene("cornell"))
+        elif name == "textured":
+            sc = bvh_create(scenes.feature_scene("textured", W, H))
+        else:
+            sc = bvh_create(scenes.build(name, W, H))
+        _cache[name] = sc
+    return _cache[name]
+
+
+def context(sc, depth=4, flags=0, sampler=S.JITTERED, super_sampling=False, devices=None):
+    be = Backend().setup_context(W, H, depth, sc.lightsSize, sampler, super_sampling=super_sampling, flags=flags, devices=devices)
+    be.initialize_memory(sc)
+    return be
+
+
+def state(be, variance=False):
+    color, count = be.read_image()
+    out = dict(color=color.view(np.uint32).copy(), count=count.copy(), stats=[s.copy() for s in be.read_statistics()], counters=be.counters())
+    if variance:
+        out["variance"] = be.read_variance().view(np.uint32).copy()
+    return out
+
+
+def assert_same(a, b):
+    assert a["counters"] == b["counters"], (a["counters"], b["counters"])
+    for x, y in zip(a["stats"], b["stats"]):
+        assert np.array_equal(x, y)
+    assert np.array_equal(a["count"], b["count"])
+    diff = int((a["color"] != b["color"]).any(axis=-1).sum())
+    assert diff == 0, f"{diff} pixels differ"
+    if "variance" in a or "variance" in b:
+        assert np.array_equal(a["variance"], b["variance"])
+
+
+def moved_camera(sc, step=1):
+    """`sc` seen from a little to the side, the view tilted about the camera's right axis (the frame stays orthonormal)."""
+    out = copy.copy(sc)
+    a = np.float32(0.07 * step)
+    c, s = np.float32(np.cos(a)), np.float32(np.sin(a))
+    d, u = np.asarray(sc.cameraDirection, np.float32), np.asarray(sc.cameraUp, np.float32)
+    out.cameraPosition = (np.asarray(sc.cameraPosition, np.float32) + np.float32([0.11 * step, -0.05 * step, 0.02, 0])).astype(np.float32)
+    out.cameraDirection = (c * d + s * u).astype(np.float32)
+    out.cameraUp = (c * u - s * d).astype(np.float32)
+    return out
+
+
+def set_camera(be, sc):
+    be.set_camera(sc.cameraPosition, sc.cameraDirection, sc.cameraRight, sc.cameraUp)
+
+
+def rendered(sc, n=4, first=0, **kw):
+    be = context(sc, **kw)
+    try:
+        be.render(first, n)
+        return state(be, variance=kw.get("super_sampling", False))
+    finally:
+        be.release()
+
+
+# ---------------------------------------------------------------------------------------------- camera
+
+@pytest.mark.parametrize("sampler", [S.JITTERED, S.UNIFORM], ids=["jittered", "uniform"])
+@pytest.mark.parametrize("flags", [0, DA], ids=["strict", "default"])
+@pytest.mark.parametrize("name", ["cornell", "matmix"])
+def test_set_camera_equals_a_fresh_upload(name, flags, sampler):
+    sc = scene(name)
+    cam = moved_camera(sc)
+    be = context(sc, flags=flags, sampler=sampler)
+    try:
+        be.render(0, 2)
+        set_camera(be, cam)
+        be.clear()
+        be.render(0, 4)
+        got = state(be)
+    finally:
+        be.release()
+    want = rendered(cam, flags=flags, sampler=sampler)
+    assert_same(got, want)
+    assert not np.array_equal(want["color"], rendered(sc, flags=flags, sampler=sampler)["color"])  # (the camera did move)
+
+
+@pytest.mark.parametrize("kw", [dict(flags=backend.FLAG_MEGAKERNEL), dict(super_sampling=True)], ids=["megakernel", "super_sampling"])
+def test_set_camera_with_the_other_kernel_and_with_adaptive_sampling(kw):
+    sc = scene("cornell")
+    cam = moved_camera(sc)
+    be = context(sc, **kw)
+    try:
+        be.render(0, 2)
+        set_camera(be, cam)
+        be.clear()
+        be.render(0, 6)
+        got = state(be, variance="super_sampling" in kw)
+    finally:
+        be.release()
+    assert_same(got, rendered(cam, n=6, **kw))
+
+
+# ---------------------------------------------------------------------------------------------- triangles
+
+def moved_triangles(name, seed=7):
+    sc = scene(name)
+    tris = U.displaced(sc.triangulation, seed, amplitude=0.01 if name == "tris20k" else 0.02)
+    if name == "textured":
+        rs = np.random.default_rng(seed)
+        for field in ("UVP1", "UVP2", "UVP3", "UVN1", "UVN2", "UVN3"):
+            tris[field] = (tris[field] + rs.uniform(-0.3, 0.3, tris[field].shape)).astype(np.float32)
+        for field in ("N1", "N2", "N3"):
+            v = tris[field].copy()
+            v[:, :3] += rs.uniform(-0.2, 0.2, (len(v), 3)).astype(np.float32)
+            v[:, :3] /= np.linalg.norm(v[:, :3], axis=1, keepdims=True).astype(np.float32)
+            tris[field] = v
+    return sc, tris
+
+
+UPDATE_CASES = {
+    "cornell-strict": ("cornell", 0, 4, False),
+    "cornell-default": ("cornell", DA, 4, False),
+    "tris20k-precomputed": ("tris20k", 0, 5, False),
+    "tris20k-precomputed-default": ("tris20k", DA, 5, False),
+    "tris20k-generic": ("tris20k", 0, 5, True),
+    "textured": ("textured", 0, 4, False),
+    "textured-default": ("textured", DA, 4, False),
+    "big_leaf": ("big_leaf", 0, 4, False),
+    "empty_leaves": ("empty_leaves", 0, 4, False),
+}
+
+
+@pytest.mark.parametrize("case", list(UPDATE_CASES))
+def test_update_triangles_equals_a_fresh_upload_of_the_refit_tree(case, monkeypatch):
+    name, flags, depth, generic = UPDATE_CASES[case]
+    if generic:
+        monkeypatch.setenv("PTMI_GENERIC_TRIANGLES", "1")
+    sc, tris = moved_triangles(name)
+    be = context(sc, depth=depth, flags=flags)
+    try:
+        be.render(0, 2)
+        info = be.update_triangles(tris)
+        be.clear()
+        be.render(0, 4)
+        got = state(be)
+    finally:
+        be.release()
+    want = rendered(U.moved_scene(sc, tris), depth=depth, flags=flags)
+    assert_same(got, want)
+    assert info["struct_size"] == 40 and info["levels"] == sc.bvhMaxDepth and info["total_ms"] > 0
+    if name == "tris20k":
+        assert 12 <= info["levels"] <= 20
+    assert not np.array_equal(want["color"], rendered(sc, depth=depth, flags=flags)["color"])  # (the triangles did move)
+
+
+def test_two_successive_updates_reuse_the_schedule():
+    sc, tris1 = moved_triangles("tris20k", seed=1)
+    tris2 = U.displaced(tris1, seed=2, amplitude=0.01)
+    be = context(sc, depth=5)
+    try:
+        first = be.update_triangles(tris1)
+        second = be.update_triangles(tris2)
+        be.render(0, 4)
+        got = state(be)
+    finally:
+        be.release()
+    assert first["levels"] == second["levels"] > 0
+    once = U.moved_scene(sc, tris1)
+    assert_same(got, rendered(U.moved_scene(once, tris2), depth=5))
+
+
+def test_update_with_unchanged_triangles_changes_nothing():
+    sc = scene("cornell")
+    be = context(sc)
+    try:
+        be.update_triangles(sc.triangulation)
+        be.render(0, 4)
+        got = state(be)
+    finally:
+        be.release()
+    assert_same(got, rendered(sc))
+
+
+def test_an_update_keeps_what_has_been_rendered():
+    """4 iterations, update, 4 more WITHOUT a clear: accumulation over the motion."""
+    sc, tris = moved_triangles("cornell")
+    be = context(sc)
+    try:
+        be.render(0, 4)
+        before = state(be)
+        be.update_triangles(tris)
+        assert_same(state(be), before)  # the update itself touched nothing that was rendered
+        be.render(4, 4)
+        got = state(be)
+    finally:
+        be.release()
+    yard = context(U.moved_scene(sc, tris))
+    try:
+        yard.write_image(before["color"].view(np.float32), before["count"])
+        yard.render(4, 4)
+        want = state(yard)
+    finally:
+        yard.release()
+    assert np.array_equal(got["color"], want["color"]) and np.array_equal(got["count"], want["count"])
+    assert got["counters"] == {k: before["counters"][k] + want["counters"][k] for k in want["counters"]}
+    for g, b, w in zip(got["stats"], before["stats"], want["stats"]):
+        assert np.array_equal(g, b + w)
+
+
+def test_set_camera_under_render_ahead(monkeypatch):
+    """The blocking one-iteration-per-call caller that is rendered ahead of: what ran ahead for the old camera is dropped."""
+    sc = scene("cornell")
+    cam = moved_camera(sc)
+
+    def play(ahead):
+        monkeypatch.setenv("PTMI_RENDER_AHEAD", str(ahead))
+        be = context(sc)
+        try:
+            for k in range(6):
+                be.render(k, 1)
+                be.synchronize()
+            set_camera(be, cam)
+            for k in range(6, 12):
+                be.render(k, 1)
+                be.synchronize()
+            return state(be)
+        finally:
+            be.release()
+
+    assert_same(play(2), play(0))
+
+
+def test_update_triangles_under_render_ahead(monkeypatch):
+    sc, tris = moved_triangles("cornell")
+
+    def play(ahead):
+        monkeypatch.setenv("PTMI_RENDER_AHEAD", str(ahead))
+        be = context(sc)
+        try:
+            for k in range(6):
+                be.render(k, 1)
+                be.synchronize()
+            be.update_triangles(tris)
+            for k in range(6, 12):
+                be.render(k, 1)
+                be.synchronize()
+            return state(be)
+        finally:
+            be.release()
+
+    assert_same(play(2), play(0))
+
+
+def test_two_listed_devices():
+    sc, tris = moved_triangles("cornell")
+    cam = moved_camera(sc)
+    be = context(sc, devices=[0, 0])
+    try:
+        be.render(0, 3)
+        set_camera(be, cam)
+        be.clear()
+        be.render(0, 5)
+        got_camera = state(be)
+        be.update_triangles(tris)
+        be.clear()
+        be.render(0, 5)
+        got_both = state(be)
+    finally:
+        be.release()
+    assert_same(got_camera, rendered(cam, n=5, devices=[0, 0]))
+    assert_same(got_both, rendered(U.moved_scene(cam, tris), n=5, devices=[0, 0]))
+
+
+# ---------------------------------------------------------------------------------------------- refusals
+
+def _bad_triangles(sc, kind):
+    t = U.raw_copy(sc.triangulation)
+    if kind == "zero_area":
+        t["S3"][5] = t["S2"][5]
+        U.recompute_aabb(t)
+    elif kind == "nan_vertex":
+        t["S1"][2] = [np.nan, 0, 0, 1]
+    elif kind == "unequal_w":
+        t["S2"][7] = t["S2"][7] * np.float32([1, 1, 1, 2])
+    elif kind == "empty_aabb":
+        box = t["AABB"].copy()
+        box["isEmpty"][1] = 1
+        t["AABB"] = box
+    elif kind == "wrong_count":
+        t = t[:-1]
+    return t
+
+
+def test_refused_updates_leave_the_old_scene_rendering():
+    sc = scene("cornell")
+    be = context(sc)
+    try:
+        be.render(0, 3)
+        baseline = state(be)
+
+        def refused(call, code):
+            with pytest.raises(PtmiError) as e:
+                call()
+            assert e.value.code == code, str(e.value)
+            assert len(str(e.value).split(": ", 1)[1]) > 0
+            be.clear()
+            be.render(0, 3)
+            assert_same(state(be), baseline)
+
+        for kind, code in (("zero_area", UNSUPPORTED), ("nan_vertex", UNSUPPORTED), ("unequal_w", UNSUPPORTED), ("empty_aabb", UNSUPPORTED),
+                           ("wrong_count", INVALID_ARGUMENT)):
+            refused(lambda: be.update_triangles(_bad_triangles(sc, kind)), code)
+        bad = moved_camera(sc)
+        bad.cameraPosition = np.float32([np.inf, 0, 0, 1])
+        refused(lambda: set_camera(be, bad), UNSUPPORTED)
+        bad = moved_camera(sc)
+        bad.cameraUp = np.float32([0, np.nan, 0, 0])
+        refused(lambda: set_camera(be, bad), UNSUPPORTED)
+        # ... and a good update still works after the refused ones
+        _, tris = moved_triangles("cornell")
+        be.update_triangles(tris)
+        be.clear()
+        be.render(0, 3)
+        assert_same(state(be), rendered(U.moved_scene(sc, tris), n=3))
+    finally:
+        be.release()
+
+
+def test_update_before_initialize_memory_is_a_state_error():
+    sc = scene("cornell")
+    be = Backend().setup_context(W, H, 4, sc.lightsSize)
+    try:
+        for call in (lambda: be.update_triangles(sc.triangulation), lambda: set_camera(be, sc)):
+            with pytest.raises(PtmiError) as e:
+                call()
+            assert e.value.code == STATE and "before ptmi_initialize_memory" in str(e.value)
+    finally:
+        be.release()
