@@ -15,7 +15,8 @@ OBJDIR     := $(LIBDIR)/obj
 # reference's default OpenCL arithmetic (PTMI_FLAG_DEFAULT_ARITHMETIC).  Object files: `make -j` builds them side by side.
 LIB_OBJS   := $(OBJDIR)/kernels.o $(OBJDIR)/kernel_wavefront.o $(OBJDIR)/kernels_da.o $(OBJDIR)/kernel_wavefront_da.o \
               $(OBJDIR)/display.o $(OBJDIR)/ptmi_api.o $(OBJDIR)/scene_layout.o $(OBJDIR)/bvh_build.o \
-              $(OBJDIR)/bvh_build_device.o $(OBJDIR)/scene_refit.o $(OBJDIR)/scene_refit_host.o
+              $(OBJDIR)/bvh_build_device.o $(OBJDIR)/scene_refit.o $(OBJDIR)/scene_refit_host.o \
+              $(OBJDIR)/ray_query.o $(OBJDIR)/ray_query_da.o
 
 .PHONY: all lib shim oracle ref clean resources
 all: lib shim oracle
@@ -53,4 +54,4 @@ clean:
 
 # register / LDS budget of both kernels (occupancy is VGPR-bound: read this after every kernel edit)
 resources:
-	@for f in kernels kernel_wavefront; do for m in 0 1; do $(HIPCC) $(HIPFLAGS) -DPTMI_DEFAULT_ARITHMETIC=$$m --cuda-device-only -c $(CSRC)/$$f.hip -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs:|ScratchSize|Occupancy|LDS Size|Spill" | sed 's/.*remark: *//' | tr '\n' ' '; echo; done; done
+	@for f in kernels kernel_wavefront ray_query; do for m in 0 1; do $(HIPCC) $(HIPFLAGS) -DPTMI_DEFAULT_ARITHMETIC=$$m --cuda-device-only -c $(CSRC)/$$f.hip -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs:|ScratchSize|Occupancy|LDS Size|Spill" | sed 's/.*remark: *//' | tr '\n' ' '; echo; done; done

@@ -296,6 +296,50 @@ typedef struct ptmi_update_info {
 
 int ptmi_update_triangles(ptmi_ctx* ctx, const ptmi_triangle* triangulation, uint32_t triangulation_size, ptmi_update_info* info);
 
+/* ---- single rays against the loaded scene --------------------------------- */
+
+/* Rays of the caller's own, traced against the geometry the context holds NOW (after any ptmi_update_triangles): viewport
+ * picking, line-of-sight and occlusion probes, collision rays, and a probe of traversal cost that renders no image.  One query
+ * is the reference's BVH_IntersectRay (PTMI_QUERY_CLOSEST) or BVH_IntersectShadowRay (PTMI_QUERY_ANY) (FullKernel.cl:620-783)
+ * on a ray made by Ray3D_Create, bit for bit in the context's arithmetic: the same visit order, the same 1e-5 thresholds, the
+ * same quirks (the box test compares a linear distance with the squared limit, cl:135; a NaN distance is accepted and from then
+ * on the last triangle that passes wins - a scene with a ptmi_literal_kernel_reason is served too).  Ray contents are not
+ * validated: a ray that is not finite gets what the reference's loops would give it, and no ray can make the kernel leave the
+ * tree that was validated at upload.  Where a field of a hit is a NaN, its sign and payload mean nothing: IEEE 754 leaves them
+ * open, and so does the reference.
+ * A QUERY TOUCHES NOTHING THAT HAS BEEN RENDERED: accumulators, histograms, ptmi_counters, scheduler statistics and snapshots
+ * stay as they are, and launches rendered ahead are neither dropped nor waited for.  Both calls run on devices[0] of a
+ * multi-device context (every device holds the same scene).  PTMI_ERR_STATE before ptmi_initialize_memory;
+ * PTMI_ERR_INVALID_ARGUMENT for an unknown kind, a NULL pointer with n_rays > 0 or a device pointer that is not 16-byte
+ * aligned; n_rays == 0 is PTMI_OK and launches nothing. */
+typedef struct ptmi_ray {            /* 48 bytes */
+    ptmi_float4 origin;              /* all four components enter the arithmetic, as in the reference (dot() is 4-wide); w = 0 is the usual choice */
+    ptmi_float4 direction;           /* normalised by the library exactly as Ray3D_Create / Ray3D_SetDirection does (header.cl:276-284) */
+    float max_squared_distance;      /* initial distance limit (the reference's squaredDistance); INFINITY = unlimited */
+    uint32_t reserved[3];            /* 0 */
+} ptmi_ray;
+
+typedef struct ptmi_ray_hit {        /* 48 bytes */
+    ptmi_float4 point;               /* intersectionPoint */
+    float squared_distance, s, t;    /* as Triangle_Intersects leaves them */
+    uint32_t triangle_id;            /* index into the triangulation[] given to ptmi_initialize_memory (the convention of ptmi_update_triangles); 0xFFFFFFFF = miss */
+    uint32_t front;                  /* 1: dot(N, dir) < 0, the side materialWithPositiveNormalIndex shades */
+    uint32_t box_tests, triangle_tests; /* numIntersectedBBx / numIntersectedTri of this one query */
+    uint32_t reserved;
+} ptmi_ray_hit;                      /* a miss: triangle_id 0xFFFFFFFF, front 0, point / squared_distance / s / t +0; both counts are still filled */
+
+enum { PTMI_QUERY_CLOSEST = 0,  /* BVH_IntersectRay */
+       PTMI_QUERY_ANY = 1 };    /* BVH_IntersectShadowRay: stops at the first accepted triangle, which is the one reported */
+
+/* Host arrays: the rays go up into a scratch buffer of the context (allocated by the first query, grown on demand, freed by
+ * ptmi_release: a context that never queries pays nothing), the kernel runs, the hits come down, and the call returns with
+ * them in place - straight into `hits` where the caller has page-locked it (ptmi_pin_host_buffer). */
+int ptmi_query_rays(ptmi_ctx* ctx, uint32_t kind, const ptmi_ray* rays, uint32_t n_rays, ptmi_ray_hit* hits);
+/* Device pointers (e.g. torch tensors), 16-byte aligned: asynchronous on the context's stream (ptmi_set_stream's, where one
+ * was given).  ptmi_update_triangles, ptmi_set_camera and ptmi_initialize_memory wait for a pending query before they
+ * rewrite the scene; the caller orders its own reads of d_hits behind the stream (or calls ptmi_synchronize). */
+int ptmi_query_rays_device(ptmi_ctx* ctx, uint32_t kind, const void* d_rays, uint32_t n_rays, void* d_hits);
+
 /* ---- measurement / plumbing -------------------------------------------- */
 
 int ptmi_get_counters(ptmi_ctx* ctx, ptmi_counters* out);

@@ -124,7 +124,10 @@ ABI_SYMBOLS = ["ptmi_setup_context", "ptmi_initialize_memory", "ptmi_render", "p
                "ptmi_set_stream", "ptmi_device_accumulators", "ptmi_bind_accumulators", "ptmi_read_variance",
                "ptmi_device_variance", "ptmi_last_error",
                "ptmi_abi_version", "ptmi_device_count", "ptmi_device_share", "ptmi_bvh_create",
-               "ptmi_bvh_create_device", "ptmi_set_camera", "ptmi_update_triangles", "ptmi_bvh_refit"]
+               "ptmi_bvh_create_device", "ptmi_set_camera", "ptmi_update_triangles", "ptmi_bvh_refit",
+               "ptmi_query_rays", "ptmi_query_rays_device"]
+
+QUERY_CLOSEST, QUERY_ANY = 0, 1  # ptmi.h: PTMI_QUERY_*
 
 
 def library_path():
@@ -177,6 +180,8 @@ def load_library():
     lib.ptmi_set_camera.argtypes = [vp, C.POINTER(Float4), C.POINTER(Float4), C.POINTER(Float4), C.POINTER(Float4)]
     lib.ptmi_update_triangles.argtypes = [vp, vp, u32, C.POINTER(UpdateInfo)]
     lib.ptmi_bvh_refit.argtypes = [vp, u32, vp, u32]
+    lib.ptmi_query_rays.argtypes = [vp, u32, vp, u32, vp]
+    lib.ptmi_query_rays_device.argtypes = [vp, u32, vp, u32, vp]
     lib.ptmi_device_share.argtypes = [u32, u32, u32, u32, C.POINTER(u32), C.POINTER(u32)]
     lib.ptmi_device_share.restype = None
     _lib = lib
@@ -190,6 +195,19 @@ def _ptr(a):
 def _f4(v):
     v = np.asarray(v, np.float32)
     return Float4(float(v[0]), float(v[1]), float(v[2]), float(v[3]))
+
+
+def make_rays(origins, directions, max_squared_distance=None):
+    """A ``structs.RAY`` array from float32 (n,3) / (n,4) origins and directions (w = 0 for (n,3)) and a scalar or n distance
+    limits (None: INFINITY)."""
+    o, d = np.asarray(origins, np.float32), np.asarray(directions, np.float32)
+    if o.ndim != 2 or d.ndim != 2 or o.shape[0] != d.shape[0] or o.shape[1] not in (3, 4) or d.shape[1] not in (3, 4):
+        raise PtmiError(-1, "origins and directions must be (n,3) or (n,4) arrays of the same length")
+    rays = np.zeros(len(o), S.RAY)
+    rays["origin"][:, :o.shape[1]] = o
+    rays["direction"][:, :d.shape[1]] = d
+    rays["max_squared_distance"] = np.inf if max_squared_distance is None else np.asarray(max_squared_distance, np.float32)
+    return rays
 
 
 def device_share(first_iteration, n_iterations, k, n_devices):
@@ -334,6 +352,27 @@ class Backend:
         info = UpdateInfo()
         self._check(self._lib.ptmi_update_triangles(self._ctx, tris.ctypes.data_as(C.c_void_p), len(tris), C.byref(info)))
         return info.as_dict()
+
+    # -- rays of the caller's own against the loaded scene (no counterpart in the reference) --
+    def query_rays(self, origins, directions, max_squared_distance=None, any_hit=False, out=None):
+        """``BVH_IntersectRay`` (or, ``any_hit``, ``BVH_IntersectShadowRay``) for n rays of the caller's: ``origins`` and
+        ``directions`` are float32 (n,3) or (n,4) arrays (w = 0 for (n,3)), ``max_squared_distance`` a scalar or n values
+        (None: unlimited).  Returns a ``structs.RAY_HIT`` array (``out``: fill this one, e.g. a page-locked array);
+        ``triangle_id`` indexes the triangulation the context was given, ``structs.RAY_MISS`` = no hit.  Touches nothing that
+        has been rendered."""
+        rays = make_rays(origins, directions, max_squared_distance)
+        hits = np.zeros(len(rays), S.RAY_HIT) if out is None else out
+        if hits.dtype != S.RAY_HIT or len(hits) != len(rays) or not hits.flags.c_contiguous:
+            raise PtmiError(-1, "out must be a contiguous structs.RAY_HIT array with one record per ray")
+        self._check(self._lib.ptmi_query_rays(self._ctx, QUERY_ANY if any_hit else QUERY_CLOSEST, rays.ctypes.data_as(C.c_void_p),
+                                              len(rays), hits.ctypes.data_as(C.c_void_p)))
+        return hits
+
+    def query_rays_device(self, d_rays, n, d_hits, any_hit=False):
+        """The same for ``n`` 48-byte ``structs.RAY`` records at device address ``d_rays`` (e.g. ``tensor.data_ptr()``), hits to
+        ``d_hits``: asynchronous on the context's stream."""
+        self._check(self._lib.ptmi_query_rays_device(self._ctx, QUERY_ANY if any_hit else QUERY_CLOSEST, C.c_void_p(d_rays), n,
+                                                     C.c_void_p(d_hits)))
 
     # -- one launch of the loop body of OpenCL_RunKernel, generalised to a range ----------
     def render(self, first_iteration, n_iterations):

@@ -128,6 +128,11 @@ struct ptmi_ctx {
     float* h_staging = nullptr;  // pinned, 5*W*H floats
     struct HostRange { char* p; size_t bytes; };
     std::vector<HostRange> pinned_host;  // caller buffers page-locked by ptmi_pin_host_buffer: readbacks DMA straight into them
+    // ptmi_query_rays (host arrays), on devices[0]: room for query_cap rays and as many hits behind them, and a pinned landing
+    // place for the hits of a destination that is not page-locked; allocated by the first query, grown on demand, freed at release
+    char* d_query = nullptr;
+    char* h_query = nullptr;
+    size_t query_cap = 0;
 
     size_t npix() const { return (size_t)cfg.image_width * cfg.image_height; }
     uint32_t n_dev() const { return (uint32_t)dev.size(); }
@@ -1520,10 +1525,80 @@ int ptmi_update_triangles(ptmi_ctx* ctx, const ptmi_triangle* triangulation, uin
     return PTMI_OK;
 }
 
+// ---- rays of the caller's own (ray_query.hip) ------------------------------------------------------------------------------
+// Both entry points launch on devices[0]'s MAIN stream and touch nothing but the two ray buffers: the launch streams, the stage
+// sets, the schedule and the counters are left alone, so whatever was rendered - or rendered ahead - stays what it was.  The
+// calls that rewrite scene records wait for that stream first (quiesce, free_scene_memory; ptmi_set_stream waits for the
+// stream it leaves), which covers a device-pointer query still in flight.
+static int query_check(ptmi_ctx* ctx, const char* who, uint32_t kind, const void* rays, uint32_t n_rays, const void* hits)
+{
+    if (!ctx->have_scene) return fail(ctx, PTMI_ERR_STATE, std::string(who) + " before ptmi_initialize_memory");
+    if (kind != PTMI_QUERY_CLOSEST && kind != PTMI_QUERY_ANY) return fail(ctx, PTMI_ERR_INVALID_ARGUMENT, std::string(who) + ": unknown kind " + std::to_string(kind));
+    if (n_rays && (!rays || !hits)) return fail(ctx, PTMI_ERR_INVALID_ARGUMENT, std::string(who) + ": rays or hits is NULL");
+    return PTMI_OK;
+}
+
+int ptmi_query_rays_device(ptmi_ctx* ctx, uint32_t kind, const void* d_rays, uint32_t n_rays, void* d_hits)
+{
+    if (!ctx) return PTMI_ERR_INVALID_ARGUMENT;
+    if (int rc = query_check(ctx, "ptmi_query_rays_device", kind, d_rays, n_rays, d_hits)) return rc;
+    if (n_rays == 0) return PTMI_OK;
+    if (((uintptr_t)d_rays | (uintptr_t)d_hits) & 15u)
+        return fail(ctx, PTMI_ERR_INVALID_ARGUMENT, "ptmi_query_rays_device: the device pointers must be 16-byte aligned");
+    DeviceState& d = ctx->dev[0];
+    ON_DEVICE(ctx, d);
+    std::string err;
+    if (int rc = KERNELS_OF(ctx, launch_query_rays)(d.ds, kind == PTMI_QUERY_ANY, d_rays, d_hits, n_rays, ctx->stack_levels, d.stream, &err))
+        return fail(ctx, rc, err);
+    return PTMI_OK;
+}
+
+int ptmi_query_rays(ptmi_ctx* ctx, uint32_t kind, const ptmi_ray* rays, uint32_t n_rays, ptmi_ray_hit* hits)
+{
+    if (!ctx) return PTMI_ERR_INVALID_ARGUMENT;
+    if (int rc = query_check(ctx, "ptmi_query_rays", kind, rays, n_rays, hits)) return rc;
+    if (n_rays == 0) return PTMI_OK;
+    static_assert(sizeof(ptmi_ray) == 48 && sizeof(ptmi_ray_hit) == 48, "ray_query.hip moves both as three 16-byte quads");
+    DeviceState& d = ctx->dev[0];
+    ON_DEVICE(ctx, d);
+    const size_t bytes = (size_t)n_rays * sizeof(ptmi_ray);
+    const bool pinned = host_is_pinned(ctx, hits, bytes);
+    if (n_rays > ctx->query_cap) {
+        // (every earlier host-array query has returned, so nothing is in flight on the buffers that go)
+        if (ctx->d_query) (void)hipFree(ctx->d_query);
+        if (ctx->h_query) (void)hipHostFree(ctx->h_query);
+        ctx->d_query = ctx->h_query = nullptr;
+        ctx->query_cap = 0;
+        const size_t cap = std::max<size_t>(n_rays, 1024);
+        void* p = nullptr;
+        HIP_TRY(ctx, hipMalloc(&p, 2 * cap * sizeof(ptmi_ray)));
+        ctx->d_query = (char*)p;
+        ctx->query_cap = cap;
+    }
+    if (!pinned && !ctx->h_query) {
+        void* p = nullptr;
+        HIP_TRY(ctx, hipHostMalloc(&p, ctx->query_cap * sizeof(ptmi_ray_hit), hipHostMallocDefault));
+        ctx->h_query = (char*)p;
+    }
+    char* const d_rays = ctx->d_query;
+    char* const d_hits = ctx->d_query + ctx->query_cap * sizeof(ptmi_ray);
+    HIP_TRY(ctx, hipMemcpyAsync(d_rays, rays, bytes, hipMemcpyHostToDevice, d.stream));
+    std::string err;
+    if (int rc = KERNELS_OF(ctx, launch_query_rays)(d.ds, kind == PTMI_QUERY_ANY, d_rays, d_hits, n_rays, ctx->stack_levels, d.stream, &err))
+        return fail(ctx, rc, err);
+    HIP_TRY(ctx, hipMemcpyAsync(pinned ? (void*)hits : (void*)ctx->h_query, d_hits, bytes, hipMemcpyDeviceToHost, d.stream));
+    HIP_TRY(ctx, hipStreamSynchronize(d.stream));
+    if (!pinned) std::memcpy(hits, ctx->h_query, bytes);
+    return PTMI_OK;
+}
+
 void ptmi_release(ptmi_ctx* ctx)
 {
     if (!ctx) return;
     free_scene_memory(ctx);
+    if (!ctx->dev.empty()) (void)hipSetDevice(ctx->dev[0].device);
+    if (ctx->d_query) (void)hipFree(ctx->d_query);
+    if (ctx->h_query) (void)hipHostFree(ctx->h_query);
     for (void* comm : ctx->rccl_comms)
         if (comm) (void)rccl_api().CommDestroy(comm);
     ctx->rccl_comms.clear();

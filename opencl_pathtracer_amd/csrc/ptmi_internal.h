@@ -202,6 +202,14 @@ PTMI_DECLARE_INTEGRATOR_ENTRY_POINTS(_da)
 // the device after the upload.  `tri_ids[i]` == 0xFFFFFFFF marks a node record.
 int launch_precompute_denominators_da(DTri* records, const uint32_t* tri_ids, uint32_t n_records, void* stream, std::string* err);
 
+// ray_query.hip (compiled once per arithmetic mode, like the integrator): n_rays ptmi_ray records at d_rays -> as many
+// ptmi_ray_hit records at d_hits, closest hit or (any_hit) first accepted triangle.  stack_levels as for the wavefront kernel:
+// the depth of the uploaded tree, which sizes the LDS stack.  Reads the scene's records only.
+int launch_query_rays(const DScene& sc, bool any_hit, const void* d_rays, void* d_hits, uint32_t n_rays, uint32_t stack_levels,
+                      void* stream, std::string* err);
+int launch_query_rays_da(const DScene& sc, bool any_hit, const void* d_rays, void* d_hits, uint32_t n_rays, uint32_t stack_levels,
+                         void* stream, std::string* err);
+
 // display.hip: accumulators -> padded B,G,R scanlines (the reference's ConvertRGBAToBMPBuffer), on the device
 int launch_display_bgr(const float* image_color, const float* image_ray_nb, uint8_t* out, uint32_t width, uint32_t height,
                        uint32_t row_stride, void* stream, std::string* err);

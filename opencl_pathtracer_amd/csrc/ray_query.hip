@@ -1,0 +1,166 @@
+// ray_query.hip - rays the CALLER supplies, traced against the scene a context holds (ptmi_query_rays, ptmi.h).
+//
+// One query = the reference's BVH_IntersectRay (FullKernel.cl:620-702, PTMI_QUERY_CLOSEST) or BVH_IntersectShadowRay
+// (:705-783, PTMI_QUERY_ANY) on a ray made by Ray3D_Create (header.cl:276-295), bit for bit in the arithmetic of the build
+// (ptmi_device.hpp).  The loop below is `traverse` of ptmi_literal_path.hpp - same visit order, same comparisons - with three
+// differences that no result can show:
+//   * the LDS traversal stack is sized at launch by the depth of the uploaded tree, not by PTMI_BVH_MAX_DEPTH;
+//   * a ray whose slabs are ordered takes the 5-comparison box test (box_hit_ordered), chosen once per ray;
+//   * the any-hit form reports the record it accepted.
+// The kernel only READS scene memory: no accumulator, histogram or counter of the context is touched.
+#include <hip/hip_runtime.h>
+
+#include <cstdlib>
+
+#include "ptmi_literal_path.hpp"
+
+namespace PTMI_DEV_NS {
+
+constexpr int kQueryBlock = 256;  // 4 waves; a lane keeps one ray and one column of the stack
+
+struct QueryCounts {
+    uint32_t bbx, tri;
+};
+
+// `stack`: the lane's column of the [level][lane] array, kQueryBlock words from one level to the next.
+// Returns whether a triangle was accepted; hit.tri = its RECORD index, `limit` = the squared distance it left.
+template <bool ANY_HIT, bool PRE, bool ORDERED>
+__device__ __forceinline__ bool query_walk(const DScene& sc, const Ray& r, float& limit, Hit& hit, QueryCounts& pc,
+                                           uint32_t* __restrict__ stack)
+{
+    bool found = false;
+    int top = 0;
+    uint32_t cur = sc.root_ref;
+    for (;;) {
+        if (cur & REF_LEAF) {
+            uint32_t count = (cur >> REF_COUNT_SHIFT) & 7u;
+            uint32_t start = cur & REF_INDEX_MASK_LEAF;
+            if (count == REF_COUNT_BIG) {
+                const DBigLeaf bl = sc.big_leaves[start];
+                start = bl.start;
+                count = bl.count;
+            }
+            for (uint32_t i = start; i < start + count; i++) {
+                pc.tri++;
+                const float4* q4 = reinterpret_cast<const float4*>(&sc.tris[i]);
+                if (tri_hit_record<PRE>(q4[0], q4[1], q4[2], q4[3], r, limit, hit)) {
+                    hit.tri = i;
+                    if (ANY_HIT) return true;
+                    found = true;
+                }
+            }
+            if (top == 0) break;
+            cur = stack[(--top) * kQueryBlock];
+        } else {
+            const float4* np = reinterpret_cast<const float4*>(&sc.nodes[cur & REF_INDEX_MASK_INNER]);
+            const float4 a = np[0], b = np[1], c = np[2], d = np[3];
+            const float lo1[3] = {a.x, a.y, a.z}, hi1[3] = {a.w, b.x, b.y};
+            const float lo2[3] = {b.z, b.w, c.x}, hi2[3] = {c.y, c.z, c.w};
+            const uint32_t ref1 = __float_as_uint(d.x), ref2 = __float_as_uint(d.y), axis = __float_as_uint(d.z);
+            const float da = axis == 0 ? r.d.x : (axis == 1 ? r.d.y : r.d.z);
+            const bool fwd = da > 0;
+            const bool h1 = ORDERED ? box_hit_ordered(lo1, hi1, r, limit) : box_hit(lo1, hi1, (ref1 & REF_EMPTY) != 0, r, limit);
+            const bool h2 = ORDERED ? box_hit_ordered(lo2, hi2, r, limit) : box_hit(lo2, hi2, (ref2 & REF_EMPTY) != 0, r, limit);
+            pc.bbx += 2;
+            const uint32_t near_ref = fwd ? ref1 : ref2, far_ref = fwd ? ref2 : ref1;
+            const bool near_hit = fwd ? h1 : h2, far_hit = fwd ? h2 : h1;
+            if (near_hit) {
+                if (far_hit) stack[(top++) * kQueryBlock] = far_ref;
+                cur = near_ref;
+            } else if (far_hit) {
+                cur = far_ref;
+            } else {
+                if (top == 0) break;
+                cur = stack[(--top) * kQueryBlock];
+            }
+        }
+    }
+    return found;
+}
+
+// rays: 3 x 16 bytes each (ptmi_ray), hits: 3 x 16 bytes each (ptmi_ray_hit)
+template <bool ANY_HIT, bool PRE>
+__global__ void __launch_bounds__(kQueryBlock) query_rays_kernel(const DScene sc, const float4* __restrict__ rays,
+                                                                 float4* __restrict__ hits, const uint32_t n_rays)
+{
+    extern __shared__ uint32_t query_stack[];  // [stack_levels][kQueryBlock]
+    uint32_t* const stack = &query_stack[threadIdx.x];
+
+    for (uint32_t i = blockIdx.x * kQueryBlock + threadIdx.x; i < n_rays; i += gridDim.x * kQueryBlock) {
+        const float4 in_o = rays[3 * (size_t)i], in_d = rays[3 * (size_t)i + 1], in_l = rays[3 * (size_t)i + 2];
+        Ray r;
+        r.o = v4(in_o);
+        ray_set_direction(r, v4(in_d));
+        float limit = in_l.x;
+        Hit hit;
+        hit.tri = 0; hit.s = 0; hit.t = 0; hit.front = false; hit.point = v4(0, 0, 0, 0);
+        QueryCounts pc{0, 0};
+        bool found;
+        if (!ANY_HIT && sc.nan_walk_box_tests != 0xFFFFFFFFu && (r.d.x != r.d.x) & (r.d.y != r.d.y) & (r.d.z != r.d.z)) {
+            // the closest-hit walk of an all-NaN direction visits the whole tree and keeps its last triangle: `traverse` and
+            // scene_layout.cpp (nan_walk_*) explain; the counts of that walk, and the last triangle's test made for real
+            pc.bbx = sc.nan_walk_box_tests;
+            pc.tri = sc.nan_walk_tri_tests;
+            found = false;
+            if (sc.nan_walk_last_tri != 0xFFFFFFFFu) {
+                const float4* q4 = reinterpret_cast<const float4*>(&sc.tris[sc.nan_walk_last_tri]);
+                found = tri_hit_record<PRE>(q4[0], q4[1], q4[2], q4[3], r, limit, hit);
+                hit.tri = sc.nan_walk_last_tri;
+            }
+        } else if (sc.boxes_ordered && ray_slabs_are_ordered(r) && !(limit < 0)) {
+            // (box_hit_ordered takes the distance limit as never negative: a caller's negative one keeps the literal form)
+            found = query_walk<ANY_HIT, PRE, true>(sc, r, limit, hit, pc, stack);
+        } else {
+            found = query_walk<ANY_HIT, PRE, false>(sc, r, limit, hit, pc, stack);
+        }
+        float4 out_p = make_float4(0, 0, 0, 0), out_q = make_float4(0, 0, 0, __uint_as_float(0xFFFFFFFFu));
+        uint32_t front = 0;
+        if (found) {
+            out_p = make_float4(hit.point.x, hit.point.y, hit.point.z, hit.point.w);
+            out_q = make_float4(limit, hit.s, hit.t, __uint_as_float(sc.tri_ids[hit.tri]));
+            front = hit.front ? 1u : 0u;
+        }
+        hits[3 * (size_t)i] = out_p;
+        hits[3 * (size_t)i + 1] = out_q;
+        hits[3 * (size_t)i + 2] = make_float4(__uint_as_float(front), __uint_as_float(pc.bbx), __uint_as_float(pc.tri), 0.0f);
+    }
+}
+
+}  // namespace PTMI_DEV_NS
+
+namespace ptmi_internal {
+
+int PTMI_ARITH(launch_query_rays)(const DScene& sc, bool any_hit, const void* d_rays, void* d_hits, uint32_t n_rays,
+                                  uint32_t stack_levels, void* stream, std::string* err)
+{
+    using namespace PTMI_DEV_NS;
+    if (n_rays == 0) return PTMI_OK;
+    if (stack_levels < 1 || stack_levels > PTMI_BVH_MAX_DEPTH) {
+        if (err) *err = "query_rays_kernel: " + std::to_string(stack_levels) + " stack levels";
+        return PTMI_ERR_INTERNAL;
+    }
+    const bool pre = sc.tris_precomputed != 0;
+    const auto kernel = any_hit ? (pre ? query_rays_kernel<true, true> : query_rays_kernel<true, false>)
+                                : (pre ? query_rays_kernel<false, true> : query_rays_kernel<false, false>);
+    const size_t lds_bytes = (size_t)stack_levels * kQueryBlock * sizeof(uint32_t);
+    // as many workgroups as the device holds at once - 8 of four waves by wave slots, fewer where 160 KB of LDS hold fewer
+    // stacks - four times over (rays differ in cost); the grid-stride loop takes the rest
+    int device = 0, cus = 0;
+    hipError_t e = hipGetDevice(&device);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+    if (e != hipSuccess) return launch_status(e, "query_rays_kernel", err);
+    const size_t by_lds = (160u * 1024u) / lds_bytes;
+    const int per_cu = (int)(by_lds < 8 ? by_lds : 8);
+    uint64_t blocks = ((uint64_t)n_rays + kQueryBlock - 1) / kQueryBlock;
+    uint64_t cap = 4ull * (uint64_t)(cus > 0 ? cus : 1) * (uint64_t)(per_cu > 0 ? per_cu : 1);
+    if (const char* v = std::getenv("PTMI_QUERY_MAX_BLOCKS")) {  // env: test switch - small batches take the grid-stride loop
+        const long want = std::strtol(v, nullptr, 10);
+        if (want >= 1 && (uint64_t)want < cap) cap = (uint64_t)want;
+    }
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(kQueryBlock), lds_bytes, (hipStream_t)stream, sc,
+                       static_cast<const float4*>(d_rays), static_cast<float4*>(d_hits), n_rays);
+    return launch_status(hipGetLastError(), "query_rays_kernel", err);
+}
+
+}  // namespace ptmi_internal

@@ -66,6 +66,22 @@ Sky = np.dtype({
 
 Uchar4 = np.dtype((np.uint8, 4))
 
+# include/ptmi.h: ptmi_ray / ptmi_ray_hit, what Backend.query_rays sends and gets
+RAY = np.dtype({
+    "names": ["origin", "direction", "max_squared_distance", "reserved"],
+    "formats": [FLOAT4, FLOAT4, np.float32, (np.uint32, 3)],
+    "offsets": [0, 16, 32, 36],
+    "itemsize": 48,
+})
+
+RAY_HIT = np.dtype({
+    "names": ["point", "squared_distance", "s", "t", "triangle_id", "front", "box_tests", "triangle_tests", "reserved"],
+    "formats": [FLOAT4, np.float32, np.float32, np.float32, np.uint32, np.uint32, np.uint32, np.uint32, np.uint32],
+    "offsets": [0, 16, 20, 24, 28, 32, 36, 40, 44],
+    "itemsize": 48,
+})
+RAY_MISS = 0xFFFFFFFF  # RAY_HIT.triangle_id of a ray that hit nothing
+
 # enums (PathTracer_Structs.h:24-30, 43-51, 66-71, 130-135)
 LIGHT_DIRECTIONNAL, LIGHT_POINT, LIGHT_SPOT, LIGHT_UNKNOWN = 0, 1, 2, 3
 MAT_STANDART, MAT_WATER, MAT_GLASS, MAT_VARNHISHED, MAT_METAL, MAT_UNKNOWN = 0, 1, 2, 3, 4, 5
@@ -79,3 +95,4 @@ MAX_LIGHT_SIZE = 30             # PathTracer_PreProc.h:20
 
 assert BoundingBox.itemsize == 64 and Light.itemsize == 64 and Material.itemsize == 48
 assert Node.itemsize == 160 and Texture.itemsize == 12 and Triangle.itemsize == 336 and Sky.itemsize == 92
+assert RAY.itemsize == 48 and RAY_HIT.itemsize == 48
