@@ -14,7 +14,8 @@ OBJDIR     := $(LIBDIR)/obj
 # The integrator's device code is compiled once per arithmetic mode (ptmi_device.hpp): strict, and `_da` = the
 # reference's default OpenCL arithmetic (PTMI_FLAG_DEFAULT_ARITHMETIC).  Object files: `make -j` builds them side by side.
 LIB_OBJS   := $(OBJDIR)/kernels.o $(OBJDIR)/kernel_wavefront.o $(OBJDIR)/kernels_da.o $(OBJDIR)/kernel_wavefront_da.o \
-              $(OBJDIR)/display.o $(OBJDIR)/ptmi_api.o $(OBJDIR)/scene_layout.o $(OBJDIR)/bvh_build.o \
+              $(OBJDIR)/display.o $(OBJDIR)/ptmi_api.o $(OBJDIR)/ptmi_scene_memory.o $(OBJDIR)/ptmi_render.o \
+              $(OBJDIR)/ptmi_readback.o $(OBJDIR)/ptmi_query.o $(OBJDIR)/scene_layout.o $(OBJDIR)/bvh_build.o \
               $(OBJDIR)/bvh_build_device.o $(OBJDIR)/scene_refit.o $(OBJDIR)/scene_refit_host.o \
               $(OBJDIR)/ray_query.o $(OBJDIR)/ray_query_da.o
 

@@ -1,6 +1,6 @@
 // launch_schedule.h - one device's launches for a ptmi_render call: on the main stream, on a stage set (stage_sets.h), adopted
 // from a launch that ran AHEAD of the caller, and the launches to keep in flight for the next calls; render_on_device
-// (ptmi_api.cpp) issues them.  Pure host code without HIP, played on the CPU by tests/launch_schedule_model.cpp.  Not ABI.
+// (ptmi_render.cpp) issues them.  Pure host code without HIP, played on the CPU by tests/launch_schedule_model.cpp.  Not ABI.
 // A short launch touches nothing of the context but its stage set until the main stream ADOPTS it.  So once a caller that waits
 // for each call has been seen to come back for the next ids with the same count, every call leaves up to `ahead_depth` launches
 // for the next calls in flight, each for up to kAheadIterations / n calls.  A call that asks for something else

@@ -1,5 +1,5 @@
 // scene_layout.h - validation and re-layout of a scene for the device: host code without a device call (scene_layout.cpp).
-// Used by ptmi_initialize_memory (ptmi_api.cpp) and, on its own, by ptmi_validate_scene - which is also how the tests run it
+// Used by ptmi_initialize_memory (ptmi_scene_memory.cpp) and, on its own, by ptmi_validate_scene - which is also how the tests run it
 // under AddressSanitizer on a box without a GPU.
 #pragma once
 

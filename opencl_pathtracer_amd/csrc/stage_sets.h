@@ -1,4 +1,4 @@
-// stage_sets.h - how large the staging arrays of one ptmi_render call must be (render_on_device, ptmi_api.cpp).
+// stage_sets.h - how large the staging arrays of one ptmi_render call must be (render_on_device, ptmi_render.cpp).
 // Pure host code without HIP: tests/stage_sets_model.cpp checks it on the CPU.  Not part of the ABI.
 //
 // A device stages the radiance and statistics word of every path of a launch in one of kStageSets STAGE SETS (20 bytes per
