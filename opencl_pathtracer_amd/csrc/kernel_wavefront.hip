@@ -1090,9 +1090,7 @@ __global__ void __launch_bounds__(256) precompute_denominators_kernel(DTri* __re
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_records || tri_ids[i] == 0xFFFFFFFFu) return;
     DTriPre* const p = reinterpret_cast<DTriPre*>(&records[i]);
-    const V4 u = v4(p->u_den[0], p->u_den[1], p->u_den[2], 0.0f), v = v4(p->v_s1w[0], p->v_s1w[1], p->v_s1w[2], 0.0f);
-    const float uv = dot(u, v), uu = dot(u, u), vv = dot(v, v);
-    p->u_den[3] = frcp(mad(uv, uv, -(uu * vv)));
+    p->u_den[3] = pre_record_denominator(*p);
 }
 #endif
 

@@ -251,8 +251,9 @@ __device__ __forceinline__ bool box_hit(const float lo[3], const float hi[3], bo
 }
 
 // The same decision in 5 compare/select instructions per box instead of 16, valid when nothing in it can be a NaN
-// and the box is ordered: box coordinates finite with lo <= hi (checked at upload), ray origin not NaN and the three
-// reciprocals finite (checked per ray, `ray_slabs_are_ordered`).  Then every slab has tmin_a <= tmax_a (rounding is
+// and the box is ordered: box coordinates finite with lo <= hi (checked at upload), ray origin finite and the three
+// reciprocals finite (checked per ray, `ray_slabs_are_ordered`; an infinite origin meets the inverted infinite box of an
+// empty child below as inf - inf).  Then every slab has tmin_a <= tmax_a (rounding is
 // monotonic), so
 //   "both ends negative on some axis"  (FullKernel.cl:85-86,99-100,119-120)  ==  min_a tmax_a < 0
 //   every cross test  tmin_a > tmax_b  (:101-102,121-122)                    ==  max_a tmin_a > min_a tmax_a
@@ -278,7 +279,7 @@ __device__ __forceinline__ bool box_hit_ordered(const float lo[3], const float h
 __device__ __forceinline__ bool ray_slabs_are_ordered(const Ray& r)
 {
     return (__builtin_fabsf(r.ix) < INFINITY) & (__builtin_fabsf(r.iy) < INFINITY) & (__builtin_fabsf(r.iz) < INFINITY) &
-           (r.o.x == r.o.x) & (r.o.y == r.o.y) & (r.o.z == r.o.z);
+           (__builtin_fabsf(r.o.x) < INFINITY) & (__builtin_fabsf(r.o.y) < INFINITY) & (__builtin_fabsf(r.o.z) < INFINITY);
 }
 
 struct Hit {
@@ -350,6 +351,16 @@ __device__ __forceinline__ bool tri_hit_pre(const V4 N, const V4 s1d, const V4 u
     h.t = t;
     h.front = nd < 0;
     return true;
+}
+
+// The reciprocal determinant of a DTriPre record in this unit's arithmetic (FullKernel.cl:556), from the record's own edge
+// vectors: what the default arithmetic writes into u_den[3] after an upload (kernel_wavefront.hip: precompute_denominators_kernel;
+// v_rcp_f32 is not reproducible on the host).
+__device__ __forceinline__ float pre_record_denominator(const DTriPre& p)
+{
+    const V4 u = v4(p.u_den[0], p.u_den[1], p.u_den[2], 0.0f), v = v4(p.v_s1w[0], p.v_s1w[1], p.v_s1w[2], 0.0f);
+    const float uv = dot(u, v), uu = dot(u, u), vv = dot(v, v);
+    return frcp(mad(uv, uv, -(uu * vv)));
 }
 
 template <bool PRE>

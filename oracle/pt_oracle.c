@@ -443,23 +443,27 @@ static inline uint32_t gpu_f2u(float x)
     return (uint32_t)x;
 }
 
-static f4 texture_pixel(const ptmi_texture* tex, const ptmi_uchar4* data, float u, float v)
+/* the texel Texture_GetPixelColorValue reads, h:432-437 */
+static uint32_t texture_index(const ptmi_texture* tex, float u, float v)
 {
     uint32_t x, y;
     u = u - (float)gpu_f2i(u) + (float)(u < 0 ? 1 : 0);
     v = v - (float)gpu_f2i(v) + (float)(v < 0 ? 1 : 0);
     x = gpu_f2u(u * (float)(tex->width - 1u));
     y = gpu_f2u(v * (float)(tex->height - 1u));
-    {
-        const uint32_t index = tex->offset + y * tex->width + x;
-        const ptmi_uchar4 p = data[index];
-        f4 c = mk4(fdivc((float)p.x, 255.f), fdivc((float)p.y, 255.f), fdivc((float)p.z, 255.f), fdivc((float)p.w, 255.f));
-        c.w = 1.f - c.w;
-        return c;
-    }
+    return tex->offset + y * tex->width + x;
 }
 
-static f4 sky_color(const ptmi_sky* sky, const ptmi_uchar4* data, f4 d)
+static f4 texture_pixel(const ptmi_texture* tex, const ptmi_uchar4* data, float u, float v)
+{
+    const ptmi_uchar4 p = data[texture_index(tex, u, v)];
+    f4 c = mk4(fdivc((float)p.x, 255.f), fdivc((float)p.y, 255.f), fdivc((float)p.z, 255.f), fdivc((float)p.w, 255.f));
+    c.w = 1.f - c.w;
+    return c;
+}
+
+/* the face and the texture coordinates Sky_GetColorValue hands to Sky_GetFaceColorValue, cl:438-495 */
+static int sky_face_uv(const ptmi_sky* sky, f4 d, float* pu, float* pv)
 {
     const float x = mad(sky->cos_rotation_angle, d.x, -(sky->sin_rotation_angle * d.y)); /* cl:441 */
     const float y = mad(sky->sin_rotation_angle, d.x, sky->cos_rotation_angle * d.y);    /* cl:442 */
@@ -477,6 +481,14 @@ static f4 sky_color(const ptmi_sky* sky, const ptmi_uchar4* data, f4 d)
         if (y > 0) { face = 4; u = (1 + fdiv(x, y)) / 2; v = (1 + fdiv(z, y)) / 2; }
         else       { face = 2; u = (1 + fdiv(x, y)) / 2; v = (1 - fdiv(z, y)) / 2; }
     }
+    *pu = u; *pv = v;
+    return face;
+}
+
+static f4 sky_color(const ptmi_sky* sky, const ptmi_uchar4* data, f4 d)
+{
+    float u, v;
+    const int face = sky_face_uv(sky, d, &u, &v);
     return texture_pixel(&sky->sky_textures[face], data, u, v); /* Sky_GetFaceColorValue, cl:497-512 */
 }
 
@@ -657,12 +669,16 @@ static int bvh_intersect_shadow_ray(const pto_scene* sc, ray_t* r, float squared
 /* shared body of the three Fresnel functions (cl:192-292) */
 /* n2_is_literal: the glass and varnish functions divide by a literal (1.55f, 3.f), the water function by a value selected at
  * run time (cl:223-232) - the default build divides differently by the two (fdivc / fdiv) */
-static float fresnel_fraction(float n1, float n2, int n2_is_literal, float cos1, f4 incident, f4 N, f4* refraction_dir)
+/* `total` (optional): set when the function returns on total reflection, before the refraction outputs are written */
+static float fresnel_fraction(float n1, float n2, int n2_is_literal, float cos1, f4 incident, f4 N, f4* refraction_dir, int* total)
 {
     const float sin1 = fsqrt(mad(-cos1, cos1, 1));
     const float sin2 = n2_is_literal ? fdivc(n1 * sin1, n2) : fdiv(n1 * sin1, n2);
     float cos2, r_para, r_perp;
-    if (sin2 >= 1) return 1;
+    if (sin2 >= 1) {
+        if (total) *total = 1;
+        return 1;
+    }
     cos2 = fsqrt(mad(-sin2, sin2, 1));
     r_para = fdiv(mad(n2, cos1, -(n1 * cos2)), mad(n2, cos1, n1 * cos2));
     r_perp = fdiv(mad(n1, cos1, -(n2 * cos2)), mad(n1, cos1, n2 * cos2));
@@ -676,7 +692,7 @@ static float fresnel_fraction(float n1, float n2, int n2_is_literal, float cos1,
 /* Material_FresnelGlassReflectionFraction, cl:192-217 */
 static float fresnel_glass(f4 incident, f4 N)
 {
-    return fresnel_fraction(1, MATERIAL_N_GLASS, 1, -dot4(incident, N), incident, N, NULL);
+    return fresnel_fraction(1, MATERIAL_N_GLASS, 1, -dot4(incident, N), incident, N, NULL, NULL);
 }
 
 /* Material_FresnelWaterReflectionFraction, cl:219-254.  On total reflection the
@@ -688,11 +704,11 @@ static float fresnel_glass(f4 incident, f4 N)
  * checker and the integrator agree on a zero direction and the factor n2^2/n1^2
  * there (the caller's initial values / fresnel_water's own computation); round 4
  * found the one such path in 531 M of the configs[4] stand-in. */
-static float fresnel_water(f4 incident, f4 N, int already_in_water, f4* refraction_dir, float* mult)
+static float fresnel_water(f4 incident, f4 N, int already_in_water, f4* refraction_dir, float* mult, int* total)
 {
     float n1, n2, f;
     if (already_in_water) { n1 = MATERIAL_N_WATER; n2 = 1; } else { n1 = 1; n2 = MATERIAL_N_WATER; }
-    f = fresnel_fraction(n1, n2, 0, -dot4(incident, N), incident, N, refraction_dir);
+    f = fresnel_fraction(n1, n2, 0, -dot4(incident, N), incident, N, refraction_dir, total);
     if (mult) *mult = fdiv(n2 * n2, n1 * n1);
     return f;
 }
@@ -702,7 +718,7 @@ static float fresnel_varnish(f4 incident, f4 N, f4* refraction_dir)
 {
     const float cos1 = fmaxf(0.f, fminf(1.f, -dot4(incident, N)));
     (void)refraction_dir; /* computed by the reference, never read (cl:856) */
-    return fresnel_fraction(1.0f, MATERIAL_N_VARNISH, 1, cos1, incident, N, NULL);
+    return fresnel_fraction(1.0f, MATERIAL_N_VARNISH, 1, cos1, incident, N, NULL, NULL);
 }
 
 /* Material_FresnelReflection, cl:294-300 */
@@ -840,7 +856,7 @@ static f4 compute_radiance(ray_t* r, int32_t* seed, const ptmi_material* mat, f4
     } else if (mat->type == PTMI_MAT_WATER) {
         f4 refracted = mk4(0, 0, 0, 0);
         float mult = 0;
-        const float f = fresnel_water(r->direction, Ns, r->is_in_water, &refracted, &mult);
+        const float f = fresnel_water(r->direction, Ns, r->is_in_water, &refracted, &mult, NULL);
         if (pto_random(seed) < f) {
             out = fresnel_reflection(r->direction, Ns);
             N = Ng;
@@ -1115,15 +1131,204 @@ int pto_bounding_box_intersects(const ptmi_bounding_box* bb, const float origin[
     return bbox_intersects(bb, &r, squared_distance);
 }
 
-int pto_triangle_intersects(const ptmi_triangle* tri, const float origin[4], const float direction[4],
-                            float* squared_distance, float* s, float* t, float point[4])
+int pto_triangle_intersects_side(const ptmi_triangle* tri, const float origin[4], const float direction[4],
+                                 float* squared_distance, float* s, float* t, float point[4], int* positive_normal)
 {
     ray_t r;
     int hit;
     ray_create(&r, arr4(origin), arr4(direction), 0);
+    r.material_id = 0;
     hit = triangle_intersects(NULL, tri, &r, squared_distance, 0);
-    if (hit) { *s = r.s; *t = r.t; memcpy(point, &r.point, 16); }
+    if (hit) {
+        *s = r.s; *t = r.t; memcpy(point, &r.point, 16);
+        /* cl:568: the side is `dot(N, direction) < 0`, the value the material index was picked by */
+        if (positive_normal) *positive_normal = dot4(ld4(&tri->n), r.direction) < 0;
+    }
     return hit;
+}
+
+int pto_triangle_intersects(const ptmi_triangle* tri, const float origin[4], const float direction[4],
+                            float* squared_distance, float* s, float* t, float point[4])
+{
+    return pto_triangle_intersects_side(tri, origin, direction, squared_distance, s, t, point, NULL);
+}
+
+/* The rejection of Triangle_Intersects that fires FIRST in the reference's order (cl:533, 542, 543, 561, 566), 0 = accepted:
+ * for the coverage counts of tests/test_unit_probe_model.py. */
+int pto_triangle_first_rejection(const ptmi_triangle* tri, const float origin[4], const float direction[4], float squared_distance)
+{
+    const f4 S1 = ld4(&tri->s1), S2 = ld4(&tri->s2), S3 = ld4(&tri->s3), N = ld4(&tri->n);
+    const f4 u = sub4(S2, S1), v = sub4(S3, S1);
+    ray_t r;
+    f4 q, full_ray, w;
+    float d, nd, nsd, uv, wv, wu, uu, vv, denom, s, t;
+    ray_create(&r, arr4(origin), arr4(direction), 0);
+    d = dot4(N, S1);
+    nd = dot4(N, r.direction);
+    if ((nd > -0.00001f) && (nd < 0.00001f)) return 1;
+    q = mad4s(r.direction, fdiv(d - dot4(N, r.origin), nd), r.origin);
+    full_ray = sub4(q, r.origin);
+    nsd = dot4(full_ray, full_ray);
+    if (nsd > squared_distance) return 2;
+    if (nsd < 0.00001f) return 3;
+    w = sub4(q, S1);
+    uv = dot4(u, v); wv = dot4(w, v); wu = dot4(w, u); uu = dot4(u, u); vv = dot4(v, v);
+    denom = fdiv(1, mad(uv, uv, -(uu * vv)));
+    s = mad(uv, wv, -(vv * wu)) * denom;
+    t = mad(uv, wu, -(uu * wv)) * denom;
+    if (s < 0) return 4;
+    if (t < 0) return 5;
+    if (s + t > 1) return 6;
+    if (dot4(full_ray, r.direction) < 0) return 7;
+    return 0;
+}
+
+/* which test of BoundingBox_Intersects decided (cl:68 ... 136), in the reference's order: 1 isEmpty, 2 x behind, 3 y behind,
+ * 4 tmin > tymax, 5 tymin > tmax, 6 z behind, 7 tmin > tzmax, 8 tzmin > tmax, 9 origin inside (hit), 10 beyond the limit,
+ * 11 hit */
+int pto_bounding_box_decider(const ptmi_bounding_box* bb, const float origin[4], const float direction[4], float squared_distance)
+{
+    ray_t r;
+    float t_min, t_max, ty_min, ty_max, tz_min, tz_max;
+    ray_create(&r, arr4(origin), arr4(direction), 0);
+    if (bb->is_empty) return 1;
+    if (r.direction.x > 0) { t_min = (bb->p_min.x - r.origin.x) * r.inverse.x; t_max = (bb->p_max.x - r.origin.x) * r.inverse.x; }
+    else                   { t_min = (bb->p_max.x - r.origin.x) * r.inverse.x; t_max = (bb->p_min.x - r.origin.x) * r.inverse.x; }
+    if (t_min < 0 && t_max < 0) return 2;
+    if (r.direction.y > 0) { ty_min = (bb->p_min.y - r.origin.y) * r.inverse.y; ty_max = (bb->p_max.y - r.origin.y) * r.inverse.y; }
+    else                   { ty_min = (bb->p_max.y - r.origin.y) * r.inverse.y; ty_max = (bb->p_min.y - r.origin.y) * r.inverse.y; }
+    if (ty_min < 0 && ty_max < 0) return 3;
+    if (t_min > ty_max) return 4;
+    if (ty_min > t_max) return 5;
+    if (ty_min > t_min) t_min = ty_min;
+    if (ty_max < t_max) t_max = ty_max;
+    if (r.direction.z > 0) { tz_min = (bb->p_min.z - r.origin.z) * r.inverse.z; tz_max = (bb->p_max.z - r.origin.z) * r.inverse.z; }
+    else                   { tz_min = (bb->p_max.z - r.origin.z) * r.inverse.z; tz_max = (bb->p_min.z - r.origin.z) * r.inverse.z; }
+    if (tz_min < 0 && tz_max < 0) return 6;
+    if (t_min > tz_max) return 7;
+    if (tz_min > t_max) return 8;
+    if (tz_min > t_min) t_min = tz_min;
+    if (t_min < 0) return 9;
+    if (t_min > squared_distance) return 10;
+    return 11;
+}
+
+/* the ray Ray3D_Create makes of (origin, direction): direction[4] then inverse.xyz (for the ordered-slab predicate of the tests) */
+void pto_ray_create(const float origin[4], const float direction[4], float out_direction[4], float out_inverse[3])
+{
+    ray_t r;
+    ray_create(&r, arr4(origin), arr4(direction), 0);
+    memcpy(out_direction, &r.direction, 16);
+    memcpy(out_inverse, &r.inverse, 12);
+}
+
+/* Texture_GetPixelColorValue: *index receives the texel it reads; a texel at or beyond `data_size` is NOT read (rgba untouched) */
+void pto_texture_pixel(const ptmi_texture* tex, const ptmi_uchar4* data, uint32_t data_size, float u, float v, float rgba[4],
+                       uint32_t* index)
+{
+    *index = texture_index(tex, u, v);
+    if (*index < data_size) {
+        const f4 c = texture_pixel(tex, data, u, v);
+        memcpy(rgba, &c, 16);
+    }
+}
+
+/* the face Sky_GetColorValue picks and the texel it reads there (6 = no face test passed: face 0 at uv (0, 0)) */
+uint32_t pto_sky_texel(const ptmi_sky* sky, const float direction[4], int* face_or_fallthrough)
+{
+    float u, v;
+    const f4 d = arr4(direction);
+    const int face = sky_face_uv(sky, d, &u, &v);
+    if (face_or_fallthrough) {
+        const float x = mad(sky->cos_rotation_angle, d.x, -(sky->sin_rotation_angle * d.y));
+        const float y = mad(sky->sin_rotation_angle, d.x, sky->cos_rotation_angle * d.y);
+        const float ax = fabsf(x), ay = fabsf(y), az = fabsf(d.z);
+        const int any = (az > ax && az > ay) || (ax > ay && ax > az) || (ay > ax && ay > az);
+        *face_or_fallthrough = any ? face : 6;
+    }
+    return texture_index(&sky->sky_textures[face], u, v);
+}
+
+float pto_light_power_toward(const ptmi_light* light, const float p[4], const float n[4])
+{
+    return light_power_toward(light, arr4(p), arr4(n));
+}
+
+float pto_material_brdf(int32_t type, const float incident[4], const float n[4], const float reflected[4])
+{
+    ptmi_material m;
+    memset(&m, 0, sizeof m);
+    m.type = type;
+    return material_brdf(&m, arr4(incident), arr4(n), arr4(reflected));
+}
+
+/* refraction[4] and *mult are written only when the function does not return on total reflection (cl:237 before :249-251);
+ * returns the fraction */
+float pto_fresnel_water(const float incident[4], const float n[4], int already_in_water, float refraction[4], float* mult)
+{
+    f4 refr = mk4(0, 0, 0, 0);
+    float m = 0;
+    int total = 0;
+    const float f = fresnel_water(arr4(incident), arr4(n), already_in_water, &refr, &m, &total);
+    if (!total) {
+        memcpy(refraction, &refr, 16);
+        *mult = m;
+    }
+    return f;
+}
+
+/* draw position -> pixel offset, cl:1333-1336 */
+uint32_t pto_sample_pixel(uint32_t width, uint32_t height, float sx, float sy)
+{
+    pto_scene sc;
+    int px, py;
+    memset(&sc, 0, sizeof sc);
+    sc.image_width = width;
+    sc.image_height = height;
+    sample_to_pixel(&sc, sx, sy, &px, &py);
+    return (uint32_t)py * width + (uint32_t)px;
+}
+
+/* which branch of Light_PowerToward a case takes (coverage counts): 0 directional, 1 point, 2 spot inside the inner cone,
+ * 3 spot outside the outer cone, 4 spot between the cones, 5 spot between EQUAL cones (0 / 0), 6 unknown type */
+int pto_light_branch(const ptmi_light* l, const float p4[4])
+{
+    if (l->type == PTMI_LIGHT_DIRECTIONNAL) return 0;
+    if (l->type == PTMI_LIGHT_POINT) return 1;
+    if (l->type == PTMI_LIGHT_SPOT) {
+        const f4 lrd = normalize4(sub4(arr4(p4), ld4(&l->position)));
+        const float cos_angle = dot4(lrd, ld4(&l->direction));
+        if (cos_angle > l->cos_inner) return 2;
+        if (cos_angle < l->cos_outer) return 3;
+        return l->cos_inner == l->cos_outer ? 5 : 4;
+    }
+    return 6;
+}
+
+/* which branch of Material_ConcentricSampleDisk a seed takes, in its order (cl:352-397): 4 |sx| < 1e-4, 5 |sy| < 1e-4 (alone),
+ * 0..3 the octant pairs (sx > -sy: sx > sy / not; else: sx < sy / not); *both = the two overrides hold together */
+int pto_disk_branch(int32_t seed, int* both)
+{
+    const float u1 = pto_random(&seed);
+    const float u2 = pto_random(&seed);
+    const float sx = mad(2, u1, -1), sy = mad(2, u2, -1);
+    if (both) *both = fabsf(sx) < 0.0001f && fabsf(sy) < 0.0001f;
+    if (fabsf(sx) < 0.0001f) return 4;
+    if (fabsf(sy) < 0.0001f) return 5;
+    if (sx > -sy) return sx > sy ? 0 : 1;
+    return sx < sy ? 2 : 3;
+}
+
+void pto_fresnel_reflection(const float v[4], const float n[4], float out[4])
+{
+    const f4 r = fresnel_reflection(arr4(v), arr4(n));
+    memcpy(out, &r, 16);
+}
+
+void pto_put_in_same_hemisphere(const float v[4], const float n[4], float out[4])
+{
+    const f4 r = put_in_same_hemisphere(arr4(v), arr4(n));
+    memcpy(out, &r, 16);
 }
 
 void pto_cosine_sample_hemisphere(int32_t* seed, const float n[4], float out[4])

@@ -114,6 +114,24 @@ int pto_bounding_box_intersects(const ptmi_bounding_box* bb, const float origin[
                                 float squared_distance);
 int pto_triangle_intersects(const ptmi_triangle* tri, const float origin[4], const float direction[4],
                             float* squared_distance, float* s, float* t, float point[4]);
+/* the same, and *positive_normal = the side that was hit (cl:568), written on a hit */
+int pto_triangle_intersects_side(const ptmi_triangle* tri, const float origin[4], const float direction[4],
+                                 float* squared_distance, float* s, float* t, float point[4], int* positive_normal);
+/* which test decided, in the reference's order (coverage counts of tests/test_unit_probe_model.py; the lists are in pt_oracle.c) */
+int pto_triangle_first_rejection(const ptmi_triangle* tri, const float origin[4], const float direction[4], float squared_distance);
+int pto_bounding_box_decider(const ptmi_bounding_box* bb, const float origin[4], const float direction[4], float squared_distance);
+void pto_ray_create(const float origin[4], const float direction[4], float out_direction[4], float out_inverse[3]);
+void pto_texture_pixel(const ptmi_texture* tex, const ptmi_uchar4* textures_data, uint32_t data_size, float u, float v,
+                       float rgba[4], uint32_t* index);
+uint32_t pto_sky_texel(const ptmi_sky* sky, const float direction[4], int* face_or_fallthrough);
+float pto_light_power_toward(const ptmi_light* light, const float p[4], const float n[4]);
+float pto_material_brdf(int32_t type, const float incident[4], const float n[4], const float reflected[4]);
+float pto_fresnel_water(const float incident[4], const float n[4], int already_in_water, float refraction[4], float* mult);
+uint32_t pto_sample_pixel(uint32_t width, uint32_t height, float sx, float sy);
+int pto_light_branch(const ptmi_light* light, const float p[4]);
+int pto_disk_branch(int32_t seed, int* both);
+void pto_fresnel_reflection(const float v[4], const float n[4], float out[4]);
+void pto_put_in_same_hemisphere(const float v[4], const float n[4], float out[4]);
 void pto_concentric_sample_disk(int32_t* seed, float* dx, float* dy);
 void pto_cosine_sample_hemisphere(int32_t* seed, const float n[4], float out[4]);
 float pto_fresnel_glass(const float incident[4], const float n[4]);
