@@ -134,7 +134,8 @@ typedef struct ptmi_counters {
  * one-path-per-lane kernel. */
 typedef struct ptmi_scheduler_stats {
     uint64_t trips_node, lanes_node;         /* node trips: lanes that took an inner-node step */
-    uint64_t trips_triangle, lanes_triangle; /* leaf passes: triangles tested, one per lane */
+    uint64_t trips_triangle, lanes_triangle; /* leaf passes: triangles tested, one per lane (+ the triangles of leaves beyond a
+                                              * query's limit, which are counted without a pass: csrc/leaf_cull.h) */
     uint64_t trips_path, lanes_path;         /* path logic (shade / shadow set-up / scatter / regenerate) */
     uint64_t cycles_path, cycles_loop;       /* shader-clock cycles, summed over waves: inside path-logic passes / in the main loop */
     uint64_t leaf_item_violations;           /* leaf passes: work items whose owner lane or triangle record index was out of range when a

@@ -39,17 +39,21 @@
 //  * The one thing a leaf pass cannot express is a NaN distance (the reference accepts it and then keeps the LAST triangle
 //    that passes, not the nearest): a path whose ray is not a number is GIVEN UP where path logic sets the ray up - a marked
 //    radiance goes to its staging slot - and redo_poisoned_kernel, queued behind every staged launch, traces it again with
-//    the reference's literal loops (ptmi_literal_path.hpp).  Scenes whose RECORDS yield NaN distances never get here
-//    (scene_layout.cpp: scene_needs_literal_kernel).
+//    the reference's literal loops (ptmi_literal_path.hpp).  Scenes whose RECORDS yield NaN distances (scene_layout.cpp:
+//    scene_needs_literal_kernel) run the NANSAFE instantiation, which also looks at every accepted distance.
+//  * A leaf no triangle of which can be accepted - its box lies farther from the ray's origin than the query's limit reaches,
+//    and the upload has certified its triangles (leaf_cull.h) - is COUNTED, not fetched: the reference walks on through every
+//    box behind the hit it has found, and the counts of that walk are results, the rejected tests are not.
 //
 // Exit: a lane dies when it has seen every queue empty; a wave leaves the outer loop when no lane is alive
 // (every path is bounded by the ray depth, every traversal by the finite tree, and a pass or trip only runs
 // with at least one lane that wants it).
 //
-// The kernel's limits, measured: DESIGN.md 5 "What binds".  tools/isa_trip.sh prints the instruction mix of the
-// traversal loop.
+// The kernel's limits, measured: DESIGN.md 5 "What binds" (the instruction counts of a trip there are read off the
+// disassembly of the traversal loop).
 #include <hip/hip_runtime.h>
 
+#include "leaf_cull.h"
 #include "ptmi_device.hpp"
 #include "ptmi_shading.hpp"
 #include "ptmi_literal_path.hpp"
@@ -134,6 +138,7 @@ struct DWarm {
     uint32_t source_seed;       // PTMI_FLAG_SOURCE_SEED (non-parity mode)
     uint32_t wait_debt;         // lane-trips of waiting before a path-logic pass (launch_render_wavefront chooses it)
     uint32_t split_paths;       // DScene::split_paths
+    uint32_t leaf_cull;         // DScene::leaf_cull
 };
 
 // A finished path's three histogram bins in one word: depth (6 bits, < kStatDepthBins), box tests and triangle tests
@@ -224,7 +229,8 @@ __device__ __forceinline__ void give_path_up(V4& radiance, V4& transfer, uint32_
 // never reaches such a record - is the ordinary kernel.  (A shadow query needs nothing: it ends at the FIRST accepted triangle
 // in index order whatever the distances are, and its limit never changes.)  Clean scenes run the instantiations without it.
 // BLOCK: lanes per workgroup (kWfBlock, or kWfBlockNarrow for deep trees: see there).
-template <bool STATS, bool PRE, bool SS, bool PLAIN = false, bool NANSAFE = false, int BLOCK = 256>
+// CULL: leaves beyond a query's limit are counted instead of tested (leaf_cull.h; precomputed records only).
+template <bool STATS, bool PRE, bool SS, bool PLAIN = false, bool NANSAFE = false, int BLOCK = 256, bool CULL = false>
 __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN_WAVES_GENERAL) render_wavefront_kernel(
                                                                     const DScene* __restrict__ scene_in_memory, const DWarm sc_arg, const uint32_t first_iteration,
                                                                     const uint32_t n_iterations, const uint32_t iteration_stride,
@@ -252,6 +258,12 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
     // The general instantiations gain 3-6 % (their spilled registers also fall from 67 to 30: the allocator's doing), the plain one
     // loses 0.8 %.
     constexpr bool kTos = !PLAIN;
+    // Leaves beyond the limit are counted instead of tested (leaf_cull.h).  An instantiation of its own: a node step pays two
+    // box distances for it, which a scene whose rays meet nothing behind their hits (the Cornell box) gets nothing back for -
+    // the launch picks it per scene (instance_for).  The statistics and SUPER_SAMPLING builds always hold the code and mask the
+    // records' bits with sc.leaf_cull.
+    static_assert(!CULL || PRE, "cull bits are computed for precomputed records only");
+    constexpr bool kCull = CULL;
     extern __shared__ __attribute__((aligned(16))) uint32_t stack_mem[];
     // (the statistics build: one block with every counter, its launches never render for several calls)
     constexpr uint32_t kBlockCounters = STATS ? (uint32_t)C_COUNT : PTMI_COUNTER_SPLITS * kSplitWords;
@@ -308,7 +320,7 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
     bool exact_boxes = false;  // this ray needs the literal box test (see box_hit_ordered)
     bool wave_exact = true;    // ... and so does some ray of this wave (wave-uniform, refreshed after every path-logic pass)
     uint32_t cur = REF_IDLE, tri_i = 0, tri_end = 0;
-    uint32_t dir_signs = 0;  // bit k: direction component k > 0 (which child of a node cut along k is the near one)
+    uint32_t dir_signs = 0;  // bit k: direction component k > 0 (which child of a node cut along k is the near one); bits 3, 4: see node_step
     uint32_t* sp = stack_floor;  // the top entry (the sentinel when the stack is empty)
     uint32_t tos = REF_NONE;     // kTos: ... and its value; invariant tos == *sp
     // the point of the closest hit, as path logic needs it when a query has finished
@@ -418,6 +430,10 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
     uint2* const item_mem = reinterpret_cast<uint2*>(&stack_mem[(kHitRecordWords + 3 + stack_levels) * kWfBlock]) + (tid & ~63u);
     const uint32_t lane = tid & 63u, wave_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid & ~63u));  // (a scalar)
     uint32_t pass_rounds = 0, pass_items = 0, item_violations = 0;
+    // (statistics build) triangles this lane counted without a pass, in culled leaves: they enter C_LANES_T beside the items of
+    // the passes, which keeps "every counted triangle test was one item" (ptmi_scheduler_stats.lanes_triangle); the passes
+    // they saved show in C_TRIPS_T
+    uint32_t culled_items = 0;
     const uint32_t n_records = STATS ? cold_scene().n_records : 0u;
     auto leaf_pass = [&](bool waits_at_leaf) {
         auto lanes_below = [&](unsigned long long m) {
@@ -529,6 +545,15 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
         // dir[cutAxis] > 0 (:663) from a per-ray word of the three signs (one bit test; selected from the three sign masks
         // the box tests hold it took three compares and five scalar instructions)
         const bool fwd = ((dir_signs >> axis) & 1u) != 0;
+        // (Both distances BEFORE the box tests, which then use up the box registers in place: two registers across the tests.
+        // Behind them the twelve box registers stay alive through the tests, and the plain instantiation spills eighteen
+        // registers more around the loop: 23 against a budget of 8, tests/test_resources.py.)
+        float d2_1 = 0, d2_2 = 0;
+        if (kCull) {
+            d2_1 = ptmi_cull::box_distance2(lo1, hi1, r.o.x, r.o.y, r.o.z);
+            d2_2 = ptmi_cull::box_distance2(lo2, hi2, r.o.x, r.o.y, r.o.z);
+            asm volatile("" : "+v"(d2_1), "+v"(d2_2));  // (made HERE: left alone, the compiler sinks them behind the tests)
+        }
         bool h1, h2;
         if (!wave_exact) {
             h1 = box_hit_ordered(lo1, hi1, r, limit);
@@ -538,6 +563,18 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
             h2 = box_hit(lo2, hi2, (ref2 & REF_EMPTY) != 0, r, limit);
         }
         p_bbx += 2;
+        // The leaf this step chooses (near child or only child hit - not one it pops) is CULLED when the record certifies it and
+        // its box, still in the step's registers, lies beyond the limit (leaf_cull.h: then every triangle of it is rejected):
+        // the lane counts its triangles and pops, as it does after the leaf's last pass.  Closest-hit and shadow queries alike
+        // (acceptance is `nsd <= limit` for both, cl:537; a shadow query that accepts nothing counts the whole leaf).
+        bool culled = false;
+        if (kCull) {
+            // (the ray's own part of the rule was evaluated where the ray was set up: bits 3 and 4 of dir_signs)
+            const uint32_t cull_bits = __float_as_uint(d.w) & (dir_signs >> 3) & sc.leaf_cull;
+            const bool first = fwd ? h1 : !h2;  // which child the step chooses, when it chooses one
+            const bool certified = (cull_bits & (first ? ptmi_cull::kCullChild1 : ptmi_cull::kCullChild2)) != 0u;
+            culled = (h1 | h2) & certified & ptmi_cull::box_is_beyond(first ? d2_1 : d2_2, limit);
+        }
         // (every choice as a select on the two hit masks themselves: combined into new booleans first - both, neither - the
         // compiler builds them as 0 / 1 integers in vector registers: seven instructions more per step)
         if (kTos) {
@@ -556,11 +593,23 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
                 tos = *sp;
             }
             if (cur != REF_NONE && (cur & REF_LEAF)) {  // (the triangle range of a lane that takes node steps is free)
-                decode_leaf(sc, cur, tri_i, tri_end);
-                cur = tos;
-                uint32_t* const under = sp - kWfBlock;
-                sp = under < stack_floor ? stack_floor : under;
-                tos = *sp;
+                bool leaf = true;
+                if (kCull && culled) {
+                    p_tri += (cur >> REF_COUNT_SHIFT) & 7u;
+                    if (STATS) culled_items += (cur >> REF_COUNT_SHIFT) & 7u;
+                    cur = tos;
+                    uint32_t* const under = sp - kWfBlock;
+                    sp = under < stack_floor ? stack_floor : under;
+                    tos = *sp;
+                    leaf = cur != REF_NONE && (cur & REF_LEAF);  // (a popped leaf carries no mark: its triangles are tested)
+                }
+                if (leaf) {
+                    decode_leaf(sc, cur, tri_i, tri_end);
+                    cur = tos;
+                    uint32_t* const under = sp - kWfBlock;
+                    sp = under < stack_floor ? stack_floor : under;
+                    tos = *sp;
+                }
             }
             return;
         }
@@ -574,10 +623,21 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
         cur = h1 ? child : (h2 ? child : popped);
         sp = h1 ? sp : (h2 ? sp : under);
         if (cur != REF_NONE && (cur & REF_LEAF)) {  // (the triangle range of a lane that takes node steps is free)
-            decode_leaf(sc, cur, tri_i, tri_end);
-            cur = *sp;
-            uint32_t* const under = sp - kWfBlock;
-            sp = under < stack_floor ? stack_floor : under;
+            bool leaf = true;
+            if (kCull && culled) {
+                p_tri += (cur >> REF_COUNT_SHIFT) & 7u;
+                if (STATS) culled_items += (cur >> REF_COUNT_SHIFT) & 7u;
+                cur = *sp;
+                uint32_t* const under = sp - kWfBlock;
+                sp = under < stack_floor ? stack_floor : under;
+                leaf = cur != REF_NONE && (cur & REF_LEAF);  // (a popped leaf carries no mark: its triangles are tested)
+            }
+            if (leaf) {
+                decode_leaf(sc, cur, tri_i, tri_end);
+                cur = *sp;
+                uint32_t* const under = sp - kWfBlock;
+                sp = under < stack_floor ? stack_floor : under;
+            }
         }
     };
 
@@ -829,6 +889,8 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
             if (new_ray) {
                 ray_set_direction(r, new_direction);
                 dir_signs = (r.d.x > 0 ? 1u : 0u) | (r.d.y > 0 ? 2u : 0u) | (r.d.z > 0 ? 4u : 0u);
+                // ... and, above the signs, the two cull bits of a node record this ray honours (leaf_cull.h: ray_may_cull)
+                if (kCull && ptmi_cull::ray_may_cull(r.o.x, r.o.y, r.o.z, r.o.w, r.d.w)) dir_signs |= (ptmi_cull::kCullChild1 | ptmi_cull::kCullChild2) << 3;
                 // A ray that is not a number - a refraction at |cos| = 1 + 1 ulp takes the square root of a negative (cl:235),
                 // a hit on a fake plane 1e30 away overflows - makes every triangle test compute a NaN distance, and the
                 // reference ACCEPTS those (its rejections are comparisons, cl:533-567): from then on nothing is "too far" and
@@ -876,6 +938,7 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
         atomicAdd(&block_counters[C_CYCLES_P], cycles_p);
         atomicAdd(&block_counters[C_CYCLES_LOOP], __builtin_amdgcn_s_memtime() - loop_start);
     }
+    if (STATS && culled_items != 0u) atomicAdd(&block_counters[C_LANES_T], (unsigned long long)culled_items);
     if (STATS && item_violations != 0u) atomicAdd(&block_counters[C_ITEM_VIOLATIONS], (unsigned long long)item_violations);
     __syncthreads();
     // every surface hit sends one shadow ray to every light (Scene_ComputeDirectIllumination, :901-954)
@@ -1181,10 +1244,10 @@ static bool five_wide_workgroups_fit(const WavefrontLaunch& w)
 // Launches one instantiation on its persistent grid on the CURRENT device (instantiations differ in registers, devices in CUs and
 // partition mode, hence in workgroups held at once): asked once per (instantiation, device, stack levels); host threads that
 // drive contexts of their own may race for an entry, and then write the same value.
-template <bool S, bool P, bool A, bool L, bool N, int B>
+template <bool S, bool P, bool A, bool L, bool N, int B, bool C = false>
 static void launch_instance(const WavefrontLaunch& w)
 {
-    auto kernel = PTMI_DEV_NS::render_wavefront_kernel<S, P, A, L, N, B>;
+    auto kernel = PTMI_DEV_NS::render_wavefront_kernel<S, P, A, L, N, B, C>;
     static std::atomic<int> resident_cache[kMaxCachedDevices][PTMI_BVH_MAX_DEPTH + 1];
     int resident = w.cached_device ? resident_cache[w.device][w.lv].load(std::memory_order_relaxed) : 0;
     if (resident == 0) {
@@ -1208,15 +1271,21 @@ static LaunchInstance instance_for(const DScene& sc, bool scheduler_stats, bool 
     constexpr int kWide = PTMI_DEV_NS::kWfBlock, kNarrow = PTMI_DEV_NS::kWfBlockNarrow;
     const bool pre = sc.tris_precomputed != 0;
     //                                               STATS  PRE    SS     PLAIN  NANSAFE
-    if (sc.super_sampling) return pre ? launch_instance<true, true, true, false, true, kWide> : launch_instance<true, false, true, false, true, kWide>;
-    if (scheduler_stats) return pre ? launch_instance<true, true, false, false, true, kWide> : launch_instance<true, false, false, false, true, kWide>;
+    const bool cull = pre && sc.leaf_cull != 0u;  // (the host clears leaf_cull where culling is off or cannot pay: ptmi_scene_memory.cpp)
+    if (sc.super_sampling) return pre ? launch_instance<true, true, true, false, true, kWide, true> : launch_instance<true, false, true, false, true, kWide>;
+    if (scheduler_stats) return pre ? launch_instance<true, true, false, false, true, kWide, true> : launch_instance<true, false, false, false, true, kWide>;
     if (sc.nan_safe) {
         if (plain) return launch_instance<false, true, false, true, true, kWide>;
         return pre ? launch_instance<false, true, false, false, true, kWide> : launch_instance<false, false, false, false, true, kWide>;
     }
-    if (plain)  // the common case, BASELINE's untextured scenes among them
+    if (plain) {  // the common case, BASELINE's untextured scenes among them
+        if (cull) return narrow ? launch_instance<false, true, false, true, false, kNarrow, true> : launch_instance<false, true, false, true, false, kWide, true>;
         return narrow ? launch_instance<false, true, false, true, false, kNarrow> : launch_instance<false, true, false, true, false, kWide>;
-    if (pre) return narrow ? launch_instance<false, true, false, false, false, kNarrow> : launch_instance<false, true, false, false, false, kWide>;
+    }
+    if (pre) {
+        if (cull) return narrow ? launch_instance<false, true, false, false, false, kNarrow, true> : launch_instance<false, true, false, false, false, kWide, true>;
+        return narrow ? launch_instance<false, true, false, false, false, kNarrow> : launch_instance<false, true, false, false, false, kWide>;
+    }
     return launch_instance<false, false, false, false, false, kWide>;
 }
 
@@ -1261,6 +1330,7 @@ int PTMI_ARITH(launch_render_wavefront)(const DScene& sc, const DScene* scene_in
         warm.russian_roulette = sc.russian_roulette;
         warm.source_seed = sc.source_seed;
         warm.split_paths = sc.split_paths;
+        warm.leaf_cull = sc.leaf_cull;
         const bool plain = sc.tris_precomputed && sc.plain_shading && sc.sampler == PTMI_SAMPLER_JITTERED && !sc.russian_roulette &&
                            sc.n_lights == 1 && !sc.super_sampling && !scheduler_stats;
         // lane-trips of waiting a wave tolerates before it spends a pass on path logic: 768 from tree depth 16 on, below that

@@ -109,6 +109,9 @@ int ptmi_setup_context(ptmi_ctx** out, const ptmi_config* cfg)
             if (want >= 1 && want <= 32 && (uint32_t)want < ctx->iterations_per_launch) ctx->iterations_per_launch = (uint32_t)want;
         }
     }
+    // env: developer switch - 0: the wavefront kernel fetches and tests the triangles of every leaf it reaches (leaf_cull.h);
+    // 1: it culls in every scene whose records carry the bits, also where upload_scene would not expect it to pay
+    if (const char* v = std::getenv("PTMI_LEAF_CULL")) ctx->leaf_cull = v[0] != '0' ? 1 : 0;
     *out = ctx;
     return PTMI_OK;
 }

@@ -181,6 +181,8 @@ int build_layout(const ptmi_config& cfg, const ptmi_scene* sc, Relayout& out, st
     // What a ray reads next is then usually the neighbour of what it has just read: the caches fetch 128-byte lines,
     // so a bottom-level node brings its first triangle along and an even-numbered node its first inner child
     // (the integrator is bound by cache misses in flight).  `seen` rejects cycles and shared subtrees.
+    // The certificates of leaf_cull.h speak of precomputed records whose distances are numbers: the other scenes get no bits.
+    const bool cull_bits = out.tris_precomputed && out.literal_kernel_reason.empty();
     std::vector<uint8_t> seen(nn, 0);
     std::string why;
     auto check_node = [&](uint32_t id) -> bool {
@@ -252,6 +254,9 @@ int build_layout(const ptmi_config& cfg, const ptmi_scene* sc, Relayout& out, st
         d.lo2[0] = b2.p_min.x; d.lo2[1] = b2.p_min.y; d.lo2[2] = b2.p_min.z;
         d.hi2[0] = b2.p_max.x; d.hi2[1] = b2.p_max.y; d.hi2[2] = b2.p_max.z;
         d.ref1 = r1; d.ref2 = r2; d.axis = n.cut_axis; d.pad = 0;  // inner children: index patched in when they are emitted
+        // which of the two are leaves no triangle of which can be accepted from beyond the limit (leaf_cull.h)
+        if (cull_bits) d.pad = ptmi_cull::record_cull_bits(d, [&](uint32_t r) -> const ptmi_triangle& { return sc->triangulation[out.tri_ids[r]]; });
+        out.cullable_leaves += ((d.pad & ptmi_cull::kCullChild1) ? 1u : 0u) + ((d.pad & ptmi_cull::kCullChild2) ? 1u : 0u);
         // the short slab test (box_hit_ordered) needs finite, ordered boxes; anything else keeps the literal form
         for (int k = 0; k < 3; k++) {
             if (!(r1 & REF_EMPTY) && !(std::isfinite(d.lo1[k]) && std::isfinite(d.hi1[k]) && d.lo1[k] <= d.hi1[k])) out.boxes_ordered = false;

@@ -23,6 +23,7 @@ struct Relayout {
     bool tris_precomputed = false;
     bool plain_shading = false; // every material a plain-colour MAT_STANDART, every light a LIGHT_POINT
     bool boxes_ordered = true;  // all non-empty child boxes finite with pMin <= pMax
+    uint32_t cullable_leaves = 0;  // leaves whose record bit says the kernel may count them untested (leaf_cull.h)
     std::string literal_kernel_reason;  // scene_needs_literal_kernel()
     uint32_t root_ref = 0;
     uint32_t max_depth = 0;

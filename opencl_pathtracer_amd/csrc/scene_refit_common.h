@@ -21,6 +21,7 @@
 #include <cstdint>
 
 #include "bvh_build_common.h"
+#include "leaf_cull.h"
 #include "ptmi_internal.h"
 
 namespace ptmi_refit {
@@ -147,11 +148,14 @@ PTMI_HD void refit_child_box(uint32_t ref, const DNode* nodes, const DBigLeaf* b
 
 // One inner record of a level pass: both child boxes refitted; a child flagged empty keeps what it holds (the inverted infinite
 // box where the boxes are ordered).  Reads records of the level below only, writes `d` only: a level's records can be taken in
-// any order.
+// any order.  A record that carries "child is a cullable leaf" bits (leaf_cull.h) gets them again from its new boxes and
+// triangles, by the function the upload computed them with: unchanged triangles, unchanged bits.
 PTMI_HD void refit_record(DNode* d, const DNode* nodes, const DBigLeaf* big_leaves, const uint32_t* tri_ids, const ptmi_triangle* tris)
 {
     if (!(d->ref1 & ptmi_internal::REF_EMPTY)) refit_child_box(d->ref1, nodes, big_leaves, tri_ids, tris, d->lo1, d->hi1);
     if (!(d->ref2 & ptmi_internal::REF_EMPTY)) refit_child_box(d->ref2, nodes, big_leaves, tri_ids, tris, d->lo2, d->hi2);
+    if (d->pad & ptmi_cull::kCullComputed)
+        d->pad = ptmi_cull::record_cull_bits(*d, [&](uint32_t r) -> const ptmi_triangle& { return tris[tri_ids[r]]; });
 }
 
 }  // namespace ptmi_refit

@@ -12,6 +12,14 @@ from collections import Counter
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+# the mangled template arguments: five bools, the workgroup's lanes, and whether the instantiation culls leaves (leaf_cull.h)
+NAME = r"\w+?23render_wavefront_kernelI((?:Lb[01]E){5})(?:Li(\d+)E)?(?:Lb([01])E)?E"
+
+
+def key_of(m):
+    return "".join(re.findall(r"Lb([01])E", m.group(1))) + ("b" + m.group(2) if m.group(2) not in (None, "256") else "") + ("c" if m.group(3) == "1" else "")
+
+
 def resources(tree=ROOT, arithmetic=1, extra=()):
     csrc = os.path.join(tree, "opencl_pathtracer_amd", "csrc")
     out = os.path.join(tempfile.mkdtemp(), "wf.s")
@@ -23,16 +31,16 @@ def resources(tree=ROOT, arithmetic=1, extra=()):
         raise RuntimeError(r.stderr[-3000:])
     res = {}
     for block in re.split(r"Function Name: ", r.stderr)[1:]:
-        m = re.match(r"\w+?23render_wavefront_kernelI((?:Lb[01]E)+)(?:Li(\d+)E)?E", block)
+        m = re.match(NAME, block)
         if not m:
             continue
-        key = "".join(re.findall(r"Lb([01])E", m.group(1))) + ("b" + m.group(2) if m.group(2) not in (None, "256") else "")  # STATS PRE SS PLAIN NANSAFE [bN: lanes per workgroup]
+        key = key_of(m)  # STATS PRE SS PLAIN NANSAFE [bN: lanes per workgroup] [c: the culling instantiation]
         res[key] = {k.strip(): int(v) for k, v in re.findall(r"remark: [^\n]*?\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", block)}
     name, depth2 = None, False
     for line in open(out):
-        m = re.match(r"\w+?23render_wavefront_kernelI((?:Lb[01]E)+)(?:Li(\d+)E)?E\w*:", line)
+        m = re.match(NAME + r"\w*:", line)
         if m:
-            name, depth2 = "".join(re.findall(r"Lb([01])E", m.group(1))) + ("b" + m.group(2) if m.group(2) not in (None, "256") else ""), False
+            name, depth2 = key_of(m), False
             res[name]["loop"] = Counter()
         elif re.match(r"(\.LBB|; %bb\.)", line):
             depth2 = "Depth=2" in line
