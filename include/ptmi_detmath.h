@@ -21,14 +21,14 @@
 #define PTMI_DETMATH_H
 
 #if defined(__HIPCC__)
-#define PTMI_HD __host__ __device__ static inline
+#define PTMI_DETMATH_FN __host__ __device__ static inline
 #else
 #include <math.h>
-#define PTMI_HD static inline
+#define PTMI_DETMATH_FN static inline
 #endif
 
 /* sin and cos of x for |x| < 131072 (the reference's argument is theta in [0, 2*pi]). */
-PTMI_HD void ptmi_sincosf(float x, float* sin_out, float* cos_out)
+PTMI_DETMATH_FN void ptmi_sincosf(float x, float* sin_out, float* cos_out)
 {
     const float ax = x < 0.0f ? -x : x;
     /* __ocmlpriv_trigredsmall_f32: k = rint(ax * 2/pi), r = ax - k * pi/2 with pi/2 split in three */

@@ -23,14 +23,8 @@
 #include <cmath>
 #include <cstdint>
 
+#include "ptmi_hd.h"
 #include "ptmi_scene.h"
-
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define PTMI_HD __host__ __device__ __forceinline__
-#else
-#define PTMI_HD inline
-#endif
 
 namespace ptmi_bvh {
 

@@ -181,13 +181,8 @@ __device__ __forceinline__ uint32_t pack_path_statistics(uint32_t depth, uint32_
 
 __device__ __forceinline__ void decode_leaf(const DWarm& sc, uint32_t ref, uint32_t& tri_i, uint32_t& tri_end)
 {
-    uint32_t count = (ref >> REF_COUNT_SHIFT) & 7u;
-    uint32_t start = ref & REF_INDEX_MASK_LEAF;
-    if (count == REF_COUNT_BIG) {
-        const DBigLeaf bl = sc.big_leaves[start];
-        start = bl.start;
-        count = bl.count;
-    }
+    uint32_t start, count;
+    leaf_range(ref, sc.big_leaves, &start, &count);
     tri_i = start;
     tri_end = start + count;
 }
@@ -435,6 +430,27 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
     // they saved show in C_TRIPS_T
     uint32_t culled_items = 0;
     const uint32_t n_records = STATS ? cold_scene().n_records : 0u;
+    // The top of the stack becomes the lane's reference, and the entry under it the top (under the last one lies the sentinel).
+    // kTos: the new top's value is read from LDS here, but needed only when this lane pops the next time.
+    auto pop = [&]() {
+        cur = kTos ? tos : *sp;
+        uint32_t* const under = sp - kWfBlock;
+        sp = under < stack_floor ? stack_floor : under;
+        if (kTos) tos = *sp;
+    };
+    // `cur` refers to a leaf and the lane's triangle range is free: the range takes the leaf and `cur` what the stack holds next.
+    // culled: this leaf is counted instead (node_step) - and what is popped in its place may be a leaf again, which carries no
+    // mark: its triangles are tested.
+    auto enter_leaf = [&](bool culled) {
+        if (kCull && culled) {
+            p_tri += ref_leaf_count(cur);
+            if (STATS) culled_items += ref_leaf_count(cur);
+            pop();
+            if (!ref_is_leaf(cur)) return;
+        }
+        decode_leaf(sc, cur, tri_i, tri_end);
+        pop();
+    };
     auto leaf_pass = [&](bool waits_at_leaf) {
         auto lanes_below = [&](unsigned long long m) {
             return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
@@ -524,13 +540,7 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
             } else {
                 p_tri += cnt; tri_i += cnt;
             }
-            if (tri_i >= tri_end && cur != REF_NONE && (cur & REF_LEAF)) {
-                decode_leaf(sc, cur, tri_i, tri_end);
-                cur = kTos ? tos : *sp;
-                uint32_t* const under = sp - kWfBlock;
-                sp = under < stack_floor ? stack_floor : under;
-                if (kTos) tos = *sp;
-            }
+            if (tri_i >= tri_end && ref_is_leaf(cur)) enter_leaf(false);
         }
     };
     // one inner-node step of the calling lanes (:660-697)
@@ -539,28 +549,26 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
     auto node_step = [&]() {
         const float4* const rec = reinterpret_cast<const float4*>(&sc.tris[cur & REF_INDEX_MASK_INNER]);
         const float4 a = rec[0], b = rec[1], c = rec[2], d = rec[3];
-        const float lo1[3] = {a.x, a.y, a.z}, hi1[3] = {a.w, b.x, b.y};
-        const float lo2[3] = {b.z, b.w, c.x}, hi2[3] = {c.y, c.z, c.w};
-        const uint32_t ref1 = __float_as_uint(d.x), ref2 = __float_as_uint(d.y), axis = __float_as_uint(d.z);
+        const NodeView n = node_view(a, b, c, d);
         // dir[cutAxis] > 0 (:663) from a per-ray word of the three signs (one bit test; selected from the three sign masks
         // the box tests hold it took three compares and five scalar instructions)
-        const bool fwd = ((dir_signs >> axis) & 1u) != 0;
+        const bool fwd = ((dir_signs >> n.axis) & 1u) != 0;
         // (Both distances BEFORE the box tests, which then use up the box registers in place: two registers across the tests.
         // Behind them the twelve box registers stay alive through the tests, and the plain instantiation spills eighteen
         // registers more around the loop: 23 against a budget of 8, tests/test_resources.py.)
         float d2_1 = 0, d2_2 = 0;
         if (kCull) {
-            d2_1 = ptmi_cull::box_distance2(lo1, hi1, r.o.x, r.o.y, r.o.z);
-            d2_2 = ptmi_cull::box_distance2(lo2, hi2, r.o.x, r.o.y, r.o.z);
+            d2_1 = ptmi_cull::box_distance2(n.lo1, n.hi1, r.o.x, r.o.y, r.o.z);
+            d2_2 = ptmi_cull::box_distance2(n.lo2, n.hi2, r.o.x, r.o.y, r.o.z);
             asm volatile("" : "+v"(d2_1), "+v"(d2_2));  // (made HERE: left alone, the compiler sinks them behind the tests)
         }
         bool h1, h2;
         if (!wave_exact) {
-            h1 = box_hit_ordered(lo1, hi1, r, limit);
-            h2 = box_hit_ordered(lo2, hi2, r, limit);
+            h1 = box_hit_ordered(n.lo1, n.hi1, r, limit);
+            h2 = box_hit_ordered(n.lo2, n.hi2, r, limit);
         } else {
-            h1 = box_hit(lo1, hi1, (ref1 & REF_EMPTY) != 0, r, limit);
-            h2 = box_hit(lo2, hi2, (ref2 & REF_EMPTY) != 0, r, limit);
+            h1 = box_hit(n.lo1, n.hi1, (n.ref1 & REF_EMPTY) != 0, r, limit);
+            h2 = box_hit(n.lo2, n.hi2, (n.ref2 & REF_EMPTY) != 0, r, limit);
         }
         p_bbx += 2;
         // The leaf this step chooses (near child or only child hit - not one it pops) is CULLED when the record certifies it and
@@ -570,75 +578,23 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
         bool culled = false;
         if (kCull) {
             // (the ray's own part of the rule was evaluated where the ray was set up: bits 3 and 4 of dir_signs)
-            const uint32_t cull_bits = __float_as_uint(d.w) & (dir_signs >> 3) & sc.leaf_cull;
+            const uint32_t cull_bits = n.cull & (dir_signs >> 3) & sc.leaf_cull;
             const bool first = fwd ? h1 : !h2;  // which child the step chooses, when it chooses one
             const bool certified = (cull_bits & (first ? ptmi_cull::kCullChild1 : ptmi_cull::kCullChild2)) != 0u;
             culled = (h1 | h2) & certified & ptmi_cull::box_is_beyond(first ? d2_1 : d2_2, limit);
         }
         // (every choice as a select on the two hit masks themselves: combined into new booleans first - both, neither - the
         // compiler builds them as 0 / 1 integers in vector registers: seven instructions more per step)
-        if (kTos) {
-            const uint32_t far_ref = fwd ? ref2 : ref1;
-            sp[kWfBlock] = far_ref;
-            uint32_t* const pushed = sp + kWfBlock;
-            const uint32_t child = fwd ? (h1 ? ref1 : ref2) : (h2 ? ref2 : ref1);  // near child if it was hit, else the far one
-            // both hit: the far child becomes the top; one hit: nothing moves; none: the top is the next node and the entry
-            // under it becomes the top - read from LDS, but needed only when this lane pops the next time
-            cur = h1 ? child : (h2 ? child : tos);
-            tos = h1 ? (h2 ? far_ref : tos) : tos;
-            sp = h1 ? (h2 ? pushed : sp) : sp;
-            if (!(h1 | h2)) {
-                uint32_t* const below = sp - kWfBlock;
-                sp = below < stack_floor ? stack_floor : below;
-                tos = *sp;
-            }
-            if (cur != REF_NONE && (cur & REF_LEAF)) {  // (the triangle range of a lane that takes node steps is free)
-                bool leaf = true;
-                if (kCull && culled) {
-                    p_tri += (cur >> REF_COUNT_SHIFT) & 7u;
-                    if (STATS) culled_items += (cur >> REF_COUNT_SHIFT) & 7u;
-                    cur = tos;
-                    uint32_t* const under = sp - kWfBlock;
-                    sp = under < stack_floor ? stack_floor : under;
-                    tos = *sp;
-                    leaf = cur != REF_NONE && (cur & REF_LEAF);  // (a popped leaf carries no mark: its triangles are tested)
-                }
-                if (leaf) {
-                    decode_leaf(sc, cur, tri_i, tri_end);
-                    cur = tos;
-                    uint32_t* const under = sp - kWfBlock;
-                    sp = under < stack_floor ? stack_floor : under;
-                    tos = *sp;
-                }
-            }
-            return;
-        }
-        sp[kWfBlock] = fwd ? ref2 : ref1;
+        const uint32_t far_ref = fwd ? n.ref2 : n.ref1;
+        sp[kWfBlock] = far_ref;
         uint32_t* const pushed = sp + kWfBlock;
+        const uint32_t child = fwd ? (h1 ? n.ref1 : n.ref2) : (h2 ? n.ref2 : n.ref1);  // near child if it was hit, else the far one
+        // both hit: the far child becomes the top; one hit: nothing moves; none: the step pops
+        cur = h1 ? child : (h2 ? child : cur);
+        if (kTos) tos = h1 ? (h2 ? far_ref : tos) : tos;
         sp = h1 ? (h2 ? pushed : sp) : sp;
-        const uint32_t popped = *sp;
-        uint32_t* const below = sp - kWfBlock;
-        uint32_t* const under = below < stack_floor ? stack_floor : below;
-        const uint32_t child = fwd ? (h1 ? ref1 : ref2) : (h2 ? ref2 : ref1);  // near child if it was hit, else the far one
-        cur = h1 ? child : (h2 ? child : popped);
-        sp = h1 ? sp : (h2 ? sp : under);
-        if (cur != REF_NONE && (cur & REF_LEAF)) {  // (the triangle range of a lane that takes node steps is free)
-            bool leaf = true;
-            if (kCull && culled) {
-                p_tri += (cur >> REF_COUNT_SHIFT) & 7u;
-                if (STATS) culled_items += (cur >> REF_COUNT_SHIFT) & 7u;
-                cur = *sp;
-                uint32_t* const under = sp - kWfBlock;
-                sp = under < stack_floor ? stack_floor : under;
-                leaf = cur != REF_NONE && (cur & REF_LEAF);  // (a popped leaf carries no mark: its triangles are tested)
-            }
-            if (leaf) {
-                decode_leaf(sc, cur, tri_i, tri_end);
-                cur = *sp;
-                uint32_t* const under = sp - kWfBlock;
-                sp = under < stack_floor ? stack_floor : under;
-            }
-        }
+        if (!(h1 | h2)) pop();
+        if (ref_is_leaf(cur)) enter_leaf(culled);  // (the triangle range of a lane that takes node steps is free)
     };
 
     // Scheduling of path logic: a fixed lane threshold cannot serve both a 21-node scene (queries of ~10 steps,
@@ -1261,7 +1217,7 @@ static void launch_instance(const WavefrontLaunch& w)
                        w.n_iterations, w.iteration_stride, w.n_jobs, w.job_counter, w.lv, w.stage, w.stage_stats);
 }
 
-// Which instantiation a launch gets - the twelve that exist.  The common case (no statistics, no adaptive sampling, records
+// Which instantiation a launch gets, of those that exist.  The common case (no statistics, no adaptive sampling, records
 // that cannot yield NaN distances) pays for none of them; the statistics and SUPER_SAMPLING builds always carry the NaN check
 // (two instructions per accepted triangle).  `plain`: see the kernel's PLAIN (it implies precomputed records).  `narrow`: the
 // two production instantiations in workgroups of kWfBlockNarrow lanes (deep trees).
@@ -1270,8 +1226,8 @@ static LaunchInstance instance_for(const DScene& sc, bool scheduler_stats, bool 
 {
     constexpr int kWide = PTMI_DEV_NS::kWfBlock, kNarrow = PTMI_DEV_NS::kWfBlockNarrow;
     const bool pre = sc.tris_precomputed != 0;
-    //                                               STATS  PRE    SS     PLAIN  NANSAFE
     const bool cull = pre && sc.leaf_cull != 0u;  // (the host clears leaf_cull where culling is off or cannot pay: ptmi_scene_memory.cpp)
+    //                                               STATS  PRE    SS     PLAIN  NANSAFE
     if (sc.super_sampling) return pre ? launch_instance<true, true, true, false, true, kWide, true> : launch_instance<true, false, true, false, true, kWide>;
     if (scheduler_stats) return pre ? launch_instance<true, true, false, false, true, kWide, true> : launch_instance<true, false, false, false, true, kWide>;
     if (sc.nan_safe) {

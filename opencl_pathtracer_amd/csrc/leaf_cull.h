@@ -22,13 +22,6 @@
 
 #include "ptmi_internal.h"
 
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define PTMI_CULL_HD __host__ __device__ __forceinline__
-#else
-#define PTMI_CULL_HD inline
-#endif
-
 namespace ptmi_cull {
 
 // ---- the rule -------------------------------------------------------------------------------------------------------------
@@ -40,11 +33,11 @@ constexpr float kRel = 1.001f, kAbs = 0.01f, kMaxOrigin = 0x1p+41f;
 // what the certificate may grant: with eta = (kRel - 1) / 2,  (1 - kappa)^2 (1 - eta) kRel >= 1 + 40u  and  eps_abs^2 / eta <= 0.99 kAbs
 constexpr double kKappaMax = 0x1p-13, kEpsAbsMax = 2.0e-3;
 
-// DNode::pad of an inner record: the children that are cullable leaves, and "this record's bits were computed" (a refit
+// DNode::cull of an inner record: the children that are cullable leaves, and "this record's bits were computed" (a refit
 // recomputes the bits of the records that carry them and leaves the others alone: scene_refit_common.h)
 constexpr uint32_t kCullChild1 = 1u, kCullChild2 = 2u, kCullComputed = 4u;
 
-PTMI_CULL_HD float box_distance2(const float lo[3], const float hi[3], float ox, float oy, float oz)
+PTMI_HD float box_distance2(const float lo[3], const float hi[3], float ox, float oy, float oz)
 {
     // max(lo - o, o - hi, 0) per axis: at most one of the two differences is positive (lo <= hi)
     const float dx = fmaxf(fmaxf(lo[0] - ox, ox - hi[0]), 0.0f);
@@ -58,16 +51,16 @@ PTMI_CULL_HD float box_distance2(const float lo[3], const float hi[3], float ox,
 // of the test is N.xyz . x + x.w = d, and it is the triangle's plane of xyz exactly when the computed point has the vertices'
 // w.  Points carry w = 1 and directions w = 0 everywhere but behind a GLASS / WATER reflection (Numerics); a ray of
 // another kind never culls (the certificate wants S1.w = 1 of a triangle whose N.w is not zero).
-PTMI_CULL_HD bool ray_may_cull(float ox, float oy, float oz, float ow, float dw)
+PTMI_HD bool ray_may_cull(float ox, float oy, float oz, float ow, float dw)
 {
     return fabsf(ox) + fabsf(oy) + fabsf(oz) <= kMaxOrigin && ow == 1.0f && dw == 0.0f;  // (all false for a NaN)
 }
 // ... and the part that is the box's
-PTMI_CULL_HD bool box_is_beyond(float d2, float limit)
+PTMI_HD bool box_is_beyond(float d2, float limit)
 {
     return d2 > fmaf(limit, kRel, kAbs);  // (false for a NaN)
 }
-PTMI_CULL_HD bool leaf_cull_rule(float d2, float limit, float ox, float oy, float oz, float ow, float dw)
+PTMI_HD bool leaf_cull_rule(float d2, float limit, float ox, float oy, float oz, float ow, float dw)
 {
     return box_is_beyond(d2, limit) && ray_may_cull(ox, oy, oz, ow, dw);
 }
@@ -91,7 +84,7 @@ PTMI_CULL_HD bool leaf_cull_rule(float d2, float limit, float ox, float oy, floa
 //     with sigma = E + 0.025 (E_s + E_t) + 1.25 dk, a triangle whose corners lie within
 //     max(sigma_s |u| + sigma_t |v|, (sigma_s + 2 sigma_t) |u| + sigma_t |v|, sigma_s |u| + (2 sigma_s + sigma_t) |v|)
 //     of the corners of the true one, whose vertices lie inside the box.
-PTMI_CULL_HD bool triangle_slack(const ptmi_triangle& t, const float lo[3], const float hi[3], double* eps_abs, double* kappa)
+PTMI_HD bool triangle_slack(const ptmi_triangle& t, const float lo[3], const float hi[3], double* eps_abs, double* kappa)
 {
     const double u24 = 0x1p-24;
     const float S[3][3] = {{t.s1.x, t.s1.y, t.s1.z}, {t.s2.x, t.s2.y, t.s2.z}, {t.s3.x, t.s3.y, t.s3.z}};
@@ -149,7 +142,7 @@ PTMI_CULL_HD bool triangle_slack(const ptmi_triangle& t, const float lo[3], cons
     return std::isfinite(*kappa) && std::isfinite(*eps_abs);
 }
 
-PTMI_CULL_HD bool triangle_certified(const ptmi_triangle& t, const float lo[3], const float hi[3])
+PTMI_HD bool triangle_certified(const ptmi_triangle& t, const float lo[3], const float hi[3])
 {
     double eps_abs, kappa;
     return triangle_slack(t, lo, hi, &eps_abs, &kappa) && eps_abs <= kEpsAbsMax && kappa <= kKappaMax;
@@ -158,20 +151,20 @@ PTMI_CULL_HD bool triangle_certified(const ptmi_triangle& t, const float lo[3], 
 // Is the child behind `ref`, with the box the record holds for it, a leaf the kernel may cull?  An ordinary leaf (not flagged
 // empty, one to six triangles in the reference itself) whose triangles are all certified.  tri_at(k): its k-th triangle.
 template <class TriAt>
-PTMI_CULL_HD bool leaf_is_cullable(uint32_t ref, const float lo[3], const float hi[3], TriAt tri_at)
+PTMI_HD bool leaf_is_cullable(uint32_t ref, const float lo[3], const float hi[3], TriAt tri_at)
 {
     using namespace ptmi_internal;
     if (!(ref & REF_LEAF) || (ref & REF_EMPTY)) return false;
-    const uint32_t count = (ref >> REF_COUNT_SHIFT) & 7u;
+    const uint32_t count = ref_leaf_count(ref);
     if (count == 0u || count == REF_COUNT_BIG) return false;
     for (uint32_t k = 0; k < count; k++)
         if (!triangle_certified(tri_at(k), lo, hi)) return false;
     return true;
 }
 
-// DNode::pad of inner record `d`, from the boxes and references it holds; tri_of_record(r): the triangle behind leaf record r.
+// DNode::cull of inner record `d`, from the boxes and references it holds; tri_of_record(r): the triangle behind leaf record r.
 template <class TriOfRecord>
-PTMI_CULL_HD uint32_t record_cull_bits(const ptmi_internal::DNode& d, TriOfRecord tri_of_record)
+PTMI_HD uint32_t record_cull_bits(const ptmi_internal::DNode& d, TriOfRecord tri_of_record)
 {
     const uint32_t start1 = d.ref1 & ptmi_internal::REF_INDEX_MASK_LEAF, start2 = d.ref2 & ptmi_internal::REF_INDEX_MASK_LEAF;
     uint32_t bits = kCullComputed;

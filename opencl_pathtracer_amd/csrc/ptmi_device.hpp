@@ -282,6 +282,17 @@ __device__ __forceinline__ bool ray_slabs_are_ordered(const Ray& r)
            (__builtin_fabsf(r.o.x) < INFINITY) & (__builtin_fabsf(r.o.y) < INFINITY) & (__builtin_fabsf(r.o.z) < INFINITY);
 }
 
+// An inner record (DNode, ptmi_internal.h) as a traversal step sees it, from the four quads it is loaded as.
+struct NodeView {
+    float lo1[3], hi1[3], lo2[3], hi2[3];
+    uint32_t ref1, ref2, axis, cull;
+};
+__device__ __forceinline__ NodeView node_view(const float4 a, const float4 b, const float4 c, const float4 d)
+{
+    return NodeView{{a.x, a.y, a.z}, {a.w, b.x, b.y}, {b.z, b.w, c.x}, {c.y, c.z, c.w},
+                    __float_as_uint(d.x), __float_as_uint(d.y), __float_as_uint(d.z), __float_as_uint(d.w)};
+}
+
 struct Hit {
     V4 point;       // intersectionPoint
     float s, t;

@@ -6,6 +6,7 @@
 #include <string>
 
 #include "ptmi.h"
+#include "ptmi_hd.h"
 #ifdef __HIPCC__  // (host code that is built without HIP reads this header too: it gets everything but launch_status)
 #include <hip/hip_runtime.h>
 #endif
@@ -58,12 +59,35 @@ constexpr uint32_t REF_NONE = 0xFFFFFFFFu;  // traversal finished (never a valid
 constexpr uint32_t REF_IDLE = 0xFFFFFFFEu;  // wavefront kernel: the lane has no path in flight
 constexpr uint32_t REF_DEAD = 0xFFFFFFFDu;  // wavefront kernel: the job queue is empty, the lane is done
 
+struct DBigLeaf {
+    uint32_t start, count;
+};
+
+// `ref` is a leaf's reference and not the end of a query (REF_NONE carries the leaf bit too)
+PTMI_HD bool ref_is_leaf(uint32_t ref) { return ref != REF_NONE && (ref & REF_LEAF); }
+// the count field of a leaf's reference: 0..6 triangles, or REF_COUNT_BIG
+PTMI_HD uint32_t ref_leaf_count(uint32_t ref) { return (ref >> REF_COUNT_SHIFT) & 7u; }
+// the triangle records a leaf's reference means: [*start, *start + *count) of the one record array
+PTMI_HD void leaf_range(uint32_t ref, const DBigLeaf* big_leaves, uint32_t* start, uint32_t* count)
+{
+    *count = ref_leaf_count(ref);
+    *start = ref & REF_INDEX_MASK_LEAF;
+    if (*count == REF_COUNT_BIG) {
+        const DBigLeaf bl = big_leaves[*start];
+        *start = bl.start;
+        *count = bl.count;
+    }
+}
+
 struct DNode {
     float lo1[3], hi1[3];  // son1Id's trianglesAABB pMin/pMax xyz
     float lo2[3], hi2[3];  // son2Id's
     uint32_t ref1, ref2;
     uint32_t axis;  // cutAxis
-    uint32_t pad;
+    union {
+        uint32_t cull;  // which children are leaves the wavefront kernel may count untested (leaf_cull.h: kCullChild1 ...); 0 = none
+        uint32_t pad;   // the name this word had while it was padding: sources written against it still compile
+    };
 };
 static_assert(sizeof(DNode) == 64, "DNode");
 
@@ -99,10 +123,6 @@ struct DMat {
     uint32_t is_simple_color;
 };
 static_assert(sizeof(DMat) == 32, "DMat");
-
-struct DBigLeaf {
-    uint32_t start, count;
-};
 
 // calls one launch may render AHEAD for (ptmi_api.cpp: render_on_device): the launch keeps the totals of ptmi_get_counters per
 // call, in as many blocks of C_COUNT words
@@ -170,7 +190,7 @@ struct DScene {
     uint32_t boxes_ordered;    // every non-empty child box is finite with pMin <= pMax (see box_hit_ordered)
     uint32_t russian_roulette; // PTMI_FLAG_RUSSIAN_ROULETTE
     uint32_t source_seed;      // PTMI_FLAG_SOURCE_SEED
-    uint32_t leaf_cull;        // mask of the DNode::pad bits the wavefront kernel honours (leaf_cull.h): 3, or 0 = culling is off
+    uint32_t leaf_cull;        // mask of the DNode::cull bits the wavefront kernel honours (leaf_cull.h): 3, or 0 = culling is off
 };
 
 // The integrator's device code exists once per ARITHMETIC MODE (ptmi_device.hpp: strict / the reference's default OpenCL

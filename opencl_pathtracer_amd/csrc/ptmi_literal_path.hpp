@@ -64,43 +64,26 @@ __device__ __forceinline__ void add_random_sample(const DScene& sc, uint32_t off
 // (dir[cutAxis] > 0 ? son1 : son2) is tested first and descended first, the
 // other is pushed; leaf triangles in ascending index with the distance limit
 // updated between tests.
-template <bool ANY_HIT, bool PRE>
-__device__ __forceinline__ bool traverse(const DScene& sc, const Ray& r, float limit, Hit& hit, PathCounters& pc,
-                                         uint32_t* __restrict__ stack)
+// `stack`: the lane's column of a [level][lane] array, kBlock words from one level to the next.
+// ORDERED: the 5-comparison box test, for a ray and a scene that allow it (box_hit_ordered: the caller asks).
+// Returns whether a triangle was accepted; hit.tri = its RECORD index, `limit` = the squared distance it left.
+template <bool ANY_HIT, bool PRE, bool ORDERED>
+__device__ __forceinline__ bool walk(const DScene& sc, const Ray& r, float& limit, Hit& hit, PathCounters& pc,
+                                     uint32_t* __restrict__ stack)
 {
-    // A closest-hit query of a ray whose direction is NaN in every component (the scattered ray of a hit on a zero-area
-    // triangle, whose normal is 0/0): every comparison of the box test and of the triangle test is false, so every non-empty
-    // box is "hit" and every triangle accepted - the query walks the WHOLE tree in one fixed order and keeps its last triangle
-    // (seconds for one path on a million triangles, ten times per path).  The upload has walked it once
-    // (scene_layout.cpp: nan_walk_*): the counts are added and the LAST triangle's test is made for real, which leaves the
-    // very record, bit for bit, that the walk would leave.
-    if (!ANY_HIT && sc.nan_walk_box_tests != 0xFFFFFFFFu && (r.d.x != r.d.x) & (r.d.y != r.d.y) & (r.d.z != r.d.z)) {
-        pc.bbx += sc.nan_walk_box_tests;
-        pc.tri += sc.nan_walk_tri_tests;
-        if (sc.nan_walk_last_tri == 0xFFFFFFFFu) return false;
-        const float4* q4 = reinterpret_cast<const float4*>(&sc.tris[sc.nan_walk_last_tri]);
-        const bool accepted = tri_hit_record<PRE>(q4[0], q4[1], q4[2], q4[3], r, limit, hit);
-        hit.tri = sc.nan_walk_last_tri;
-        return accepted;
-    }
     bool found = false;
     int top = 0;
     uint32_t cur = sc.root_ref;
     for (;;) {
         if (cur & REF_LEAF) {
-            uint32_t count = (cur >> REF_COUNT_SHIFT) & 7u;
-            uint32_t start = cur & REF_INDEX_MASK_LEAF;
-            if (count == REF_COUNT_BIG) {
-                const DBigLeaf bl = sc.big_leaves[start];
-                start = bl.start;
-                count = bl.count;
-            }
+            uint32_t start, count;
+            leaf_range(cur, sc.big_leaves, &start, &count);
             for (uint32_t i = start; i < start + count; i++) {
                 pc.tri++;
                 const float4* q4 = reinterpret_cast<const float4*>(&sc.tris[i]);
                 if (tri_hit_record<PRE>(q4[0], q4[1], q4[2], q4[3], r, limit, hit)) {
-                    if (ANY_HIT) return true;
                     hit.tri = i;
+                    if (ANY_HIT) return true;
                     found = true;
                 }
             }
@@ -108,16 +91,13 @@ __device__ __forceinline__ bool traverse(const DScene& sc, const Ray& r, float l
             cur = stack[(--top) * kBlock];
         } else {
             const float4* np = reinterpret_cast<const float4*>(&sc.nodes[cur & REF_INDEX_MASK_INNER]);
-            const float4 a = np[0], b = np[1], c = np[2], d = np[3];
-            const float lo1[3] = {a.x, a.y, a.z}, hi1[3] = {a.w, b.x, b.y};
-            const float lo2[3] = {b.z, b.w, c.x}, hi2[3] = {c.y, c.z, c.w};
-            const uint32_t ref1 = __float_as_uint(d.x), ref2 = __float_as_uint(d.y), axis = __float_as_uint(d.z);
-            const float da = axis == 0 ? r.d.x : (axis == 1 ? r.d.y : r.d.z);
+            const NodeView n = node_view(np[0], np[1], np[2], np[3]);
+            const float da = n.axis == 0 ? r.d.x : (n.axis == 1 ? r.d.y : r.d.z);
             const bool fwd = da > 0;
-            const bool h1 = box_hit(lo1, hi1, (ref1 & REF_EMPTY) != 0, r, limit);
-            const bool h2 = box_hit(lo2, hi2, (ref2 & REF_EMPTY) != 0, r, limit);
+            const bool h1 = ORDERED ? box_hit_ordered(n.lo1, n.hi1, r, limit) : box_hit(n.lo1, n.hi1, (n.ref1 & REF_EMPTY) != 0, r, limit);
+            const bool h2 = ORDERED ? box_hit_ordered(n.lo2, n.hi2, r, limit) : box_hit(n.lo2, n.hi2, (n.ref2 & REF_EMPTY) != 0, r, limit);
             pc.bbx += 2;
-            const uint32_t near_ref = fwd ? ref1 : ref2, far_ref = fwd ? ref2 : ref1;
+            const uint32_t near_ref = fwd ? n.ref1 : n.ref2, far_ref = fwd ? n.ref2 : n.ref1;
             const bool near_hit = fwd ? h1 : h2, far_hit = fwd ? h2 : h1;
             if (near_hit) {
                 if (far_hit) stack[(top++) * kBlock] = far_ref;
@@ -131,6 +111,39 @@ __device__ __forceinline__ bool traverse(const DScene& sc, const Ray& r, float l
         }
     }
     return found;
+}
+
+// A closest-hit query of a ray whose direction is NaN in every component (the scattered ray of a hit on a zero-area
+// triangle, whose normal is 0/0): every comparison of the box test and of the triangle test is false, so every non-empty
+// box is "hit" and every triangle accepted - the query walks the WHOLE tree in one fixed order and keeps its last triangle
+// (seconds for one path on a million triangles, ten times per path).  The upload has walked it once
+// (scene_layout.cpp: nan_walk_*): the counts are added and the LAST triangle's test is made for real, which leaves the
+// very record, bit for bit, that the walk would leave.
+template <bool ANY_HIT>
+__device__ __forceinline__ bool nan_walk_applies(const DScene& sc, const Ray& r)
+{
+    return !ANY_HIT && sc.nan_walk_box_tests != 0xFFFFFFFFu && (r.d.x != r.d.x) & (r.d.y != r.d.y) & (r.d.z != r.d.z);
+}
+template <bool PRE>
+__device__ __forceinline__ bool nan_walk(const DScene& sc, const Ray& r, float& limit, Hit& hit, PathCounters& pc)
+{
+    pc.bbx += sc.nan_walk_box_tests;
+    pc.tri += sc.nan_walk_tri_tests;
+    if (sc.nan_walk_last_tri == 0xFFFFFFFFu) return false;
+    const float4* q4 = reinterpret_cast<const float4*>(&sc.tris[sc.nan_walk_last_tri]);
+    const bool accepted = tri_hit_record<PRE>(q4[0], q4[1], q4[2], q4[3], r, limit, hit);
+    hit.tri = sc.nan_walk_last_tri;
+    return accepted;
+}
+
+// One query of a path: the shortcut, else the walk with the LITERAL box test - which is what makes these loops the fallback
+// for everything the fast forms cannot express.
+template <bool ANY_HIT, bool PRE>
+__device__ __forceinline__ bool traverse(const DScene& sc, const Ray& r, float limit, Hit& hit, PathCounters& pc,
+                                         uint32_t* __restrict__ stack)
+{
+    if (nan_walk_applies<ANY_HIT>(sc, r)) return nan_walk<PRE>(sc, r, limit, hit, pc);
+    return walk<ANY_HIT, PRE, false>(sc, r, limit, hit, pc, stack);
 }
 
 // One path = one Kernel_Main work-item (FullKernel.cl:1180-1331) up to the

@@ -2,11 +2,11 @@
 //
 // One query = the reference's BVH_IntersectRay (FullKernel.cl:620-702, PTMI_QUERY_CLOSEST) or BVH_IntersectShadowRay
 // (:705-783, PTMI_QUERY_ANY) on a ray made by Ray3D_Create (header.cl:276-295), bit for bit in the arithmetic of the build
-// (ptmi_device.hpp).  The loop below is `traverse` of ptmi_literal_path.hpp - same visit order, same comparisons - with three
-// differences that no result can show:
+// (ptmi_device.hpp).  The queries are `walk` and `nan_walk` of ptmi_literal_path.hpp, the loops the integrator's literal path
+// runs.  What is this kernel's own:
 //   * the LDS traversal stack is sized at launch by the depth of the uploaded tree, not by PTMI_BVH_MAX_DEPTH;
-//   * a ray whose slabs are ordered takes the 5-comparison box test (box_hit_ordered), chosen once per ray;
-//   * the any-hit form reports the record it accepted.
+//   * a ray whose slabs are ordered takes the walk with the 5-comparison box test (box_hit_ordered), chosen once per ray;
+//   * the grid-stride loop over the caller's rays, and the ptmi_ray_hit it writes for each.
 // The kernel only READS scene memory: no accumulator, histogram or counter of the context is touched.
 #include <hip/hip_runtime.h>
 
@@ -17,66 +17,7 @@
 namespace PTMI_DEV_NS {
 
 constexpr int kQueryBlock = 256;  // 4 waves; a lane keeps one ray and one column of the stack
-
-struct QueryCounts {
-    uint32_t bbx, tri;
-};
-
-// `stack`: the lane's column of the [level][lane] array, kQueryBlock words from one level to the next.
-// Returns whether a triangle was accepted; hit.tri = its RECORD index, `limit` = the squared distance it left.
-template <bool ANY_HIT, bool PRE, bool ORDERED>
-__device__ __forceinline__ bool query_walk(const DScene& sc, const Ray& r, float& limit, Hit& hit, QueryCounts& pc,
-                                           uint32_t* __restrict__ stack)
-{
-    bool found = false;
-    int top = 0;
-    uint32_t cur = sc.root_ref;
-    for (;;) {
-        if (cur & REF_LEAF) {
-            uint32_t count = (cur >> REF_COUNT_SHIFT) & 7u;
-            uint32_t start = cur & REF_INDEX_MASK_LEAF;
-            if (count == REF_COUNT_BIG) {
-                const DBigLeaf bl = sc.big_leaves[start];
-                start = bl.start;
-                count = bl.count;
-            }
-            for (uint32_t i = start; i < start + count; i++) {
-                pc.tri++;
-                const float4* q4 = reinterpret_cast<const float4*>(&sc.tris[i]);
-                if (tri_hit_record<PRE>(q4[0], q4[1], q4[2], q4[3], r, limit, hit)) {
-                    hit.tri = i;
-                    if (ANY_HIT) return true;
-                    found = true;
-                }
-            }
-            if (top == 0) break;
-            cur = stack[(--top) * kQueryBlock];
-        } else {
-            const float4* np = reinterpret_cast<const float4*>(&sc.nodes[cur & REF_INDEX_MASK_INNER]);
-            const float4 a = np[0], b = np[1], c = np[2], d = np[3];
-            const float lo1[3] = {a.x, a.y, a.z}, hi1[3] = {a.w, b.x, b.y};
-            const float lo2[3] = {b.z, b.w, c.x}, hi2[3] = {c.y, c.z, c.w};
-            const uint32_t ref1 = __float_as_uint(d.x), ref2 = __float_as_uint(d.y), axis = __float_as_uint(d.z);
-            const float da = axis == 0 ? r.d.x : (axis == 1 ? r.d.y : r.d.z);
-            const bool fwd = da > 0;
-            const bool h1 = ORDERED ? box_hit_ordered(lo1, hi1, r, limit) : box_hit(lo1, hi1, (ref1 & REF_EMPTY) != 0, r, limit);
-            const bool h2 = ORDERED ? box_hit_ordered(lo2, hi2, r, limit) : box_hit(lo2, hi2, (ref2 & REF_EMPTY) != 0, r, limit);
-            pc.bbx += 2;
-            const uint32_t near_ref = fwd ? ref1 : ref2, far_ref = fwd ? ref2 : ref1;
-            const bool near_hit = fwd ? h1 : h2, far_hit = fwd ? h2 : h1;
-            if (near_hit) {
-                if (far_hit) stack[(top++) * kQueryBlock] = far_ref;
-                cur = near_ref;
-            } else if (far_hit) {
-                cur = far_ref;
-            } else {
-                if (top == 0) break;
-                cur = stack[(--top) * kQueryBlock];
-            }
-        }
-    }
-    return found;
-}
+static_assert(kQueryBlock == kBlock, "walk() steps kBlock words from one stack level to the next");
 
 // rays: 3 x 16 bytes each (ptmi_ray), hits: 3 x 16 bytes each (ptmi_ray_hit)
 template <bool ANY_HIT, bool PRE>
@@ -94,24 +35,15 @@ __global__ void __launch_bounds__(kQueryBlock) query_rays_kernel(const DScene sc
         float limit = in_l.x;
         Hit hit;
         hit.tri = 0; hit.s = 0; hit.t = 0; hit.front = false; hit.point = v4(0, 0, 0, 0);
-        QueryCounts pc{0, 0};
+        PathCounters pc{0, 0};
         bool found;
-        if (!ANY_HIT && sc.nan_walk_box_tests != 0xFFFFFFFFu && (r.d.x != r.d.x) & (r.d.y != r.d.y) & (r.d.z != r.d.z)) {
-            // the closest-hit walk of an all-NaN direction visits the whole tree and keeps its last triangle: `traverse` and
-            // scene_layout.cpp (nan_walk_*) explain; the counts of that walk, and the last triangle's test made for real
-            pc.bbx = sc.nan_walk_box_tests;
-            pc.tri = sc.nan_walk_tri_tests;
-            found = false;
-            if (sc.nan_walk_last_tri != 0xFFFFFFFFu) {
-                const float4* q4 = reinterpret_cast<const float4*>(&sc.tris[sc.nan_walk_last_tri]);
-                found = tri_hit_record<PRE>(q4[0], q4[1], q4[2], q4[3], r, limit, hit);
-                hit.tri = sc.nan_walk_last_tri;
-            }
+        if (nan_walk_applies<ANY_HIT>(sc, r)) {
+            found = nan_walk<PRE>(sc, r, limit, hit, pc);
         } else if (sc.boxes_ordered && ray_slabs_are_ordered(r) && !(limit < 0)) {
             // (box_hit_ordered takes the distance limit as never negative: a caller's negative one keeps the literal form)
-            found = query_walk<ANY_HIT, PRE, true>(sc, r, limit, hit, pc, stack);
+            found = walk<ANY_HIT, PRE, true>(sc, r, limit, hit, pc, stack);
         } else {
-            found = query_walk<ANY_HIT, PRE, false>(sc, r, limit, hit, pc, stack);
+            found = walk<ANY_HIT, PRE, false>(sc, r, limit, hit, pc, stack);
         }
         float4 out_p = make_float4(0, 0, 0, 0), out_q = make_float4(0, 0, 0, __uint_as_float(0xFFFFFFFFu));
         uint32_t front = 0;

@@ -253,10 +253,10 @@ int build_layout(const ptmi_config& cfg, const ptmi_scene* sc, Relayout& out, st
         d.hi1[0] = b1.p_max.x; d.hi1[1] = b1.p_max.y; d.hi1[2] = b1.p_max.z;
         d.lo2[0] = b2.p_min.x; d.lo2[1] = b2.p_min.y; d.lo2[2] = b2.p_min.z;
         d.hi2[0] = b2.p_max.x; d.hi2[1] = b2.p_max.y; d.hi2[2] = b2.p_max.z;
-        d.ref1 = r1; d.ref2 = r2; d.axis = n.cut_axis; d.pad = 0;  // inner children: index patched in when they are emitted
+        d.ref1 = r1; d.ref2 = r2; d.axis = n.cut_axis; d.cull = 0;  // inner children: index patched in when they are emitted
         // which of the two are leaves no triangle of which can be accepted from beyond the limit (leaf_cull.h)
-        if (cull_bits) d.pad = ptmi_cull::record_cull_bits(d, [&](uint32_t r) -> const ptmi_triangle& { return sc->triangulation[out.tri_ids[r]]; });
-        out.cullable_leaves += ((d.pad & ptmi_cull::kCullChild1) ? 1u : 0u) + ((d.pad & ptmi_cull::kCullChild2) ? 1u : 0u);
+        if (cull_bits) d.cull = ptmi_cull::record_cull_bits(d, [&](uint32_t r) -> const ptmi_triangle& { return sc->triangulation[out.tri_ids[r]]; });
+        out.cullable_leaves += ((d.cull & ptmi_cull::kCullChild1) ? 1u : 0u) + ((d.cull & ptmi_cull::kCullChild2) ? 1u : 0u);
         // the short slab test (box_hit_ordered) needs finite, ordered boxes; anything else keeps the literal form
         for (int k = 0; k < 3; k++) {
             if (!(r1 & REF_EMPTY) && !(std::isfinite(d.lo1[k]) && std::isfinite(d.hi1[k]) && d.lo1[k] <= d.hi1[k])) out.boxes_ordered = false;
@@ -290,8 +290,8 @@ int build_layout(const ptmi_config& cfg, const ptmi_scene* sc, Relayout& out, st
         uint32_t cur = out.root_ref;
         for (;;) {
             if (cur & REF_LEAF) {
-                uint32_t count = (cur >> REF_COUNT_SHIFT) & 7u, start = cur & REF_INDEX_MASK_LEAF;
-                if (count == REF_COUNT_BIG) { const DBigLeaf& bl = out.big_leaves[start]; start = bl.start; count = bl.count; }
+                uint32_t start, count;
+                leaf_range(cur, out.big_leaves.data(), &start, &count);
                 tris += count;
                 if (count) last = start + count - 1;
                 if (stack.empty()) break;

@@ -129,8 +129,8 @@ PTMI_HD void refit_child_box(uint32_t ref, const DNode* nodes, const DBigLeaf* b
     using namespace ptmi_internal;
     PBox b = ptmi_bvh::pbox_empty();
     if (ref & REF_LEAF) {
-        uint32_t count = (ref >> REF_COUNT_SHIFT) & 7u, start = ref & REF_INDEX_MASK_LEAF;
-        if (count == REF_COUNT_BIG) { const DBigLeaf bl = big_leaves[start]; start = bl.start; count = bl.count; }
+        uint32_t start, count;
+        leaf_range(ref, big_leaves, &start, &count);
         const uint32_t* ids = tri_ids + start;
         for (uint32_t k = 0; k < count; k++) {
             const ptmi_bounding_box& a = tris[ids[k]].aabb;
@@ -154,8 +154,8 @@ PTMI_HD void refit_record(DNode* d, const DNode* nodes, const DBigLeaf* big_leav
 {
     if (!(d->ref1 & ptmi_internal::REF_EMPTY)) refit_child_box(d->ref1, nodes, big_leaves, tri_ids, tris, d->lo1, d->hi1);
     if (!(d->ref2 & ptmi_internal::REF_EMPTY)) refit_child_box(d->ref2, nodes, big_leaves, tri_ids, tris, d->lo2, d->hi2);
-    if (d->pad & ptmi_cull::kCullComputed)
-        d->pad = ptmi_cull::record_cull_bits(*d, [&](uint32_t r) -> const ptmi_triangle& { return tris[tri_ids[r]]; });
+    if (d->cull & ptmi_cull::kCullComputed)
+        d->cull = ptmi_cull::record_cull_bits(*d, [&](uint32_t r) -> const ptmi_triangle& { return tris[tri_ids[r]]; });
 }
 
 }  // namespace ptmi_refit

@@ -52,7 +52,7 @@ int build_refit_schedule(const DNode* records, const uint32_t* tri_ids, uint32_t
     out.first.clear();
     // the triangles behind a leaf reference: 0, or their number; -1 if anything the kernels would index is out of range
     auto leaf_count = [&](uint32_t ref) -> long {
-        uint32_t count = (ref >> REF_COUNT_SHIFT) & 7u, start = ref & REF_INDEX_MASK_LEAF;
+        uint32_t count = ref_leaf_count(ref), start = ref & REF_INDEX_MASK_LEAF;
         if (count == REF_COUNT_BIG) {
             if (start >= n_big_leaves) return -1;
             count = big_leaves[start].count;

@@ -65,8 +65,8 @@ int cull_walk(const DNode* recs, const uint32_t* tri_ids, const DBigLeaf* big_le
     while (!finished) {
         bool pop = false;
         if (cur & REF_LEAF) {
-            uint32_t count = (cur >> REF_COUNT_SHIFT) & 7u, start = cur & REF_INDEX_MASK_LEAF;
-            if (count == REF_COUNT_BIG) { const DBigLeaf bl = big_leaves[start]; start = bl.start; count = bl.count; }
+            uint32_t start, count;
+            leaf_range(cur, big_leaves, &start, &count);
             out[direct ? 4 : 5]++;
             if (marked) { out[8]++; out[9] += count; }
             if (marked && mode >= 2) {
@@ -92,8 +92,8 @@ int cull_walk(const DNode* recs, const uint32_t* tri_ids, const DBigLeaf* big_le
             const bool fwd = d[n.axis] > 0;
             auto cullable = [&](bool one) {
                 const uint32_t r = one ? n.ref1 : n.ref2;
-                if (mode == 3) return (r & REF_LEAF) && !(r & REF_EMPTY) && ((r >> REF_COUNT_SHIFT) & 7u) != REF_COUNT_BIG;
-                return (n.pad & (one ? ptmi_cull::kCullChild1 : ptmi_cull::kCullChild2)) != 0u;
+                if (mode == 3) return (r & REF_LEAF) && !(r & REF_EMPTY) && ref_leaf_count(r) != REF_COUNT_BIG;
+                return (n.cull & (one ? ptmi_cull::kCullChild1 : ptmi_cull::kCullChild2)) != 0u;
             };
             if (!h1 && !h2) {
                 pop = true;
@@ -107,7 +107,7 @@ int cull_walk(const DNode* recs, const uint32_t* tri_ids, const DBigLeaf* big_le
                 }
                 cur = first ? n.ref1 : n.ref2; direct = true; marked = false;
                 if (cur & REF_LEAF) {
-                    const uint32_t count = (cur >> REF_COUNT_SHIFT) & 7u;
+                    const uint32_t count = ref_leaf_count(cur);
                     if (!cullable(first)) out[11]++;
                     if (mode >= 1 && cullable(first) && rule(first ? n.lo1 : n.lo2, first ? n.hi1 : n.hi2)) {
                         out[4]++; out[6]++; out[7] += count; out[3] += count;
@@ -129,7 +129,7 @@ int cull_walk(const DNode* recs, const uint32_t* tri_ids, const DBigLeaf* big_le
 }
 
 // build_layout's cull bits for `scene`: out[0] = inner records, out[1] = of them with kCullComputed, out[2] = leaf children (not
-// flagged empty), out[3] = of them cullable, out[4] = inner records whose pad is not zero.  Returns build_layout's status.
+// flagged empty), out[3] = of them cullable, out[4] = inner records whose cull word is not zero.  Returns build_layout's status.
 int cull_layout_bits(const ptmi_config* cfg, const ptmi_scene* scene, uint32_t out[5])
 {
     Relayout lay;
@@ -141,10 +141,10 @@ int cull_layout_bits(const ptmi_config* cfg, const ptmi_scene* scene, uint32_t o
         if (lay.tri_ids[i] != 0xFFFFFFFFu) continue;
         const DNode& n = *reinterpret_cast<const DNode*>(&lay.recs[i]);
         out[0]++;
-        if (n.pad & ptmi_cull::kCullComputed) out[1]++;
-        if (n.pad) out[4]++;
-        if ((n.ref1 & REF_LEAF) && !(n.ref1 & REF_EMPTY)) { out[2]++; if (n.pad & ptmi_cull::kCullChild1) out[3]++; }
-        if ((n.ref2 & REF_LEAF) && !(n.ref2 & REF_EMPTY)) { out[2]++; if (n.pad & ptmi_cull::kCullChild2) out[3]++; }
+        if (n.cull & ptmi_cull::kCullComputed) out[1]++;
+        if (n.cull) out[4]++;
+        if ((n.ref1 & REF_LEAF) && !(n.ref1 & REF_EMPTY)) { out[2]++; if (n.cull & ptmi_cull::kCullChild1) out[3]++; }
+        if ((n.ref2 & REF_LEAF) && !(n.ref2 & REF_EMPTY)) { out[2]++; if (n.cull & ptmi_cull::kCullChild2) out[3]++; }
     }
     return rc;
 }
