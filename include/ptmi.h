@@ -341,6 +341,54 @@ int ptmi_query_rays(ptmi_ctx* ctx, uint32_t kind, const ptmi_ray* rays, uint32_t
  * rewrite the scene; the caller orders its own reads of d_hits behind the stream (or calls ptmi_synchronize). */
 int ptmi_query_rays_device(ptmi_ctx* ctx, uint32_t kind, const void* d_rays, uint32_t n_rays, void* d_hits);
 
+/* ---- first-hit guide buffers ----------------------------------------------- */
+
+/* What the camera sees, per pixel, without rendering it: albedo, shading normal and position planes (denoiser inputs), a hit
+ * count (the hit mask) and an id plane (picking, selection outlines).  Pixel p = gy * W + gx is visited for the iterations
+ * it = first_iteration, ..., first_iteration + n_iterations - 1, in that order, and for each one the PRIMARY ray is traced that
+ * ptmi_render traces for (gx, gy, it): the same seed (InitializeRandomSeed; PTMI_FLAG_SOURCE_SEED is honoured), the same sample
+ * (sampler(), FullKernel.cl:1119-1150), the same camera expression (cl:1213) and Ray3D_Create, the same BVH_IntersectRay with
+ * an unlimited distance - bit for bit in the context's arithmetic, against the geometry and the camera the context holds NOW
+ * (after any ptmi_set_camera / ptmi_update_triangles).  Every sum starts at +0 and adds in iteration order, so the planes are a
+ * function of the call's arguments alone.
+ *   a hit:   albedo[p]    += the colour the integrator shades with: the material's, or the texel of Triangle_GetColorValueAt
+ *            normal[p]    += Ns, the smooth normal after cl:1254-1274 (turned towards the ray, normalised)
+ *            position[p]  += intersectionPoint
+ *            hit_count[p] += 1
+ *   a miss:  albedo[p]    += Sky_GetColorValue(direction), the colour the path would collect; nothing else is added.
+ *   ids[4p .. 4p+3] describe iteration first_iteration ONLY: triangle_id (the caller's index, as in ptmi_ray_hit; 0xFFFFFFFF = a
+ *            miss), the material index that was shaded (the positive-normal one where front, else the negative-normal one; 0 on
+ *            a miss), front (as in ptmi_ray_hit; 0 on a miss), 0.
+ * All four components of albedo, normal and position are summed, as the reference's float4 arithmetic carries them.  Where a
+ * word is a NaN its sign and payload mean nothing, as for ptmi_ray_hit.  SUPER_SAMPLING is ignored: every iteration is traced
+ * (the stop criterion's draw comes after the sample and cannot move the ray).  A scene with a ptmi_literal_kernel_reason is
+ * served, as by the ray queries.
+ * A GUIDE CALL TOUCHES NOTHING THAT HAS BEEN RENDERED, with the same list as the ray queries: accumulators, histograms,
+ * ptmi_counters, scheduler statistics, snapshots and launches rendered ahead stay as they are.  Both calls run on devices[0] of
+ * a multi-device context, on its main stream (ptmi_set_stream's, where one was given); the calls that rewrite scene records
+ * wait for that stream first.
+ * PTMI_ERR_STATE before ptmi_initialize_memory; PTMI_ERR_INVALID_ARGUMENT for a NULL struct, a wrong struct_size or a device
+ * plane that is not 16-byte aligned; PTMI_ERR_UNSUPPORTED on a context set up with the RANDOM sampler (its samples land on
+ * other pixels than the work-item's); n_iterations == 0, or every plane NULL, is PTMI_OK and launches nothing.  After any error
+ * the context renders as before. */
+typedef struct ptmi_guides {
+    uint32_t struct_size;   /* = sizeof(ptmi_guides) */
+    uint32_t reserved;      /* 0 */
+    float*    albedo;       /* float4[W*H] */
+    float*    normal;       /* float4[W*H] */
+    float*    position;     /* float4[W*H] */
+    float*    hit_count;    /* float [W*H] */
+    uint32_t* ids;          /* uint32[4*W*H] */
+} ptmi_guides;              /* any plane may be NULL: not written */
+
+/* Host planes: the kernel fills a scratch buffer of the context (allocated by the first guide call for the planes it asks for,
+ * grown when a later call asks for more, freed by ptmi_release: a context that never asks pays nothing), the planes come down -
+ * straight into the ones the caller has page-locked (ptmi_pin_host_buffer) - and the call returns with them filled. */
+int ptmi_render_guides(ptmi_ctx* ctx, uint32_t first_iteration, uint32_t n_iterations, const ptmi_guides* host_planes);
+/* Device pointers (e.g. torch tensors), each 16-byte aligned: asynchronous on the context's stream, ordered like
+ * ptmi_query_rays_device. */
+int ptmi_render_guides_device(ptmi_ctx* ctx, uint32_t first_iteration, uint32_t n_iterations, const ptmi_guides* device_planes);
+
 /* ---- measurement / plumbing -------------------------------------------- */
 
 int ptmi_get_counters(ptmi_ctx* ctx, ptmi_counters* out);

@@ -87,6 +87,15 @@ class UpdateInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class Guides(C.Structure):
+    """ptmi_guides: the planes ptmi_render_guides fills (host or device addresses; None = not written)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("albedo", C.c_void_p), ("normal", C.c_void_p),
+                ("position", C.c_void_p), ("hit_count", C.c_void_p), ("ids", C.c_void_p)]
+
+
+GUIDE_PLANES = ("albedo", "normal", "position", "hit_count", "ids")  # ptmi_guides, in the struct's order
+
+
 BVH_FALLBACK_NONE, BVH_FALLBACK_STALE_AXIS, BVH_FALLBACK_HOST_ERROR, BVH_FALLBACK_RECORDS = 0, 1, 2, 3
 
 
@@ -125,7 +134,7 @@ ABI_SYMBOLS = ["ptmi_setup_context", "ptmi_initialize_memory", "ptmi_render", "p
                "ptmi_device_variance", "ptmi_last_error",
                "ptmi_abi_version", "ptmi_device_count", "ptmi_device_share", "ptmi_bvh_create",
                "ptmi_bvh_create_device", "ptmi_set_camera", "ptmi_update_triangles", "ptmi_bvh_refit",
-               "ptmi_query_rays", "ptmi_query_rays_device"]
+               "ptmi_query_rays", "ptmi_query_rays_device", "ptmi_render_guides", "ptmi_render_guides_device"]
 
 QUERY_CLOSEST, QUERY_ANY = 0, 1  # ptmi.h: PTMI_QUERY_*
 
@@ -182,6 +191,8 @@ def load_library():
     lib.ptmi_bvh_refit.argtypes = [vp, u32, vp, u32]
     lib.ptmi_query_rays.argtypes = [vp, u32, vp, u32, vp]
     lib.ptmi_query_rays_device.argtypes = [vp, u32, vp, u32, vp]
+    lib.ptmi_render_guides.argtypes = [vp, u32, u32, C.POINTER(Guides)]
+    lib.ptmi_render_guides_device.argtypes = [vp, u32, u32, C.POINTER(Guides)]
     lib.ptmi_device_share.argtypes = [u32, u32, u32, u32, C.POINTER(u32), C.POINTER(u32)]
     lib.ptmi_device_share.restype = None
     _lib = lib
@@ -373,6 +384,43 @@ class Backend:
         ``d_hits``: asynchronous on the context's stream."""
         self._check(self._lib.ptmi_query_rays_device(self._ctx, QUERY_ANY if any_hit else QUERY_CLOSEST, C.c_void_p(d_rays), n,
                                                      C.c_void_p(d_hits)))
+
+    # -- what the camera sees, per pixel (no counterpart in the reference) ------------------
+    def guide_plane(self, name):
+        """An empty array of the shape and type ``render_guides`` fills for plane ``name``."""
+        h, w = self.cfg.image_height, self.cfg.image_width
+        if name not in GUIDE_PLANES:
+            raise PtmiError(-1, f"unknown guide plane {name!r}: one of {GUIDE_PLANES}")
+        return np.empty((h, w) if name == "hit_count" else (h, w, 4), np.uint32 if name == "ids" else np.float32)
+
+    def render_guides(self, first_iteration, n_iterations, planes=GUIDE_PLANES, out=None):
+        """The first hit of the primary rays ``render`` traces for iterations [first_iteration, first_iteration + n_iterations),
+        summed per pixel: ``albedo``, ``normal``, ``position`` float32[H,W,4], ``hit_count`` float32[H,W] (a miss adds the sky's
+        colour to ``albedo`` and nothing else), and ``ids`` uint32[H,W,4] = (triangle, material, front, 0) of iteration
+        ``first_iteration`` (triangle ``structs.RAY_MISS`` = no hit).  Returns a dict of the ``planes`` asked for; ``out`` = a dict
+        of arrays to fill instead (e.g. page-locked ones).  Touches nothing that has been rendered."""
+        arrays = {}
+        for name in planes:
+            a = self.guide_plane(name) if out is None or name not in out else out[name]
+            want = self.guide_plane(name)
+            if a.dtype != want.dtype or a.shape != want.shape or not a.flags.c_contiguous:
+                raise PtmiError(-1, f"out[{name!r}] must be a contiguous {want.dtype} array of shape {want.shape}")
+            arrays[name] = a
+        g = Guides(C.sizeof(Guides), 0)
+        for name, a in arrays.items():
+            setattr(g, name, a.ctypes.data)
+        self._check(self._lib.ptmi_render_guides(self._ctx, first_iteration, n_iterations, C.byref(g)))
+        return arrays
+
+    def render_guides_device(self, first_iteration, n_iterations, **device_planes):
+        """The same to device addresses (e.g. ``albedo=tensor.data_ptr()``), 16-byte aligned, one keyword per plane wanted:
+        asynchronous on the context's stream."""
+        g = Guides(C.sizeof(Guides), 0)
+        for name, address in device_planes.items():
+            if name not in GUIDE_PLANES:
+                raise PtmiError(-1, f"unknown guide plane {name!r}: one of {GUIDE_PLANES}")
+            setattr(g, name, address)
+        self._check(self._lib.ptmi_render_guides_device(self._ctx, first_iteration, n_iterations, C.byref(g)))
 
     # -- one launch of the loop body of OpenCL_RunKernel, generalised to a range ----------
     def render(self, first_iteration, n_iterations):

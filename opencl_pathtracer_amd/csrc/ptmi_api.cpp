@@ -1,6 +1,6 @@
 // ptmi_api.cpp - host side of libptmi.so: the C ABI of include/ptmi.h.  This unit: a context's life cycle (setup, release,
 // errors) and the small accessors; the rest of the ABI lies in ptmi_scene_memory.cpp (upload and in-place update),
-// ptmi_render.cpp (the launches), ptmi_readback.cpp (snapshots and images) and ptmi_query.cpp (ray queries).
+// ptmi_render.cpp (the launches), ptmi_readback.cpp (snapshots and images), ptmi_query.cpp (ray queries) and ptmi_guides.cpp (first-hit guide buffers).
 // Owns, of ptmi_context.h: the per-context state - creates the context with its main and copy streams and destroys everything
 // the other units have added to it.
 //
@@ -291,6 +291,8 @@ void ptmi_release(ptmi_ctx* ctx)
     if (!ctx->dev.empty()) (void)hipSetDevice(ctx->dev[0].device);
     if (ctx->d_query) (void)hipFree(ctx->d_query);
     if (ctx->h_query) (void)hipHostFree(ctx->h_query);
+    if (ctx->d_guides) (void)hipFree(ctx->d_guides);
+    if (ctx->h_guides) (void)hipHostFree(ctx->h_guides);
     destroy_rccl_communicators(ctx);
     for (auto& r : ctx->pinned_host) (void)hipHostUnregister(r.p);
     (void)hipGetLastError();

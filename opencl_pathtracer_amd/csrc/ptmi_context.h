@@ -1,5 +1,5 @@
 // ptmi_context.h - the state behind a ptmi_ctx, grouped by WHEN IT DIES, and what the host units of libptmi.so share
-// (ptmi_api.cpp, ptmi_scene_memory.cpp, ptmi_render.cpp, ptmi_readback.cpp, ptmi_query.cpp).  Private: not ABI, never installed.
+// (ptmi_api.cpp, ptmi_scene_memory.cpp, ptmi_render.cpp, ptmi_readback.cpp, ptmi_query.cpp, ptmi_guides.cpp).  Private: not ABI, never installed.
 //
 // Two lifetimes.  PER SCENE (DeviceScene, ContextScene): free_scene_memory() frees what the struct owns and assigns a
 // value-initialised one, so a new per-scene field needs no line anywhere else.  PER CONTEXT (the members DeviceState and ptmi_ctx
@@ -112,6 +112,11 @@ struct ptmi_ctx : ptmi_internal::ContextScene {
     char* d_query = nullptr;
     char* h_query = nullptr;
     size_t query_cap = 0;
+    // ptmi_render_guides (host planes), on devices[0]: the planes of one call behind one another (guides_cap bytes), and a pinned
+    // landing place of the same layout for the planes that are not page-locked; allocated by the first call, grown on demand
+    char* d_guides = nullptr;
+    char* h_guides = nullptr;
+    size_t guides_cap = 0;
 
     ptmi_internal::ContextScene& scene() { return *this; }
     uint32_t n_dev() const { return (uint32_t)dev.size(); }

@@ -3,6 +3,7 @@
 #pragma once
 
 #include <cstdint>
+#include <cstdlib>
 #include <string>
 
 #include "ptmi.h"
@@ -23,6 +24,28 @@ inline int launch_status(hipError_t e, const char* kernel, std::string* err)
     if (e == hipSuccess) return PTMI_OK;
     if (err) *err = std::string(kernel) + " launch: " + hipGetErrorString(e);
     return PTMI_ERR_HIP;
+}
+
+// The grid of a kernel whose 256-lane workgroups keep one LDS traversal stack each and take their work in a grid-stride loop
+// (ray_query.hip, guide_buffers.hip): as many workgroups as the device holds at once - 8 of four waves by wave slots, fewer
+// where 160 KB of LDS hold fewer stacks - four times over (rays differ in cost), and never more than `wanted`; the loop takes
+// the rest.  `cap_env`: the environment switch of the tests that caps the grid, so that a small batch takes the loop too.
+inline int stack_kernel_grid(size_t lds_bytes, uint64_t wanted, const char* cap_env, const char* kernel, uint32_t* blocks,
+                             std::string* err)
+{
+    int device = 0, cus = 0;
+    hipError_t e = hipGetDevice(&device);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+    if (e != hipSuccess) return launch_status(e, kernel, err);
+    const size_t by_lds = (160u * 1024u) / lds_bytes;
+    const int per_cu = (int)(by_lds < 8 ? by_lds : 8);
+    uint64_t cap = 4ull * (uint64_t)(cus > 0 ? cus : 1) * (uint64_t)(per_cu > 0 ? per_cu : 1);
+    if (const char* v = std::getenv(cap_env)) {  // env: test switch
+        const long want = std::strtol(v, nullptr, 10);
+        if (want >= 1 && (uint64_t)want < cap) cap = (uint64_t)want;
+    }
+    *blocks = (uint32_t)(wanted > cap ? cap : wanted);
+    return PTMI_OK;
 }
 #endif
 
@@ -230,6 +253,21 @@ int launch_query_rays(const DScene& sc, bool any_hit, const void* d_rays, void* 
                       void* stream, std::string* err);
 int launch_query_rays_da(const DScene& sc, bool any_hit, const void* d_rays, void* d_hits, uint32_t n_rays, uint32_t stack_levels,
                          void* stream, std::string* err);
+
+// guide_buffers.hip (compiled once per arithmetic mode): the first-hit planes of ptmi_render_guides for iterations
+// [first_iteration, first_iteration + n_iterations), to DEVICE pointers; a plane that is NULL is not written.  stack_levels as
+// for launch_query_rays.  Reads the scene's records and the camera only.
+struct DGuides {
+    float* albedo;     // float4[W*H]
+    float* normal;     // float4[W*H]
+    float* position;   // float4[W*H]
+    float* hit_count;  // float[W*H]
+    uint32_t* ids;     // uint4[W*H]
+};
+int launch_guides(const DScene& sc, const DGuides& planes, uint32_t first_iteration, uint32_t n_iterations, uint32_t stack_levels,
+                  void* stream, std::string* err);
+int launch_guides_da(const DScene& sc, const DGuides& planes, uint32_t first_iteration, uint32_t n_iterations,
+                     uint32_t stack_levels, void* stream, std::string* err);
 
 // display.hip: accumulators -> padded B,G,R scanlines (the reference's ConvertRGBAToBMPBuffer), on the device
 int launch_display_bgr(const float* image_color, const float* image_ray_nb, uint8_t* out, uint32_t width, uint32_t height,

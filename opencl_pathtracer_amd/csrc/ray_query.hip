@@ -10,8 +10,6 @@
 // The kernel only READS scene memory: no accumulator, histogram or counter of the context is touched.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "ptmi_literal_path.hpp"
 
 namespace PTMI_DEV_NS {
@@ -75,22 +73,12 @@ int PTMI_ARITH(launch_query_rays)(const DScene& sc, bool any_hit, const void* d_
     const auto kernel = any_hit ? (pre ? query_rays_kernel<true, true> : query_rays_kernel<true, false>)
                                 : (pre ? query_rays_kernel<false, true> : query_rays_kernel<false, false>);
     const size_t lds_bytes = (size_t)stack_levels * kQueryBlock * sizeof(uint32_t);
-    // as many workgroups as the device holds at once - 8 of four waves by wave slots, fewer where 160 KB of LDS hold fewer
-    // stacks - four times over (rays differ in cost); the grid-stride loop takes the rest
-    int device = 0, cus = 0;
-    hipError_t e = hipGetDevice(&device);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-    if (e != hipSuccess) return launch_status(e, "query_rays_kernel", err);
-    const size_t by_lds = (160u * 1024u) / lds_bytes;
-    const int per_cu = (int)(by_lds < 8 ? by_lds : 8);
-    uint64_t blocks = ((uint64_t)n_rays + kQueryBlock - 1) / kQueryBlock;
-    uint64_t cap = 4ull * (uint64_t)(cus > 0 ? cus : 1) * (uint64_t)(per_cu > 0 ? per_cu : 1);
-    if (const char* v = std::getenv("PTMI_QUERY_MAX_BLOCKS")) {  // env: test switch - small batches take the grid-stride loop
-        const long want = std::strtol(v, nullptr, 10);
-        if (want >= 1 && (uint64_t)want < cap) cap = (uint64_t)want;
-    }
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(kQueryBlock), lds_bytes, (hipStream_t)stream, sc,
+    // what the device holds at once, four times over; the grid-stride loop takes the rest (stack_kernel_grid, ptmi_internal.h)
+    uint32_t blocks = 0;
+    if (int rc = stack_kernel_grid(lds_bytes, ((uint64_t)n_rays + kQueryBlock - 1) / kQueryBlock, "PTMI_QUERY_MAX_BLOCKS",
+                                   "query_rays_kernel", &blocks, err))
+        return rc;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kQueryBlock), lds_bytes, (hipStream_t)stream, sc,
                        static_cast<const float4*>(d_rays), static_cast<float4*>(d_hits), n_rays);
     return launch_status(hipGetLastError(), "query_rays_kernel", err);
 }
