@@ -2,10 +2,8 @@
 // the paths ptmi_render traces, summed over a range of iterations into albedo / normal / position / hit-count planes, and the
 // triangle, material and side of the first iteration's hit.
 //
-// Nothing of the integrator is restated here.  A primary ray is made as trace_path makes it (ptmi_literal_path.hpp: lcg_seed,
-// draw_sample, the camera expression of cl:1213, ray_set_direction); its closest hit is the ray query's (ray_query.hip: the
-// three-way choice between nan_walk, the walk with the ordered box test and the literal walk - the same triangle, bit for
-// bit, whichever is taken); the surface is load_surface's and a miss collects sky_color.  What is this kernel's own:
+// Nothing of the integrator is restated here.  A primary ray is trace_path's `primary_ray`, its closest hit the ray query's
+// `query` (both ptmi_literal_path.hpp); the surface is load_surface's and a miss collects sky_color.  What is this kernel's own:
 //   * one lane per pixel and one wave per 8 x 8 tile, as the wavefront kernel lays out its paths, in a grid-stride loop over
 //     tiles; the lanes of an edge tile that lie outside the image idle;
 //   * a lane runs its iterations one after the other and keeps the four sums in registers, so every plane is written once;
@@ -17,16 +15,14 @@
 
 namespace PTMI_DEV_NS {
 
-constexpr int kGuideBlock = 256;  // 4 waves = 4 tiles; a lane keeps one pixel and one column of the stack
-static_assert(kGuideBlock == kBlock, "walk() steps kBlock words from one stack level to the next");
-constexpr uint32_t kGuideWaves = kGuideBlock / 64;
+constexpr uint32_t kGuideWaves = kBlock / 64;  // 4 waves = 4 tiles; a lane keeps one pixel and one column of the stack
 
 template <bool PRE>
-__global__ void __launch_bounds__(kGuideBlock) guide_kernel(const DScene sc, const DGuides out, const uint32_t first_iteration,
+__global__ void __launch_bounds__(kBlock) guide_kernel(const DScene sc, const DGuides out, const uint32_t first_iteration,
                                                             const uint32_t n_iterations, const uint32_t tiles_x,
                                                             const uint32_t n_tiles)
 {
-    extern __shared__ uint32_t guide_stack[];  // [stack_levels][kGuideBlock]
+    extern __shared__ uint32_t guide_stack[];  // [stack_levels][kBlock]
     uint32_t* const stack = &guide_stack[threadIdx.x];
     const uint32_t wave = threadIdx.x >> 6, in_tile = threadIdx.x & 63u;
 
@@ -40,26 +36,13 @@ __global__ void __launch_bounds__(kGuideBlock) guide_kernel(const DScene sc, con
         uint32_t id_triangle = 0xFFFFFFFFu, id_material = 0, id_front = 0;
         for (uint32_t k = 0; k < n_iterations; k++) {
             const uint32_t iteration = first_iteration + k;
-            int seed = lcg_seed(gx, gy, sc.width, sc.height, iteration, sc.source_seed != 0);
+            int seed;
             float sample_x, sample_y;
-            draw_sample(sc, gx, gy, iteration, seed, sample_x, sample_y);
-            Ray r;
-            r.o = v4(sc.cam_pos);
-            ray_set_direction(r, mad(v4(sc.cam_up), sample_y, mad(v4(sc.cam_right), sample_x, v4(sc.cam_dir))));  // cl:1213
-
+            const Ray r = primary_ray(sc, gx, gy, iteration, seed, sample_x, sample_y);
             float limit = INFINITY;
-            Hit hit;
-            hit.tri = 0; hit.s = 0; hit.t = 0; hit.front = false; hit.point = v4(0, 0, 0, 0);
+            Hit hit = no_hit();
             PathCounters pc{0, 0};
-            bool found;
-            if (nan_walk_applies<false>(sc, r)) {
-                found = nan_walk<PRE>(sc, r, limit, hit, pc);
-            } else if (sc.boxes_ordered && ray_slabs_are_ordered(r)) {
-                found = walk<false, PRE, true>(sc, r, limit, hit, pc, stack);
-            } else {
-                found = walk<false, PRE, false>(sc, r, limit, hit, pc, stack);
-            }
-            if (found) {
+            if (query<false, PRE>(sc, r, limit, hit, pc, stack)) {
                 Surface sf;
                 load_surface(sc, r, hit, sf);
                 albedo = albedo + sf.color;
@@ -95,12 +78,7 @@ int PTMI_ARITH(launch_guides)(const DScene& sc, const DGuides& planes, uint32_t 
 {
     using namespace PTMI_DEV_NS;
     if (n_iterations == 0 || sc.width == 0 || sc.height == 0) return PTMI_OK;
-    if (stack_levels < 1 || stack_levels > PTMI_BVH_MAX_DEPTH) {
-        if (err) *err = "guide_kernel: " + std::to_string(stack_levels) + " stack levels";
-        return PTMI_ERR_INTERNAL;
-    }
     const auto kernel = sc.tris_precomputed != 0 ? guide_kernel<true> : guide_kernel<false>;
-    const size_t lds_bytes = (size_t)stack_levels * kGuideBlock * sizeof(uint32_t);
     const uint32_t tiles_x = (sc.width + 7u) / 8u, tiles_y = (sc.height + 7u) / 8u;
     const uint64_t n_tiles = (uint64_t)tiles_x * tiles_y;
     if (n_tiles > 0x7FFFFFFFull) {  // (the tile index plus its grid-stride step stays below 2^32)
@@ -108,10 +86,11 @@ int PTMI_ARITH(launch_guides)(const DScene& sc, const DGuides& planes, uint32_t 
         return PTMI_ERR_INTERNAL;
     }
     uint32_t blocks = 0;
-    if (int rc = stack_kernel_grid(lds_bytes, (n_tiles + kGuideWaves - 1) / kGuideWaves, "PTMI_GUIDE_MAX_BLOCKS", "guide_kernel",
-                                   &blocks, err))
+    size_t lds_bytes = 0;
+    if (int rc = stack_kernel_grid(stack_levels, (n_tiles + kGuideWaves - 1) / kGuideWaves, "PTMI_GUIDE_MAX_BLOCKS", "guide_kernel",
+                                   &blocks, &lds_bytes, err))
         return rc;
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kGuideBlock), lds_bytes, (hipStream_t)stream, sc, planes, first_iteration,
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), lds_bytes, (hipStream_t)stream, sc, planes, first_iteration,
                        n_iterations, tiles_x, (uint32_t)n_tiles);
     return launch_status(hipGetLastError(), "guide_kernel", err);
 }

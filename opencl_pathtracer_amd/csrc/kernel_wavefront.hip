@@ -799,6 +799,7 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
 
         if (want_post) {
             // ---- start the next camera path of this pixel (FullKernel.cl:1208-1215) ------------
+            // (the lane-per-ray kernels make the same ray in primary_ray, ptmi_literal_path.hpp)
             if (got_job) {
                 const uint32_t it = first_iteration + it_local * iteration_stride;
                 slot = it_local * (sc.width * sc.height) + gy * sc.width + gx;

@@ -289,10 +289,8 @@ void ptmi_release(ptmi_ctx* ctx)
     if (!ctx) return;
     free_scene_memory(ctx);
     if (!ctx->dev.empty()) (void)hipSetDevice(ctx->dev[0].device);
-    if (ctx->d_query) (void)hipFree(ctx->d_query);
-    if (ctx->h_query) (void)hipHostFree(ctx->h_query);
-    if (ctx->d_guides) (void)hipFree(ctx->d_guides);
-    if (ctx->h_guides) (void)hipHostFree(ctx->h_guides);
+    ctx->query_buffers.release();
+    ctx->guide_buffers.release();
     destroy_rccl_communicators(ctx);
     for (auto& r : ctx->pinned_host) (void)hipHostUnregister(r.p);
     (void)hipGetLastError();

@@ -9,6 +9,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstring>
 #include <string>
 #include <utility>
 #include <vector>
@@ -18,6 +19,8 @@
 #include "scene_refit.h"
 #include "launch_schedule.h"
 #include "snapshot_ring.h"
+
+struct ptmi_ctx;
 
 namespace ptmi_internal {
 
@@ -73,6 +76,22 @@ struct DeviceState : DeviceScene {
     DeviceScene& scene() { return *this; }
 };
 
+// ---- per context: a round trip through devices[0] for host arrays of the caller's (ptmi_query_rays, ptmi_render_guides) - a
+// device buffer, and a pinned landing buffer of `cap` bytes, allocated only once a result's destination is not page-locked.
+// reserve() frees and regrows both when `landing_bytes` exceeds the capacity; ptmi_release frees them.
+struct RoundTrip {
+    char *d = nullptr, *h = nullptr;
+    size_t cap = 0;
+    int reserve(ptmi_ctx* ctx, size_t device_bytes, size_t landing_bytes, bool need_landing);
+    void release()
+    {
+        if (d) (void)hipFree(d);
+        if (h) (void)hipHostFree(h);
+        d = h = nullptr;
+        cap = 0;
+    }
+};
+
 // ---- per scene, on the context
 struct ContextScene {
     bool have_scene = false;
@@ -107,16 +126,9 @@ struct ptmi_ctx : ptmi_internal::ContextScene {
     float* h_staging = nullptr;  // pinned, 5*W*H floats
     struct HostRange { char* p; size_t bytes; };
     std::vector<HostRange> pinned_host;  // caller buffers page-locked by ptmi_pin_host_buffer: readbacks DMA straight into them
-    // ptmi_query_rays (host arrays), on devices[0]: room for query_cap rays and as many hits behind them, and a pinned landing
-    // place for the hits of a destination that is not page-locked; allocated by the first query, grown on demand
-    char* d_query = nullptr;
-    char* h_query = nullptr;
-    size_t query_cap = 0;
-    // ptmi_render_guides (host planes), on devices[0]: the planes of one call behind one another (guides_cap bytes), and a pinned
-    // landing place of the same layout for the planes that are not page-locked; allocated by the first call, grown on demand
-    char* d_guides = nullptr;
-    char* h_guides = nullptr;
-    size_t guides_cap = 0;
+    // ptmi_query_rays: rays, and `cap` bytes of hits behind them, on the device; the hits land.  ptmi_render_guides: the planes
+    // of one call behind one another, in the same layout on the device and where they land
+    ptmi_internal::RoundTrip query_buffers, guide_buffers;
 
     ptmi_internal::ContextScene& scene() { return *this; }
     uint32_t n_dev() const { return (uint32_t)dev.size(); }
@@ -191,6 +203,45 @@ int lazy_pinned_buffer(ptmi_ctx* ctx, T*& p, size_t bytes)
 inline int lazy_event(ptmi_ctx* ctx, hipEvent_t& e)
 {
     if (!e) HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return PTMI_OK;
+}
+
+inline int RoundTrip::reserve(ptmi_ctx* ctx, size_t device_bytes, size_t landing_bytes, bool need_landing)
+{
+    if (landing_bytes > cap) {
+        release();  // (every earlier call has returned, so nothing is in flight on the buffers that go)
+        if (int rc = lazy_device_buffer(ctx, d, device_bytes)) return rc;
+        cap = landing_bytes;
+    }
+    return need_landing ? lazy_pinned_buffer(ctx, h, cap) : (int)PTMI_OK;
+}
+
+// Device memory -> host arrays of the caller's over `stream`: one DMA straight into a destination that is page-locked
+// (ptmi_pin_host_buffer), otherwise into `landing` at the item's offset and, after the ONE wait for the stream, a memcpy.
+struct Landing {
+    void* to;  // nullptr: nothing is asked for
+    const void* from;
+    size_t bytes, offset;
+};
+template <size_t N>
+bool needs_landing(const ptmi_ctx* ctx, const Landing (&items)[N])
+{
+    for (const Landing& i : items)
+        if (i.to && !ctx->host_is_pinned(i.to, i.bytes)) return true;
+    return false;
+}
+template <size_t N>
+int land(ptmi_ctx* ctx, const Landing (&items)[N], hipStream_t stream, char* landing)
+{
+    bool direct[N];
+    for (size_t k = 0; k < N; k++) {
+        const Landing& i = items[k];
+        direct[k] = !i.to || ctx->host_is_pinned(i.to, i.bytes);
+        if (i.to) HIP_TRY(ctx, hipMemcpyAsync(direct[k] ? i.to : landing + i.offset, i.from, i.bytes, hipMemcpyDeviceToHost, stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    for (size_t k = 0; k < N; k++)
+        if (!direct[k]) std::memcpy(items[k].to, landing + items[k].offset, items[k].bytes);
     return PTMI_OK;
 }
 

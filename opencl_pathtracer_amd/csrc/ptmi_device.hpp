@@ -299,6 +299,8 @@ struct Hit {
     uint32_t tri;   // intersectedTriangleId
     bool front;     // N.dir < 0  => materialWithPositiveNormalIndex (FullKernel.cl:568)
 };
+// what every query starts from, and what a miss leaves
+__device__ __forceinline__ Hit no_hit() { return Hit{v4(0, 0, 0, 0), 0.f, 0.f, 0u, false}; }
 
 // Triangle_Intersects, FullKernel.cl:519-589, without the colour fetch (done
 // once for the final hit: the fetch is a pure function of triangle, side, s, t).

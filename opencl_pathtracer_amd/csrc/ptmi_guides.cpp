@@ -1,10 +1,8 @@
 // ptmi_guides.cpp - first-hit guide buffers of the loaded scene (guide_buffers.hip): ptmi_render_guides / ptmi_render_guides_device.
-// Owns, of ptmi_context.h: the per-context guide buffers d_guides / h_guides and their sizes (freed by ptmi_release); reads the
-// scene.  Like the ray queries (ptmi_query.cpp), both entry points launch on devices[0]'s MAIN stream and touch nothing but the
-// planes: the launch streams, the stage sets, the schedule and the counters are left alone, so whatever was rendered - or
-// rendered ahead - stays what it was, and the calls that rewrite scene records wait for that stream first.
-#include <cstring>
-
+// Owns, of ptmi_context.h: `guide_buffers` (a RoundTrip; the planes come back through land()); reads the scene.  Like the ray
+// queries (ptmi_query.cpp), both entry points launch on devices[0]'s MAIN stream and touch nothing but the planes: the launch
+// streams, the stage sets, the schedule and the counters are left alone, so whatever was rendered - or rendered ahead - stays
+// what it was, and the calls that rewrite scene records wait for that stream first.
 #include "ptmi_context.h"
 
 using namespace ptmi_internal;
@@ -73,41 +71,22 @@ int ptmi_render_guides(ptmi_ctx* ctx, uint32_t first_iteration, uint32_t n_itera
     DeviceState& d = ctx->dev[0];
     ON_DEVICE(ctx, d);
 
-    // the planes asked for, one behind the other in the scratch (each starts on a 16-byte boundary), and which of them land in
-    // page-locked memory of the caller's
-    size_t offset[kPlanes] = {}, bytes[kPlanes] = {}, total = 0;
-    bool pinned[kPlanes] = {}, all_pinned = true;
+    // the planes asked for, one behind the other in the scratch (each starts on a 16-byte boundary): exactly their bytes
+    Landing landing[kPlanes] = {};
+    size_t total = 0;
     for (int i = 0; i < kPlanes; i++) {
         if (!host.p[i]) continue;
-        bytes[i] = ctx->npix() * kBytesPerPixel[i];
-        offset[i] = total;
-        total += (bytes[i] + 15u) & ~(size_t)15u;
-        pinned[i] = ctx->host_is_pinned(host.p[i], bytes[i]);
-        all_pinned = all_pinned && pinned[i];
+        landing[i] = Landing{host.p[i], nullptr, ctx->npix() * kBytesPerPixel[i], total};
+        total += (landing[i].bytes + 15u) & ~(size_t)15u;
     }
-    if (total > ctx->guides_cap) {
-        // (every earlier host-plane call has returned, so nothing is in flight on the buffers that go)
-        if (ctx->d_guides) (void)hipFree(ctx->d_guides);
-        if (ctx->h_guides) (void)hipHostFree(ctx->h_guides);
-        ctx->d_guides = ctx->h_guides = nullptr;
-        ctx->guides_cap = 0;
-        if (int rc = lazy_device_buffer(ctx, ctx->d_guides, total)) return rc;
-        ctx->guides_cap = total;
-    }
-    if (!all_pinned)
-        if (int rc = lazy_pinned_buffer(ctx, ctx->h_guides, ctx->guides_cap)) return rc;
+    RoundTrip& g = ctx->guide_buffers;
+    if (int rc = g.reserve(ctx, total, total, needs_landing(ctx, landing))) return rc;
 
     Planes dev{};
     for (int i = 0; i < kPlanes; i++)
-        if (host.p[i]) dev.p[i] = ctx->d_guides + offset[i];
+        if (host.p[i]) landing[i].from = dev.p[i] = g.d + landing[i].offset;
     if (int rc = launch(ctx, d, dev, first_iteration, n_iterations)) return rc;
-    for (int i = 0; i < kPlanes; i++)
-        if (host.p[i])
-            HIP_TRY(ctx, hipMemcpyAsync(pinned[i] ? host.p[i] : (void*)(ctx->h_guides + offset[i]), dev.p[i], bytes[i], hipMemcpyDeviceToHost, d.stream));
-    HIP_TRY(ctx, hipStreamSynchronize(d.stream));
-    for (int i = 0; i < kPlanes; i++)
-        if (host.p[i] && !pinned[i]) std::memcpy(host.p[i], ctx->h_guides + offset[i], bytes[i]);
-    return PTMI_OK;
+    return land(ctx, landing, d.stream, g.h);
 }
 
 }  // extern "C"

@@ -29,15 +29,21 @@ inline int launch_status(hipError_t e, const char* kernel, std::string* err)
 // The grid of a kernel whose 256-lane workgroups keep one LDS traversal stack each and take their work in a grid-stride loop
 // (ray_query.hip, guide_buffers.hip): as many workgroups as the device holds at once - 8 of four waves by wave slots, fewer
 // where 160 KB of LDS hold fewer stacks - four times over (rays differ in cost), and never more than `wanted`; the loop takes
-// the rest.  `cap_env`: the environment switch of the tests that caps the grid, so that a small batch takes the loop too.
-inline int stack_kernel_grid(size_t lds_bytes, uint64_t wanted, const char* cap_env, const char* kernel, uint32_t* blocks,
-                             std::string* err)
+// the rest.  `stack_levels`: the depth of the uploaded tree; *lds_bytes = the dynamic LDS of a workgroup, one word per level
+// and lane.  `cap_env`: the environment switch of the tests that caps the grid, so that a small batch takes the loop too.
+inline int stack_kernel_grid(uint32_t stack_levels, uint64_t wanted, const char* cap_env, const char* kernel, uint32_t* blocks,
+                             size_t* lds_bytes, std::string* err)
 {
+    if (stack_levels < 1 || stack_levels > PTMI_BVH_MAX_DEPTH) {
+        if (err) *err = std::string(kernel) + ": " + std::to_string(stack_levels) + " stack levels";
+        return PTMI_ERR_INTERNAL;
+    }
+    *lds_bytes = (size_t)stack_levels * 256 * sizeof(uint32_t);
     int device = 0, cus = 0;
     hipError_t e = hipGetDevice(&device);
     if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
     if (e != hipSuccess) return launch_status(e, kernel, err);
-    const size_t by_lds = (160u * 1024u) / lds_bytes;
+    const size_t by_lds = (160u * 1024u) / *lds_bytes;
     const int per_cu = (int)(by_lds < 8 ? by_lds : 8);
     uint64_t cap = 4ull * (uint64_t)(cus > 0 ? cus : 1) * (uint64_t)(per_cu > 0 ? per_cu : 1);
     if (const char* v = std::getenv(cap_env)) {  // env: test switch
@@ -147,7 +153,7 @@ struct DMat {
 };
 static_assert(sizeof(DMat) == 32, "DMat");
 
-// calls one launch may render AHEAD for (ptmi_api.cpp: render_on_device): the launch keeps the totals of ptmi_get_counters per
+// calls one launch may render AHEAD for (ptmi_render.cpp: render_on_device): the launch keeps the totals of ptmi_get_counters per
 // call, in as many blocks of C_COUNT words
 #define PTMI_COUNTER_SPLITS 4
 
@@ -218,7 +224,7 @@ struct DScene {
 
 // The integrator's device code exists once per ARITHMETIC MODE (ptmi_device.hpp: strict / the reference's default OpenCL
 // build, PTMI_FLAG_DEFAULT_ARITHMETIC): kernels.hip and kernel_wavefront.hip are compiled twice and their entry points
-// carry the suffix `_da` in the default-arithmetic build.  A context picks one set (ptmi_api.cpp: kernels_of).
+// carry the suffix `_da` in the default-arithmetic build.  A context picks one set (ptmi_context.h: KERNELS_OF).
 #define PTMI_DECLARE_INTEGRATOR_ENTRY_POINTS(SUFFIX)                                                                             \
     /* kernels.hip: one path per lane (kept for A/B and as a second implementation in the parity tests)                         \
        iteration ids of a launch: first_iteration + k * iteration_stride, k < n_iterations */                                   \

@@ -136,14 +136,37 @@ __device__ __forceinline__ bool nan_walk(const DScene& sc, const Ray& r, float& 
     return accepted;
 }
 
-// One query of a path: the shortcut, else the walk with the LITERAL box test - which is what makes these loops the fallback
-// for everything the fast forms cannot express.
+// One query of a ray, for every kernel that keeps one ray per lane: the shortcut, else the walk with the 5-comparison box test
+// where scene, ray and limit allow it (MAY_ORDER; box_hit_ordered takes the limit as never negative), else the walk with the
+// LITERAL box test - the same triangle, bit for bit, whichever is taken.  `limit`: as for walk.
+template <bool ANY_HIT, bool PRE, bool MAY_ORDER = true>
+__device__ __forceinline__ bool query(const DScene& sc, const Ray& r, float& limit, Hit& hit, PathCounters& pc,
+                                      uint32_t* __restrict__ stack)
+{
+    if (nan_walk_applies<ANY_HIT>(sc, r)) return nan_walk<PRE>(sc, r, limit, hit, pc);
+    if (MAY_ORDER && sc.boxes_ordered && ray_slabs_are_ordered(r) && !(limit < 0)) return walk<ANY_HIT, PRE, true>(sc, r, limit, hit, pc, stack);
+    return walk<ANY_HIT, PRE, false>(sc, r, limit, hit, pc, stack);
+}
+// One query of a path: `query` with the ordered form switched off - which is what makes these loops the fallback for
+// everything the fast forms cannot express.
 template <bool ANY_HIT, bool PRE>
 __device__ __forceinline__ bool traverse(const DScene& sc, const Ray& r, float limit, Hit& hit, PathCounters& pc,
                                          uint32_t* __restrict__ stack)
 {
-    if (nan_walk_applies<ANY_HIT>(sc, r)) return nan_walk<PRE>(sc, r, limit, hit, pc);
-    return walk<ANY_HIT, PRE, false>(sc, r, limit, hit, pc, stack);
+    return query<ANY_HIT, PRE, false>(sc, r, limit, hit, pc, stack);
+}
+
+// The camera ray of sample (gx, gy, iteration) as Kernel_Main makes it (FullKernel.cl:1208-1215); `seed` is left where the
+// path goes on.  (kernel_wavefront.hip, "start the next camera path", keeps a copy that reads the cold scene record.)
+__device__ __forceinline__ Ray primary_ray(const DScene& sc, uint32_t gx, uint32_t gy, uint32_t iteration, int& seed,
+                                           float& sample_x, float& sample_y)
+{
+    seed = lcg_seed(gx, gy, sc.width, sc.height, iteration, sc.source_seed != 0);
+    draw_sample(sc, gx, gy, iteration, seed, sample_x, sample_y);
+    Ray r;
+    r.o = v4(sc.cam_pos);
+    ray_set_direction(r, mad(v4(sc.cam_up), sample_y, mad(v4(sc.cam_right), sample_x, v4(sc.cam_dir))));  // cl:1213
+    return r;
 }
 
 // One path = one Kernel_Main work-item (FullKernel.cl:1180-1331) up to the
@@ -156,13 +179,9 @@ __device__ __forceinline__ V4 trace_path(const DScene& sc, uint32_t gx, uint32_t
                                          uint32_t& depth, uint32_t& segments, uint32_t& shadows, PathCounters& pc,
                                          bool stop_criterion_draw = false)
 {
-    int seed = lcg_seed(gx, gy, sc.width, sc.height, iteration, sc.source_seed != 0);
-    draw_sample(sc, gx, gy, iteration, seed, sample_x, sample_y);
+    int seed;
+    Ray r = primary_ray(sc, gx, gy, iteration, seed, sample_x, sample_y);
     if (stop_criterion_draw) (void)lcg_random(seed);
-
-    Ray r;
-    r.o = v4(sc.cam_pos);
-    ray_set_direction(r, mad(v4(sc.cam_up), sample_y, mad(v4(sc.cam_right), sample_x, v4(sc.cam_dir))));  // cl:1213
 
     V4 radiance = v4(0, 0, 0, 0), transfer = v4(1, 1, 1, 1);
     bool active = true, in_water = false;
@@ -171,8 +190,7 @@ __device__ __forceinline__ V4 trace_path(const DScene& sc, uint32_t gx, uint32_t
     pc.tri = 0;
 
     while (active && reflection < sc.max_depth) {
-        Hit hit;
-        hit.tri = 0; hit.s = 0; hit.t = 0; hit.front = false; hit.point = v4(0, 0, 0, 0);
+        Hit hit = no_hit();
         segments++;
         if (traverse<false, PRE>(sc, r, INFINITY, hit, pc, stack)) {
             Surface sf;

@@ -1,11 +1,10 @@
 // ptmi_query.cpp - rays of the caller's own against the loaded scene (ray_query.hip): ptmi_query_rays / ptmi_query_rays_device.
-// Owns, of ptmi_context.h: the per-context query buffers d_query / h_query / query_cap (freed by ptmi_release); reads the scene.
+// Owns, of ptmi_context.h: `query_buffers` (a RoundTrip; the hits come back through land()); reads the scene.
 // Both entry points launch on devices[0]'s MAIN stream and touch nothing but the two ray buffers: the launch streams, the stage
 // sets, the schedule and the counters are left alone, so whatever was rendered - or rendered ahead - stays what it was.  The
 // calls that rewrite scene records wait for that stream first (quiesce, free_scene_memory; ptmi_set_stream waits for the
 // stream it leaves), which covers a device-pointer query still in flight.
 #include <algorithm>
-#include <cstring>
 
 #include "ptmi_context.h"
 
@@ -43,29 +42,17 @@ int ptmi_query_rays(ptmi_ctx* ctx, uint32_t kind, const ptmi_ray* rays, uint32_t
     DeviceState& d = ctx->dev[0];
     ON_DEVICE(ctx, d);
     const size_t bytes = (size_t)n_rays * sizeof(ptmi_ray);
-    const bool pinned = ctx->host_is_pinned(hits, bytes);
-    if (n_rays > ctx->query_cap) {
-        // (every earlier host-array query has returned, so nothing is in flight on the buffers that go)
-        if (ctx->d_query) (void)hipFree(ctx->d_query);
-        if (ctx->h_query) (void)hipHostFree(ctx->h_query);
-        ctx->d_query = ctx->h_query = nullptr;
-        ctx->query_cap = 0;
-        const size_t cap = std::max<size_t>(n_rays, 1024);
-        if (int rc = lazy_device_buffer(ctx, ctx->d_query, 2 * cap * sizeof(ptmi_ray))) return rc;
-        ctx->query_cap = cap;
-    }
-    if (!pinned)
-        if (int rc = lazy_pinned_buffer(ctx, ctx->h_query, ctx->query_cap * sizeof(ptmi_ray_hit))) return rc;
-    char* const d_rays = ctx->d_query;
-    char* const d_hits = ctx->d_query + ctx->query_cap * sizeof(ptmi_ray);
-    HIP_TRY(ctx, hipMemcpyAsync(d_rays, rays, bytes, hipMemcpyHostToDevice, d.stream));
+    RoundTrip& q = ctx->query_buffers;  // room for at least 1024 rays, with as many hits behind them in the one device buffer
+    const size_t room = std::max<size_t>(n_rays, 1024) * sizeof(ptmi_ray_hit);
+    Landing landing[1] = {{hits, nullptr, bytes, 0}};
+    if (int rc = q.reserve(ctx, 2 * room, room, needs_landing(ctx, landing))) return rc;
+    char* const d_hits = q.d + q.cap;
+    landing[0].from = d_hits;
+    HIP_TRY(ctx, hipMemcpyAsync(q.d, rays, bytes, hipMemcpyHostToDevice, d.stream));
     std::string err;
-    if (int rc = KERNELS_OF(ctx, launch_query_rays)(d.ds, kind == PTMI_QUERY_ANY, d_rays, d_hits, n_rays, ctx->stack_levels, d.stream, &err))
+    if (int rc = KERNELS_OF(ctx, launch_query_rays)(d.ds, kind == PTMI_QUERY_ANY, q.d, d_hits, n_rays, ctx->stack_levels, d.stream, &err))
         return fail(ctx, rc, err);
-    HIP_TRY(ctx, hipMemcpyAsync(pinned ? (void*)hits : (void*)ctx->h_query, d_hits, bytes, hipMemcpyDeviceToHost, d.stream));
-    HIP_TRY(ctx, hipStreamSynchronize(d.stream));
-    if (!pinned) std::memcpy(hits, ctx->h_query, bytes);
-    return PTMI_OK;
+    return land(ctx, landing, d.stream, q.h);
 }
 
 }  // extern "C"

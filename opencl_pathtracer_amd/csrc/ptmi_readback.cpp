@@ -40,19 +40,10 @@ namespace {
 // Device float[4*npix] / float[npix] -> the caller's buffers over devices[0]'s `stream`, then wait for that stream.
 int copy_out(ptmi_ctx* ctx, hipStream_t stream, const float* d_color, const float* d_count, float* image_color, float* image_ray_nb)
 {
-    const size_t npix = ctx->npix(), color_bytes = ctx->color_bytes(), count_bytes = ctx->count_bytes();
-    const bool pin_c = image_color && ctx->host_is_pinned(image_color, color_bytes);
-    const bool pin_n = image_ray_nb && ctx->host_is_pinned(image_ray_nb, count_bytes);
-    if ((image_color && !pin_c) || (image_ray_nb && !pin_n))
+    const Landing items[2] = {{image_color, d_color, ctx->color_bytes(), 0}, {image_ray_nb, d_count, ctx->count_bytes(), ctx->color_bytes()}};
+    if (needs_landing(ctx, items))
         if (int rc = lazy_pinned_buffer(ctx, ctx->h_staging, ctx->image_bytes())) return rc;
-    if (image_color)
-        HIP_TRY(ctx, hipMemcpyAsync(pin_c ? image_color : ctx->h_staging, d_color, color_bytes, hipMemcpyDeviceToHost, stream));
-    if (image_ray_nb)
-        HIP_TRY(ctx, hipMemcpyAsync(pin_n ? image_ray_nb : ctx->h_staging + 4 * npix, d_count, count_bytes, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(ctx, hipStreamSynchronize(stream));
-    if (image_color && !pin_c) std::memcpy(image_color, ctx->h_staging, color_bytes);
-    if (image_ray_nb && !pin_n) std::memcpy(image_ray_nb, ctx->h_staging + 4 * npix, count_bytes);
-    return PTMI_OK;
+    return land(ctx, items, stream, reinterpret_cast<char*>(ctx->h_staging));
 }
 
 // ---- RCCL, loaded at run time (the library has no link-time dependency on it) --------------------------------------------

@@ -2,10 +2,9 @@
 //
 // One query = the reference's BVH_IntersectRay (FullKernel.cl:620-702, PTMI_QUERY_CLOSEST) or BVH_IntersectShadowRay
 // (:705-783, PTMI_QUERY_ANY) on a ray made by Ray3D_Create (header.cl:276-295), bit for bit in the arithmetic of the build
-// (ptmi_device.hpp).  The queries are `walk` and `nan_walk` of ptmi_literal_path.hpp, the loops the integrator's literal path
-// runs.  What is this kernel's own:
+// (ptmi_device.hpp).  A query is `query` of ptmi_literal_path.hpp: the loops the integrator's literal path runs, with the
+// 5-comparison box test (box_hit_ordered) for a ray whose slabs are ordered, chosen once per ray.  What is this kernel's own:
 //   * the LDS traversal stack is sized at launch by the depth of the uploaded tree, not by PTMI_BVH_MAX_DEPTH;
-//   * a ray whose slabs are ordered takes the walk with the 5-comparison box test (box_hit_ordered), chosen once per ray;
 //   * the grid-stride loop over the caller's rays, and the ptmi_ray_hit it writes for each.
 // The kernel only READS scene memory: no accumulator, histogram or counter of the context is touched.
 #include <hip/hip_runtime.h>
@@ -14,35 +13,23 @@
 
 namespace PTMI_DEV_NS {
 
-constexpr int kQueryBlock = 256;  // 4 waves; a lane keeps one ray and one column of the stack
-static_assert(kQueryBlock == kBlock, "walk() steps kBlock words from one stack level to the next");
-
-// rays: 3 x 16 bytes each (ptmi_ray), hits: 3 x 16 bytes each (ptmi_ray_hit)
+// rays: 3 x 16 bytes each (ptmi_ray), hits: 3 x 16 bytes each (ptmi_ray_hit); a lane keeps one ray and one column of the stack
 template <bool ANY_HIT, bool PRE>
-__global__ void __launch_bounds__(kQueryBlock) query_rays_kernel(const DScene sc, const float4* __restrict__ rays,
+__global__ void __launch_bounds__(kBlock) query_rays_kernel(const DScene sc, const float4* __restrict__ rays,
                                                                  float4* __restrict__ hits, const uint32_t n_rays)
 {
-    extern __shared__ uint32_t query_stack[];  // [stack_levels][kQueryBlock]
+    extern __shared__ uint32_t query_stack[];  // [stack_levels][kBlock]
     uint32_t* const stack = &query_stack[threadIdx.x];
 
-    for (uint32_t i = blockIdx.x * kQueryBlock + threadIdx.x; i < n_rays; i += gridDim.x * kQueryBlock) {
+    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n_rays; i += gridDim.x * kBlock) {
         const float4 in_o = rays[3 * (size_t)i], in_d = rays[3 * (size_t)i + 1], in_l = rays[3 * (size_t)i + 2];
         Ray r;
         r.o = v4(in_o);
         ray_set_direction(r, v4(in_d));
         float limit = in_l.x;
-        Hit hit;
-        hit.tri = 0; hit.s = 0; hit.t = 0; hit.front = false; hit.point = v4(0, 0, 0, 0);
+        Hit hit = no_hit();
         PathCounters pc{0, 0};
-        bool found;
-        if (nan_walk_applies<ANY_HIT>(sc, r)) {
-            found = nan_walk<PRE>(sc, r, limit, hit, pc);
-        } else if (sc.boxes_ordered && ray_slabs_are_ordered(r) && !(limit < 0)) {
-            // (box_hit_ordered takes the distance limit as never negative: a caller's negative one keeps the literal form)
-            found = walk<ANY_HIT, PRE, true>(sc, r, limit, hit, pc, stack);
-        } else {
-            found = walk<ANY_HIT, PRE, false>(sc, r, limit, hit, pc, stack);
-        }
+        const bool found = query<ANY_HIT, PRE>(sc, r, limit, hit, pc, stack);
         float4 out_p = make_float4(0, 0, 0, 0), out_q = make_float4(0, 0, 0, __uint_as_float(0xFFFFFFFFu));
         uint32_t front = 0;
         if (found) {
@@ -65,20 +52,15 @@ int PTMI_ARITH(launch_query_rays)(const DScene& sc, bool any_hit, const void* d_
 {
     using namespace PTMI_DEV_NS;
     if (n_rays == 0) return PTMI_OK;
-    if (stack_levels < 1 || stack_levels > PTMI_BVH_MAX_DEPTH) {
-        if (err) *err = "query_rays_kernel: " + std::to_string(stack_levels) + " stack levels";
-        return PTMI_ERR_INTERNAL;
-    }
     const bool pre = sc.tris_precomputed != 0;
     const auto kernel = any_hit ? (pre ? query_rays_kernel<true, true> : query_rays_kernel<true, false>)
                                 : (pre ? query_rays_kernel<false, true> : query_rays_kernel<false, false>);
-    const size_t lds_bytes = (size_t)stack_levels * kQueryBlock * sizeof(uint32_t);
-    // what the device holds at once, four times over; the grid-stride loop takes the rest (stack_kernel_grid, ptmi_internal.h)
     uint32_t blocks = 0;
-    if (int rc = stack_kernel_grid(lds_bytes, ((uint64_t)n_rays + kQueryBlock - 1) / kQueryBlock, "PTMI_QUERY_MAX_BLOCKS",
-                                   "query_rays_kernel", &blocks, err))
+    size_t lds_bytes = 0;
+    if (int rc = stack_kernel_grid(stack_levels, ((uint64_t)n_rays + kBlock - 1) / kBlock, "PTMI_QUERY_MAX_BLOCKS",
+                                   "query_rays_kernel", &blocks, &lds_bytes, err))
         return rc;
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kQueryBlock), lds_bytes, (hipStream_t)stream, sc,
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), lds_bytes, (hipStream_t)stream, sc,
                        static_cast<const float4*>(d_rays), static_cast<float4*>(d_hits), n_rays);
     return launch_status(hipGetLastError(), "query_rays_kernel", err);
 }

@@ -8,8 +8,7 @@ carries it was not written, which is a miss.
   a hit   triangle_id, material_id, point and ns are the record's.  `front` is the side Triangle_Intersects picked the material
           by: material_id == materialWithPositiveNormalIndex where the triangle's two materials differ, else
           pto_triangle_intersects_side on that triangle with the primary ray, which this module builds from pto_sampler and
-          the camera expression of cl:1213 in the oracle's arithmetic (an exactly rounded fused multiply-add in the default
-          one).  That second ray checks itself: the triangle must accept it with the record's s, t and point, bit for bit.
+          the camera expression of cl:1213 in the oracle's arithmetic (f32_cases.camera_direction).  That second ray checks itself: the triangle must accept it with the record's s, t and point, bit for bit.
           The albedo is the material's simpleColor where isSimpleColor is set; else, for MAT_STANDART, the record's transfer
           (Scene_ComputeRadiance multiplies the initial transfer of 1 by the colour: 1 * c is c exactly).  A hit on a TEXTURED
           material of another type has no bit-exact albedo from this oracle (glass and water scale the texel, varnish may not
@@ -19,11 +18,11 @@ carries it was not written, which is a miss.
 Sums are np.float32 additions in iteration order, starting at +0.  An iteration of a scene is traced once and kept.
 """
 import ctypes as C
-from fractions import Fraction
 
 import numpy as np
 
 from opencl_pathtracer_amd import structs as S
+from f32_cases import bits as _bits, c4 as _c4, camera_direction
 import oracle_ffi as O
 
 f32 = np.float32
@@ -33,55 +32,6 @@ MAX_EXCLUDED = 0.10  # of a scene's hit samples: a condition on the scenes the t
 
 
 # ---------------------------------------------------------------------------------------------- the primary ray
-
-def _round_to_f32(q):
-    """The float32 nearest to the Fraction q, ties to even."""
-    near = f32(float(q))
-    best = None
-    for c in (np.nextafter(near, f32(-np.inf)), near, np.nextafter(near, f32(np.inf))):
-        if not np.isfinite(c):
-            continue
-        key = (abs(Fraction(float(c)) - q), int(c.view(np.uint32)) & 1)
-        if best is None or key < best[0]:
-            best = (key, c)
-    return best[1]
-
-
-def _mad(a, b, c, fused):
-    """a * b + c on float32 scalars: two rounded operations (the strict arithmetic), or one fused multiply-add."""
-    a, b, c = f32(a), f32(b), f32(c)
-    if not fused:
-        return f32(f32(a * b) + c)
-    if not (np.isfinite(a) and np.isfinite(b) and np.isfinite(c)):
-        with np.errstate(all="ignore"):
-            return f32(np.float64(a) * np.float64(b) + np.float64(c))  # (infinities and NaNs: nothing to round)
-    # float64 holds the product exactly and rounds the sum once; rounding that to float32 is the fused result unless the
-    # float64 sum sits exactly half way between two float32 values (or is zero, or tiny): those few go through exact fractions
-    s = np.float64(a) * np.float64(b) + np.float64(c)
-    if int(s.view(np.uint64)) & 0x1FFFFFFF != 0x10000000 and abs(s) > 1e-30:
-        return f32(s)
-    q = Fraction(float(a)) * Fraction(float(b)) + Fraction(float(c))
-    if q == 0:  # IEEE 754 6.3: an exact zero sum is +0 unless both addends are -0
-        product_negative = bool(np.signbit(a)) != bool(np.signbit(b))
-        both_zero = (a == 0 or b == 0) and c == 0
-        return f32(-0.0) if both_zero and product_negative and np.signbit(c) else f32(0.0)
-    return _round_to_f32(q)
-
-
-def primary_direction(scene, sample, fused):
-    """cameraDirection + cameraRight * sample.x + cameraUp * sample.y as cl:1213 nests it (un-normalised: Ray3D_Create does that)."""
-    with np.errstate(all="ignore"):
-        return np.array([_mad(scene.cameraUp[k], sample[1], _mad(scene.cameraRight[k], sample[0], scene.cameraDirection[k], fused), fused)
-                         for k in range(4)], f32)
-
-
-def _c4(v):
-    return (C.c_float * 4)(*[float(x) for x in v])
-
-
-def _bits(x):
-    return np.asarray(x, f32).view(np.uint32)
-
 
 def _same_words(a, b):
     """bit-equal, a NaN matching any NaN"""
@@ -116,19 +66,24 @@ class Yardstick:
             seed.value = 1
         sample = (C.c_float * 2)()
         self.lib.pto_sampler(self.sampler, gx, gy, self.w, self.h, it, C.byref(seed), sample)
-        return (sample[0], sample[1]), primary_direction(self.scene, (f32(sample[0]), f32(sample[1])), self.fused)
+        return (sample[0], sample[1]), camera_direction(self.scene, sample, self.fused)
+
+    def side_by_primary_ray(self, tri, s, t, point, gx, gy, it):
+        """The side of triangle `tri` that this module's own primary ray of (gx, gy, it) meets.  The ray checks itself: the
+        triangle must accept it with the hit's s, t and point, bit for bit."""
+        _, direction = self.primary_ray(gx, gy, it)
+        lim, s_, t_, p, side = C.c_float(np.inf), C.c_float(0), C.c_float(0), (C.c_float * 4)(), C.c_int(0)
+        ok = self.lib.pto_triangle_intersects_side(C.c_void_p(self.tris.ctypes.data + 336 * tri), self.origin, _c4(direction),
+                                                   C.byref(lim), C.byref(s_), C.byref(t_), p, C.byref(side))
+        assert ok and _same_words([s_.value, t_.value], [s, t]) and _same_words(tuple(p), tuple(point)), \
+            f"the yardstick's own primary ray does not reproduce the hit of sample ({gx}, {gy}, {it})"
+        return 1 if side.value else 0
 
     def _front(self, b, gx, gy, it):
         tri = b.triangle_id
         if self.mat_pos[tri] != self.mat_neg[tri]:
             return 1 if b.material_id == self.mat_pos[tri] else 0
-        _, direction = self.primary_ray(gx, gy, it)
-        lim, s, t, p, side = C.c_float(np.inf), C.c_float(0), C.c_float(0), (C.c_float * 4)(), C.c_int(0)
-        ok = self.lib.pto_triangle_intersects_side(C.c_void_p(self.tris.ctypes.data + 336 * tri), self.origin, _c4(direction),
-                                                   C.byref(lim), C.byref(s), C.byref(t), p, C.byref(side))
-        assert ok and _same_words([s.value, t.value], [b.s, b.t]) and _same_words(tuple(p), tuple(b.point)), \
-            f"the yardstick's own primary ray does not reproduce the hit of sample ({gx}, {gy}, {it})"
-        return 1 if side.value else 0
+        return self.side_by_primary_ray(tri, b.s, b.t, b.point, gx, gy, it)
 
     def sample(self, gx, gy, it):
         """dict(hit, triangle_id, material_id, front, point, ns, s, t, albedo (None: no bit-exact one), sky)"""
@@ -246,18 +201,13 @@ def scene(name):
     import warnings
     from opencl_pathtracer_amd import bvh_create, scenes
     import bvh_stress_cases as stress
-    import scene_update_cases as U
+    from gpu_cases import cached_scene
     if name not in _scenes:
         if name == "one_triangle":
             sc = scenes.cornell_box(W, H)
             sc.triangulation = scenes._concat_tris([sc.triangulation[5:6]])
             sc = bvh_create(sc)
             assert sc.bvh["isLeaf"][0] and len(sc.bvh) == 1
-        elif name == "big_leaf":
-            sc = bvh_create(U.big_leaf_scene(W, H))
-            assert sc.bvh["nbTriangles"][sc.bvh["isLeaf"] != 0].max() >= 9
-        elif name == "empty_leaves":
-            sc = U.with_empty_leaves(scene("cornell"))
         elif name == "deep_chain":
             sc = scenes.cornell_box(W, H)
             sc.triangulation = stress.make("deep_chain_27", 0, 56)
@@ -270,7 +220,7 @@ def scene(name):
         elif name == "feat_two_sided_from_behind":
             sc = behind_the_sheet(scene("feat_two_sided"))
         else:
-            sc = bvh_create(scenes.build(name, W, H))
+            sc = cached_scene(name, W, H)
         _scenes[name] = sc
     return _scenes[name]
 

@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 
 from opencl_pathtracer_amd import backend, structs as S
+from f32_cases import camera_direction, fma as _fma, mad as _mad
 import oracle_ffi as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -118,34 +119,6 @@ def ray_direction(lib, origin, direction):
     return out
 
 
-def _round_f32(x):
-    """An exact rational to the nearest float (ties to even): through a double first, then corrected among its neighbours."""
-    from fractions import Fraction
-    c = f32(float(x))
-    best = None
-    for cand in (np.nextafter(c, f32(-np.inf)), c, np.nextafter(c, f32(np.inf))):
-        if not np.isfinite(cand):
-            continue
-        err = abs(Fraction(float(cand)) - x)
-        even = (int(np.array(cand, f32).view(np.uint32)) & 1) == 0
-        if best is None or err < best[0] or (err == best[0] and even):
-            best = (err, cand)
-    return f32(best[1])
-
-
-def _fma(a, b, c):
-    """fmaf(a, b, c): one rounding of the exact a * b + c"""
-    from fractions import Fraction
-    return _round_f32(Fraction(float(a)) * Fraction(float(b)) + Fraction(float(c)))
-
-
-def _mad(a, s, c, fused):
-    """a * s + c per component in float: one rounding (the reference's default build fuses it) or two"""
-    if fused:
-        return np.array([_fma(x, f32(s), y) for x, y in zip(a, c)], f32)
-    return ((a * f32(s)).astype(f32) + c).astype(f32)
-
-
 def _length4(lib, v):
     """length(float4) of the platform library as the oracle restates it: the hardware square root of the fma-chain dot product
     (squared lengths in the normal range, which is all these scenes have)"""
@@ -167,9 +140,9 @@ def path_queries(lib, sc, w, h, depth, x, y, iteration, default_arithmetic):
     seed = C.c_int32(lib.pto_initialize_random_seed(x, y, w, h, iteration))
     sample = (C.c_float * 2)()
     lib.pto_sampler(S.JITTERED, x, y, w, h, iteration, C.byref(seed), sample)
-    cam = [np.array(v, f32).reshape(4) for v in (sc.cameraPosition, sc.cameraDirection, sc.cameraRight, sc.cameraUp)]
-    shot = _mad(cam[3], sample[1], _mad(cam[2], sample[0], cam[1], default_arithmetic), default_arithmetic)
-    queries = [(cam[0], ray_direction(lib, cam[0], shot), float("inf"), False, bounces[0].triangle_id if bounces else None, 0)]
+    eye = np.array(sc.cameraPosition, f32).reshape(4)
+    shot = camera_direction(sc, sample, default_arithmetic)
+    queries = [(eye, ray_direction(lib, eye, shot), float("inf"), False, bounces[0].triangle_id if bounces else None, 0)]
     for k, b in enumerate(bounces):
         point, out = np.array(b.point[:], f32), np.array(b.out_dir[:], f32)
         if light is not None:

@@ -22,14 +22,11 @@ import ctypes as C
 import numpy as np
 
 from opencl_pathtracer_amd import structs as S
+from f32_cases import c4 as _c4
 import oracle_ffi as O
 
 f32 = np.float32
 MISS = 0xFFFFFFFF
-
-
-def _c4(v):
-    return (C.c_float * 4)(*[float(x) for x in v])
 
 
 def _signs(d):

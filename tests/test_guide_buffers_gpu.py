@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 
 from opencl_pathtracer_amd import Backend, PtmiError, backend, bvh_create, scenes, structs as S
+from gpu_cases import assert_same_state, state
+import gpu_cases
 import guide_cases as G
 import scene_update_cases as U
 
@@ -20,10 +22,8 @@ ARITHMETICS = pytest.mark.parametrize("flags", [0, DA], ids=["strict", "default"
 SAMPLERS = pytest.mark.parametrize("sampler", [S.JITTERED, S.UNIFORM], ids=["jittered", "uniform"])
 
 
-def context(sc, depth=4, flags=0, sampler=S.JITTERED, devices=None, width=W, height=H):
-    be = Backend().setup_context(width, height, depth, sc.lightsSize, sampler=sampler, flags=flags, devices=devices)
-    be.initialize_memory(sc)
-    return be
+def context(sc, width=W, height=H, **kw):
+    return gpu_cases.context(sc, width, height, **kw)
 
 
 def assert_equal(got, want, excluded=None):
@@ -201,18 +201,6 @@ def test_a_page_locked_plane_is_filled_in_place():
 
 
 # ---------------------------------------------------------------------------------------------- guides and renders
-
-def state(be):
-    color, count = be.read_image()
-    return dict(color=color.view(np.uint32).copy(), count=count.copy(), stats=[s.copy() for s in be.read_statistics()], counters=be.counters())
-
-
-def assert_same_state(a, b):
-    assert a["counters"] == b["counters"], (a["counters"], b["counters"])
-    for x, y in zip(a["stats"], b["stats"]):
-        assert np.array_equal(x, y)
-    assert np.array_equal(a["count"], b["count"]) and np.array_equal(a["color"], b["color"])
-
 
 def test_guides_are_invisible_to_renders():
     sc, y = G.scene("cornell"), G.yardstick("cornell")

@@ -2,7 +2,6 @@
 uint32 words), in both arithmetics and for both kinds, on the scenes that take each path of the kernel; and what the feature
 promises around the kernel - queries change nothing that was rendered, they follow ptmi_update_triangles, errors leave the
 context rendering as before.  The walk of a (scene, arithmetic, kind) is computed once and shared."""
-import copy
 import warnings
 
 import numpy as np
@@ -10,6 +9,8 @@ import pytest
 
 from opencl_pathtracer_amd import Backend, PtmiError, backend, bvh_create, scenes, structs as S
 import bvh_stress_cases as stress
+from gpu_cases import assert_same_state, cached_scene, state
+import gpu_cases
 import ray_query_cases as Q
 import scene_update_cases as U
 
@@ -29,11 +30,6 @@ def scene(name):
             sc.triangulation = scenes._concat_tris([sc.triangulation[5:6]])
             sc = bvh_create(sc)
             assert sc.bvh["isLeaf"][0] and len(sc.bvh) == 1
-        elif name == "big_leaf":
-            sc = bvh_create(U.big_leaf_scene(W, H))
-            assert sc.bvh["nbTriangles"][sc.bvh["isLeaf"] != 0].max() >= 9
-        elif name == "empty_leaves":
-            sc = U.with_empty_leaves(scene("cornell"))
         elif name == "deep_chain":
             sc = scenes.cornell_box(W, H)
             sc.triangulation = stress.make("deep_chain_27", 0, 56)
@@ -44,7 +40,7 @@ def scene(name):
                 warnings.simplefilter("ignore")  # (the hostile scenes divide 0 by 0 on purpose, as the importer would)
                 sc = bvh_create(scenes.add_zero_area_triangles(scenes.build("fuzz5h_l1", W, H), 24))
         else:
-            sc = bvh_create(scenes.build(name, W, H))
+            sc = cached_scene(name, W, H)
         _scenes[name] = sc
     return _scenes[name]
 
@@ -72,10 +68,8 @@ def wanted(name, flags, any_hit, sc=None, rays=None):
     return _want[key]
 
 
-def context(sc, depth=4, flags=0, devices=None):
-    be = Backend().setup_context(W, H, depth, sc.lightsSize, flags=flags, devices=devices)
-    be.initialize_memory(sc)
-    return be
+def context(sc, **kw):
+    return gpu_cases.context(sc, W, H, **kw)
 
 
 def query(be, rays, any_hit=False, out=None):
@@ -105,6 +99,26 @@ def test_batch_sizes_on_cornell(flags, any_hit, monkeypatch):
         monkeypatch.delenv("PTMI_QUERY_MAX_BLOCKS")
         # a later, smaller batch reuses the scratch; a middle slice is its own batch
         assert_equal(query(be, rays[100:165], any_hit), want[100:165])
+    finally:
+        be.release()
+
+
+@pytest.mark.parametrize("page_locked", [False, True], ids=["pageable", "page_locked"])
+def test_the_scratch_grows_and_is_reused(page_locked):
+    """257 rays, then 1100 - the cached 1000 and their first 100 again, past the 1024-ray floor of the context's buffers, which
+    are freed and regrown - then 257 again, into an ordinary array and into one the caller has page-locked."""
+    rays, want = rays_of("cornell"), wanted("cornell", DA, False)
+    rays, want = np.concatenate([rays, rays[:100]]), np.concatenate([want, want[:100]])
+    out = np.zeros(1100, S.RAY_HIT)
+    be = context(scene("cornell"), flags=DA)
+    try:
+        if page_locked:
+            be.pin_host_buffer(out)
+        for n in (257, 1100, 257):
+            out[:] = np.zeros(1, S.RAY_HIT)
+            assert_equal(query(be, rays[:n], out=out[:n]), want[:n])
+        if page_locked:
+            be.unpin_host_buffer(out)
     finally:
         be.release()
 
@@ -241,18 +255,6 @@ def test_a_page_locked_destination_is_filled_in_place():
 
 
 # ---------------------------------------------------------------------------------------------- queries and renders
-
-def state(be):
-    color, count = be.read_image()
-    return dict(color=color.view(np.uint32).copy(), count=count.copy(), stats=[s.copy() for s in be.read_statistics()], counters=be.counters())
-
-
-def assert_same_state(a, b):
-    assert a["counters"] == b["counters"], (a["counters"], b["counters"])
-    for x, y in zip(a["stats"], b["stats"]):
-        assert np.array_equal(x, y)
-    assert np.array_equal(a["count"], b["count"]) and np.array_equal(a["color"], b["color"])
-
 
 def test_queries_are_invisible_to_renders():
     flags = 0

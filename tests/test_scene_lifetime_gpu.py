@@ -9,21 +9,19 @@ must be what a fresh context that only ever saw B gives for the same calls.
 import numpy as np
 import pytest
 
-from opencl_pathtracer_amd import Backend, PtmiError, bvh_create, scenes
+from opencl_pathtracer_amd import Backend, PtmiError
+from gpu_cases import assert_same_state, cached_scene, state
 import ray_query_cases as Q
 
 pytestmark = pytest.mark.gpu
 W, H, DEPTH = 16, 16, 3
 STATE, UNSUPPORTED = -6, -7
-_cache = {}
 
 
 def scene(name):
-    if name not in _cache:
-        sc = bvh_create(scenes.build(name, W, H))
-        with np.errstate(all="ignore"):
-            _cache[name] = (sc, Q.mixed_rays(sc, 8, W, H))
-    return _cache[name]
+    sc = cached_scene(name, W, H)
+    with np.errstate(all="ignore"):
+        return sc, Q.mixed_rays(sc, 8, W, H)
 
 
 def query(be, rays):
@@ -36,9 +34,7 @@ def life_with(be, name):
     be.render(0, 2)
     be.update_triangles(sc.triangulation)
     hits = query(be, rays)
-    color, count = be.read_image()
-    return dict(hits=hits, color=color.view(np.uint32).copy(), count=count.copy(), stats=[s.copy() for s in be.read_statistics()],
-                counters=be.counters())
+    return dict(state(be), hits=hits)
 
 
 @pytest.mark.parametrize("devices", [None, [0, 0]], ids=["one_device", "two_devices"])
@@ -77,8 +73,6 @@ def test_a_second_upload_starts_from_nothing(devices):
         got = life_with(be, "tris500")
     finally:
         be.release()
-    assert got["counters"] == want["counters"], (got["counters"], want["counters"])
     assert np.array_equal(got["hits"], want["hits"])
-    assert all(np.array_equal(x, y) for x, y in zip(got["stats"], want["stats"]))
-    assert np.array_equal(got["count"], want["count"]) and np.array_equal(got["color"], want["color"])
+    assert_same_state(got, want)
     assert got["count"].sum() > 0 and got["counters"]["paths"] > 0  # (the comparison is not of two empty images)

@@ -10,54 +10,23 @@ import copy
 import numpy as np
 import pytest
 
-from opencl_pathtracer_amd import Backend, PtmiError, backend, bvh_create, scenes, structs as S
+from opencl_pathtracer_amd import Backend, PtmiError, backend, structs as S
+from gpu_cases import assert_same_state as assert_same, cached_scene, state
+import gpu_cases
 import scene_update_cases as U
 
 pytestmark = pytest.mark.gpu
 W, H = 64, 48
 DA = backend.FLAG_DEFAULT_ARITHMETIC
 INVALID_ARGUMENT, BAD_SCENE, STATE, UNSUPPORTED = -1, -5, -6, -7
-_cache = {}
 
 
 def scene(name):
-    if name not in _cache:
-        if name == "big_leaf":
-            sc = bvh_create(U.big_leaf_scene(W, H))
-            assert sc.bvh["nbTriangles"][sc.bvh["isLeaf"] != 0].max() >= 9
-        elif name == "empty_leaves":
-            sc = U.with_empty_leaves(scene("cornell"))
-        elif name == "textured":
-            sc = bvh_create(scenes.feature_scene("textured", W, H))
-        else:
-            sc = bvh_create(scenes.build(name, W, H))
-        _cache[name] = sc
-    return _cache[name]
+    return cached_scene(name, W, H)
 
 
-def context(sc, depth=4, flags=0, sampler=S.JITTERED, super_sampling=False, devices=None):
-    be = Backend().setup_context(W, H, depth, sc.lightsSize, sampler, super_sampling=super_sampling, flags=flags, devices=devices)
-    be.initialize_memory(sc)
-    return be
-
-
-def state(be, variance=False):
-    color, count = be.read_image()
-    out = dict(color=color.view(np.uint32).copy(), count=count.copy(), stats=[s.copy() for s in be.read_statistics()], counters=be.counters())
-    if variance:
-        out["variance"] = be.read_variance().view(np.uint32).copy()
-    return out
-
-
-def assert_same(a, b):
-    assert a["counters"] == b["counters"], (a["counters"], b["counters"])
-    for x, y in zip(a["stats"], b["stats"]):
-        assert np.array_equal(x, y)
-    assert np.array_equal(a["count"], b["count"])
-    diff = int((a["color"] != b["color"]).any(axis=-1).sum())
-    assert diff == 0, f"{diff} pixels differ"
-    if "variance" in a or "variance" in b:
-        assert np.array_equal(a["variance"], b["variance"])
+def context(sc, **kw):
+    return gpu_cases.context(sc, W, H, **kw)
 
 
 def moved_camera(sc, step=1):
@@ -128,7 +97,7 @@ def test_set_camera_with_the_other_kernel_and_with_adaptive_sampling(kw):
 def moved_triangles(name, seed=7):
     sc = scene(name)
     tris = U.displaced(sc.triangulation, seed, amplitude=0.01 if name == "tris20k" else 0.02)
-    if name == "textured":
+    if name == "feat_textured":
         rs = np.random.default_rng(seed)
         for field in ("UVP1", "UVP2", "UVP3", "UVN1", "UVN2", "UVN3"):
             tris[field] = (tris[field] + rs.uniform(-0.3, 0.3, tris[field].shape)).astype(np.float32)
@@ -146,8 +115,8 @@ UPDATE_CASES = {
     "tris20k-precomputed": ("tris20k", 0, 5, False),
     "tris20k-precomputed-default": ("tris20k", DA, 5, False),
     "tris20k-generic": ("tris20k", 0, 5, True),
-    "textured": ("textured", 0, 4, False),
-    "textured-default": ("textured", DA, 4, False),
+    "textured": ("feat_textured", 0, 4, False),
+    "textured-default": ("feat_textured", DA, 4, False),
     "big_leaf": ("big_leaf", 0, 4, False),
     "empty_leaves": ("empty_leaves", 0, 4, False),
 }
