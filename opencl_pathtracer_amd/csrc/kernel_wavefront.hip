@@ -439,8 +439,10 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
         if (kTos) tos = *sp;
     };
     // `cur` refers to a leaf and the lane's triangle range is free: the range takes the leaf and `cur` what the stack holds next.
-    // culled: this leaf is counted instead (node_step) - and what is popped in its place may be a leaf again, which carries no
-    // mark: its triangles are tested.
+    // culled: this leaf is counted instead (node_step) - and what is popped in its place may be a leaf again, whose triangles are
+    // tested: a closest-hit query pushed it because it did not satisfy the rule then (node_step counts the ones that do instead
+    // of pushing them), and it is not judged again against the limit of now (a stack word has no bit for a mark, and the box
+    // is not at hand); a shadow query's pushed leaves are never judged.
     auto enter_leaf = [&](bool culled) {
         if (kCull && culled) {
             p_tri += ref_leaf_count(cur);
@@ -553,45 +555,52 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
         // dir[cutAxis] > 0 (:663) from a per-ray word of the three signs (one bit test; selected from the three sign masks
         // the box tests hold it took three compares and five scalar instructions)
         const bool fwd = ((dir_signs >> n.axis) & 1u) != 0;
-        // (Both distances BEFORE the box tests, which then use up the box registers in place: two registers across the tests.
-        // Behind them the twelve box registers stay alive through the tests, and the plain instantiation spills eighteen
-        // registers more around the loop: 23 against a budget of 8, tests/test_resources.py.)
+        // The squared distances of the origin from the two boxes, for the rule below: either test makes them from its own slab
+        // differences (three medians and three multiply-adds each; leaf_cull.h: box_distance2_from_slabs).
         float d2_1 = 0, d2_2 = 0;
-        if (kCull) {
-            d2_1 = ptmi_cull::box_distance2(n.lo1, n.hi1, r.o.x, r.o.y, r.o.z);
-            d2_2 = ptmi_cull::box_distance2(n.lo2, n.hi2, r.o.x, r.o.y, r.o.z);
-            asm volatile("" : "+v"(d2_1), "+v"(d2_2));  // (made HERE: left alone, the compiler sinks them behind the tests)
-        }
         bool h1, h2;
         if (!wave_exact) {
-            h1 = box_hit_ordered(n.lo1, n.hi1, r, limit);
-            h2 = box_hit_ordered(n.lo2, n.hi2, r, limit);
+            h1 = box_hit_ordered(n.lo1, n.hi1, r, limit, kCull ? &d2_1 : nullptr);
+            // (the first distance made HERE, before the second box's differences exist: left alone, the compiler holds both
+            // boxes' differences at once - spilled registers around the loop, tools/kernel_resources.py: plain 8 -> 5, 64 lanes 9 -> 4)
+            if (kCull) asm volatile("" : "+v"(d2_1));
+            h2 = box_hit_ordered(n.lo2, n.hi2, r, limit, kCull ? &d2_2 : nullptr);
         } else {
-            h1 = box_hit(n.lo1, n.hi1, (n.ref1 & REF_EMPTY) != 0, r, limit);
-            h2 = box_hit(n.lo2, n.hi2, (n.ref2 & REF_EMPTY) != 0, r, limit);
+            h1 = box_hit(n.lo1, n.hi1, (n.ref1 & REF_EMPTY) != 0, r, limit, kCull ? &d2_1 : nullptr);
+            h2 = box_hit(n.lo2, n.hi2, (n.ref2 & REF_EMPTY) != 0, r, limit, kCull ? &d2_2 : nullptr);
         }
         p_bbx += 2;
-        // The leaf this step chooses (near child or only child hit - not one it pops) is CULLED when the record certifies it and
-        // its box, still in the step's registers, lies beyond the limit (leaf_cull.h: then every triangle of it is rejected):
-        // the lane counts its triangles and pops, as it does after the leaf's last pass.  Closest-hit and shadow queries alike
-        // (acceptance is `nsd <= limit` for both, cl:537; a shadow query that accepts nothing counts the whole leaf).
-        bool culled = false;
+        // The leaf this step chooses (near child or only child hit) is CULLED when the record certifies it and its box, still in
+        // the step's registers, lies beyond the limit (leaf_cull.h: then every triangle of it is rejected): the lane counts its
+        // triangles and pops, as it does after the leaf's last pass.  Closest-hit and shadow queries alike (acceptance is
+        // `nsd <= limit` for both, cl:537; a shadow query that accepts nothing counts the whole leaf).
+        // The FAR child of a step that hits both is judged by the same rule where it would be pushed, and then counted instead
+        // (far_counted): a closest-hit query's limit only shrinks, so the rule still holds when the entry would be popped, and
+        // every entry such a query pushes is popped and tested in full, so the count is the same sum.  Not in a shadow query,
+        // which ends at its first accepted triangle with the leaves on its stack uncounted (its rays do not carry kCullPushed).
+        bool culled = false, far_counted = false;
         if (kCull) {
-            // (the ray's own part of the rule was evaluated where the ray was set up: bits 3 and 4 of dir_signs)
+            // (the ray's own part of the rule was evaluated where the ray was set up: bits 3 to 5 of dir_signs)
             const uint32_t cull_bits = n.cull & (dir_signs >> 3) & sc.leaf_cull;
             const bool first = fwd ? h1 : !h2;  // which child the step chooses, when it chooses one
             const bool certified = (cull_bits & (first ? ptmi_cull::kCullChild1 : ptmi_cull::kCullChild2)) != 0u;
             culled = (h1 | h2) & certified & ptmi_cull::box_is_beyond(first ? d2_1 : d2_2, limit);
+            const bool far_certified = (cull_bits & ptmi_cull::kCullPushed) != 0u && (cull_bits & (fwd ? ptmi_cull::kCullChild2 : ptmi_cull::kCullChild1)) != 0u;
+            far_counted = h1 & h2 & far_certified & ptmi_cull::box_is_beyond(fwd ? d2_2 : d2_1, limit);
         }
         // (every choice as a select on the two hit masks themselves: combined into new booleans first - both, neither - the
         // compiler builds them as 0 / 1 integers in vector registers: seven instructions more per step)
         const uint32_t far_ref = fwd ? n.ref2 : n.ref1;
         sp[kWfBlock] = far_ref;
-        uint32_t* const pushed = sp + kWfBlock;
+        uint32_t* const pushed = far_counted ? sp : sp + kWfBlock;
         const uint32_t child = fwd ? (h1 ? n.ref1 : n.ref2) : (h2 ? n.ref2 : n.ref1);  // near child if it was hit, else the far one
-        // both hit: the far child becomes the top; one hit: nothing moves; none: the step pops
+        if (kCull && far_counted) {
+            p_tri += ref_leaf_count(far_ref);
+            if (STATS) culled_items += ref_leaf_count(far_ref);
+        }
+        // both hit: the far child becomes the top (unless it was counted); one hit: nothing moves; none: the step pops
         cur = h1 ? child : (h2 ? child : cur);
-        if (kTos) tos = h1 ? (h2 ? far_ref : tos) : tos;
+        if (kTos) tos = h1 ? (h2 ? (far_counted ? tos : far_ref) : tos) : tos;
         sp = h1 ? (h2 ? pushed : sp) : sp;
         if (!(h1 | h2)) pop();
         if (ref_is_leaf(cur)) enter_leaf(culled);  // (the triangle range of a lane that takes node steps is free)
@@ -846,8 +855,10 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
             if (new_ray) {
                 ray_set_direction(r, new_direction);
                 dir_signs = (r.d.x > 0 ? 1u : 0u) | (r.d.y > 0 ? 2u : 0u) | (r.d.z > 0 ? 4u : 0u);
-                // ... and, above the signs, the two cull bits of a node record this ray honours (leaf_cull.h: ray_may_cull)
-                if (kCull && ptmi_cull::ray_may_cull(r.o.x, r.o.y, r.o.z, r.o.w, r.d.w)) dir_signs |= (ptmi_cull::kCullChild1 | ptmi_cull::kCullChild2) << 3;
+                // ... and, above the signs, the cull bits of a node record this ray honours (leaf_cull.h: ray_may_cull): the two
+                // children, and - a closest-hit query only - the bit that lets a step count the far child instead of pushing it
+                if (kCull && ptmi_cull::ray_may_cull(r.o.x, r.o.y, r.o.z, r.o.w, r.d.w))
+                    dir_signs |= (ptmi_cull::kCullChild1 | ptmi_cull::kCullChild2 | (shadow ? 0u : ptmi_cull::kCullPushed)) << 3;
                 // A ray that is not a number - a refraction at |cos| = 1 + 1 ulp takes the square root of a negative (cl:235),
                 // a hit on a fake plane 1e30 away overflows - makes every triangle test compute a NaN distance, and the
                 // reference ACCEPTS those (its rejections are comparisons, cl:533-567): from then on nothing is "too far" and

@@ -36,6 +36,9 @@ constexpr double kKappaMax = 0x1p-13, kEpsAbsMax = 2.0e-3;
 // DNode::cull of an inner record: the children that are cullable leaves, and "this record's bits were computed" (a refit
 // recomputes the bits of the records that carry them and leaves the others alone: scene_refit_common.h)
 constexpr uint32_t kCullChild1 = 1u, kCullChild2 = 2u, kCullComputed = 4u;
+// DScene::leaf_cull, the mask the kernel ANDs a record's bits with: the children it may cull where the step chooses them itself,
+// and - in the position of kCullComputed, which every record that carries a child bit has set - "also where it would push them".
+constexpr uint32_t kCullPushed = kCullComputed;
 
 PTMI_HD float box_distance2(const float lo[3], const float hi[3], float ox, float oy, float oz)
 {
@@ -44,6 +47,24 @@ PTMI_HD float box_distance2(const float lo[3], const float hi[3], float ox, floa
     const float dy = fmaxf(fmaxf(lo[1] - oy, oy - hi[1]), 0.0f);
     const float dz = fmaxf(fmaxf(lo[2] - oz, oz - hi[2]), 0.0f);
     return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+}
+
+// The same value from the differences a slab test forms anyway: per axis the pair (lo - o, hi - o), in either order.  Their
+// median with 0 is lo - o where that is positive, hi - o where that is negative - the exact negation of o - hi, and the sign
+// goes in the square - and 0 between: for lo <= hi, box_distance2 bit for bit (tests/test_leaf_cull_slab_distance.py).
+// (A NaN difference: whatever the median instruction returns; such a ray does not cull, ray_may_cull.)
+PTMI_HD float median_with_zero(float a, float b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_fmed3f(a, 0.0f, b);
+#else
+    return fmaxf(fminf(a, b), fminf(fmaxf(a, b), 0.0f));
+#endif
+}
+PTMI_HD float box_distance2_from_slabs(float ax, float bx, float ay, float by, float az, float bz)
+{
+    const float mx = median_with_zero(ax, bx), my = median_with_zero(ay, by), mz = median_with_zero(az, bz);
+    return fmaf(mz, mz, fmaf(my, my, mx * mx));
 }
 
 // The part of the rule that is the ray's alone (the kernel evaluates it once, where it sets the ray up).  The origin: above.

@@ -110,8 +110,9 @@ int ptmi_setup_context(ptmi_ctx** out, const ptmi_config* cfg)
         }
     }
     // env: developer switch - 0: the wavefront kernel fetches and tests the triangles of every leaf it reaches (leaf_cull.h);
-    // 1: it culls in every scene whose records carry the bits, also where upload_scene would not expect it to pay
-    if (const char* v = std::getenv("PTMI_LEAF_CULL")) ctx->leaf_cull = v[0] != '0' ? 1 : 0;
+    // 1: it culls the leaves a node step chooses itself, 2: also the ones it would push - both in every scene whose records
+    // carry the bits, also where upload_scene would not expect it to pay (anything else reads as 1, as it always did)
+    if (const char* v = std::getenv("PTMI_LEAF_CULL")) ctx->leaf_cull = v[0] == '0' ? 0 : v[0] == '2' ? 2 : 1;
     *out = ctx;
     return PTMI_OK;
 }

@@ -13,6 +13,7 @@
 
 #include "ptmi_detmath.h"
 #include "ptmi_internal.h"
+#include "leaf_cull.h"
 
 // ---- the two arithmetic modes ---------------------------------------------------------------------------
 // The reference compiles its kernel at run time with no floating-point option (PathTracer_OpenCL.cpp:292-314), so what it
@@ -227,22 +228,28 @@ __device__ __forceinline__ V4 put_in_same_hemisphere(V4 v, V4 n)
 // 0*inf compare false exactly where they do there); the early returns become
 // one conjunction because the function has no side effects besides the counter,
 // which the caller bumps.
-__device__ __forceinline__ bool box_hit(const float lo[3], const float hi[3], bool is_empty, const Ray& r, float limit)
+// distance2 (where asked for): the squared distance of the ray's origin from the box, ptmi_cull::box_distance2 bit for bit where
+// lo <= hi, from the six differences of the slabs (each rounded by itself, as the test uses it).
+__device__ __forceinline__ bool box_hit(const float lo[3], const float hi[3], bool is_empty, const Ray& r, float limit, float* distance2 = nullptr)
 {
     // bitwise & | on the comparison results: they become scalar ops on lane masks; && || would be compiled
     // into a chain of ~30 tiny divergent blocks (measured: 5 % slower)
     const bool px = r.d.x > 0, py = r.d.y > 0, pz = r.d.z > 0;
-    float tmin = ((px ? lo[0] : hi[0]) - r.o.x) * r.ix;
-    float tmax = ((px ? hi[0] : lo[0]) - r.o.x) * r.ix;
+    const float xn = (px ? lo[0] : hi[0]) - r.o.x, xf = (px ? hi[0] : lo[0]) - r.o.x;
+    const float yn = (py ? lo[1] : hi[1]) - r.o.y, yf = (py ? hi[1] : lo[1]) - r.o.y;
+    const float zn = (pz ? lo[2] : hi[2]) - r.o.z, zf = (pz ? hi[2] : lo[2]) - r.o.z;
+    if (distance2) *distance2 = ptmi_cull::box_distance2_from_slabs(xn, xf, yn, yf, zn, zf);
+    float tmin = xn * r.ix;
+    float tmax = xf * r.ix;
     bool miss = (tmin < 0) & (tmax < 0);
-    const float tymin = ((py ? lo[1] : hi[1]) - r.o.y) * r.iy;
-    const float tymax = ((py ? hi[1] : lo[1]) - r.o.y) * r.iy;
+    const float tymin = yn * r.iy;
+    const float tymax = yf * r.iy;
     miss |= (tymin < 0) & (tymax < 0);
     miss |= (tmin > tymax) | (tymin > tmax);
     tmin = tymin > tmin ? tymin : tmin;
     tmax = tymax < tmax ? tymax : tmax;
-    const float tzmin = ((pz ? lo[2] : hi[2]) - r.o.z) * r.iz;
-    const float tzmax = ((pz ? hi[2] : lo[2]) - r.o.z) * r.iz;
+    const float tzmin = zn * r.iz;
+    const float tzmax = zf * r.iz;
     miss |= (tzmin < 0) & (tzmax < 0);
     miss |= (tmin > tzmax) | (tzmin > tmax);
     tmin = tzmin > tmin ? tzmin : tmin;
@@ -263,7 +270,9 @@ __device__ __forceinline__ bool box_hit(const float lo[3], const float hi[3], bo
 // An EMPTY box (isEmpty: never hit, FullKernel.cl:68) is stored for this form as lo = +inf, hi = -inf, which gives
 // tmin = +inf > tmax = -inf for either direction sign, so no flag has to be tested.
 typedef float ptmi_f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ bool box_hit_ordered(const float lo[3], const float hi[3], const Ray& r, float limit)
+// distance2 (where asked for): the squared distance of the ray's origin from the box, ptmi_cull::box_distance2 bit for bit, from
+// the six differences of the slabs (each rounded by itself, as the test uses it) - three medians and three multiply-adds.
+__device__ __forceinline__ bool box_hit_ordered(const float lo[3], const float hi[3], const Ray& r, float limit, float* distance2 = nullptr)
 {
     // two-wide arithmetic spelled out (v_pk_add_f32 / v_pk_mul_f32: same IEEE operations, half the instructions):
     // (x, y) of the near planes, (x, y) of the far planes, and (near, far) of z
@@ -271,7 +280,9 @@ __device__ __forceinline__ bool box_hit_ordered(const float lo[3], const float h
     const ptmi_f2 o_xy = {r.o.x, r.o.y}, i_xy = {r.ix, r.iy}, o_zz = {r.o.z, r.o.z}, i_zz = {r.iz, r.iz};
     const ptmi_f2 near_xy = {px ? lo[0] : hi[0], py ? lo[1] : hi[1]}, far_xy = {px ? hi[0] : lo[0], py ? hi[1] : lo[1]};
     const ptmi_f2 z_nf = {pz ? lo[2] : hi[2], pz ? hi[2] : lo[2]};
-    const ptmi_f2 tn = (near_xy - o_xy) * i_xy, tf = (far_xy - o_xy) * i_xy, tz = (z_nf - o_zz) * i_zz;
+    const ptmi_f2 dn = near_xy - o_xy, df = far_xy - o_xy, dz = z_nf - o_zz;
+    if (distance2) *distance2 = ptmi_cull::box_distance2_from_slabs(dn.x, df.x, dn.y, df.y, dz.x, dz.y);
+    const ptmi_f2 tn = dn * i_xy, tf = df * i_xy, tz = dz * i_zz;
     const float tmin = __builtin_fmaxf(__builtin_fmaxf(tn.x, tn.y), tz.x);
     const float tmax = __builtin_fminf(__builtin_fminf(tf.x, tf.y), tz.y);
     return !((tmax < 0) | (tmin > tmax) | (tmin > limit));

@@ -219,7 +219,7 @@ struct DScene {
     uint32_t boxes_ordered;    // every non-empty child box is finite with pMin <= pMax (see box_hit_ordered)
     uint32_t russian_roulette; // PTMI_FLAG_RUSSIAN_ROULETTE
     uint32_t source_seed;      // PTMI_FLAG_SOURCE_SEED
-    uint32_t leaf_cull;        // mask of the DNode::cull bits the wavefront kernel honours (leaf_cull.h): 3, or 0 = culling is off
+    uint32_t leaf_cull;        // mask of the DNode::cull bits the wavefront kernel honours (leaf_cull.h): 3 = the children, + 4 = also where they would be pushed; 0 = culling is off
 };
 
 // The integrator's device code exists once per ARITHMETIC MODE (ptmi_device.hpp: strict / the reference's default OpenCL

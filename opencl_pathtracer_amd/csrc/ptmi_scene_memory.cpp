@@ -200,7 +200,8 @@ int upload_scene(ptmi_ctx* ctx, DeviceState& d, const Relayout& lay, const ptmi_
     constexpr uint32_t kCullMinLeaves = 1024;
     const bool cull_bits = lay.tris_precomputed && lay.literal_kernel_reason.empty();
     const bool cull = ctx->leaf_cull < 0 ? lay.cullable_leaves >= kCullMinLeaves : ctx->leaf_cull != 0;
-    ds.leaf_cull = (cull && cull_bits) ? (ptmi_cull::kCullChild1 | ptmi_cull::kCullChild2) : 0u;
+    // (forced to 1, the kernel culls only the leaves a node step chooses itself - A/B against the pushed ones in one binary)
+    ds.leaf_cull = (cull && cull_bits) ? (ptmi_cull::kCullChild1 | ptmi_cull::kCullChild2 | (ctx->leaf_cull == 1 ? 0u : ptmi_cull::kCullPushed)) : 0u;
     ds.root_ref = lay.root_ref;
     ds.width = ctx->cfg.image_width;
     ds.height = ctx->cfg.image_height;

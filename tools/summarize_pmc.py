@@ -30,7 +30,7 @@ for key in cfg:
     if m:
         cfg[key] = m.group(1) if key in ("scene", "arithmetic") else int(m.group(1))
 out["_config"] = cfg
-out["_note"] = ("rocprofv3 --pmc <one group per run> --kernel-trace -- python3 bench.py --steps 2 --warmup 1 "
+out["_note"] = ("rocprofv3 --pmc <one group per run> -- python3 bench.py --steps 2 --warmup 1 "
                 "--no-cpu-baseline --no-boundary " + extra + " (32 spp per launch, 1080p); per-launch means of "
                 "render_wavefront_kernel; FETCH_SIZE/WRITE_SIZE in KB; GRBM_GUI_ACTIVE summed over the 8 XCDs")
 print(json.dumps(out, indent=1))
