@@ -252,6 +252,10 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
     //   general only: 973.6 / 941.8 / 7263 / 2659 / 1214 / 516.9
     // The general instantiations gain 3-6 % (their spilled registers also fall from 67 to 30: the allocator's doing), the plain one
     // loses 0.8 %.
+    // Tried again in the plain CULLING instantiations (`!PLAIN || CULL`), where a step can pop, count a leaf and pop again
+    // (enter_leaf) - two LDS round trips that survey() waits for: 1M triangles plain, same box, alternating, two runs each,
+    //   !PLAIN: 1045.80 / 1046.61      !PLAIN || CULL: 1032.02 / 1030.16      (-1.4 %; 96 VGPRs, 8 spilled against 4)
+    // (profiles/node_step_waits_ab.txt).  The plain instantiations stay without it.
     constexpr bool kTos = !PLAIN;
     // Leaves beyond the limit are counted instead of tested (leaf_cull.h).  An instantiation of its own: a node step pays two
     // box distances for it, which a scene whose rays meet nothing behind their hits (the Cornell box) gets nothing back for -
@@ -276,10 +280,15 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
     uint32_t* const stack_floor = &stack_mem[kHitRecordWords * kWfBlock + tid];
     *stack_floor = REF_NONE;
     // the rare fields: pointer re-derived through an opaque asm so the loads stay where they are used
+    // (Through the asm as a pointer to the GLOBAL address space: as a generic one - until this was found - its loads, and the
+    // atomics on the pointers read through it, were flat_ instructions, and a flat_ operation in path logic leaves every wait of
+    // the traversal loop's first blocks waiting for ALL outstanding loads - the node step's first quad waited for its fourth,
+    // DESIGN.md 5.  The pointers READ through it go through as_global where they are dereferenced.  The production
+    // instantiations hold no flat_ instruction: tests/test_node_step_waits.py.)
     auto cold_scene = [&]() -> const DScene& {
-        const DScene* p = scene_in_memory;
+        const PTMI_GLOBAL DScene* p = (const PTMI_GLOBAL DScene*)scene_in_memory;
         asm volatile("" : "+s"(p));
-        return *p;
+        return *(const DScene*)p;
     };
     // The closest-hit record (point, s, t, triangle, side) changes only when a closer hit is accepted and is read
     // only by path logic: it lives in LDS in front of the stack, [field][lane], not in registers of the hot loop.
@@ -377,7 +386,7 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
             // (Three global atomics per path on a handful of hot bins cost 3 % on the 1M-triangle scene and 79 % on the
             // Cornell box: atomics of different XCDs on one address are resolved memory-side.)
             if (stage_stats != nullptr) stage_stats[slot] = pack_path_statistics(reflection, p_bbx, p_tri);
-            if (SS) cold_scene().stage_flag[slot] = 1.f;
+            if (SS) as_global(cold_scene().stage_flag)[slot] = 1.f;
         } else if (!given_up) {
             // RANDOM sampler: the sample lands on an arbitrary pixel; the reference races there (:1339-1345).  The sample
             // position is drawn again from the path's seed (the first two draws, :1137-1141) instead of being kept.
@@ -834,15 +843,15 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
                     const DScene& cs = cold_scene();
                     // the pixel the SAMPLE falls on (:1159-1161): the work-item's own with JITTERED / UNIFORM, any with RANDOM
                     const uint32_t off = owns_pixel ? gy * sc.width + gx : sample_pixel(sc, sample_x, sample_y);
-                    const float n = cs.image_ray_nb[off];
-                    const float4 vv = reinterpret_cast<const float4*>(cs.image_v)[off];
+                    const float n = as_global(cs.image_ray_nb)[off];
+                    const float4 vv = reinterpret_cast<const float4*>(as_global(cs.image_v))[off];
                     const float sigma2_n = fmaxf(fmaxf(fdiv(vv.x, n), fdiv(vv.y, n)), fdiv(vv.z, n));
                     uint32_t idx = (uint32_t)n;
                     if (idx > 1000u) idx = 1000u;  // the reference indexes past its 1001-entry table here
-                    skip = (double)lcg_random(seed) > (double)fdiv(100 * sigma2_n, cs.x2inv[idx]) + 0.05;
+                    skip = (double)lcg_random(seed) > (double)fdiv(100 * sigma2_n, as_global(cs.x2inv)[idx]) + 0.05;
                 }
                 if (skip) {
-                    if (owns_pixel) cold_scene().stage_flag[gy * sc.width + gx] = 0.f;  // returns before statistics and accumulation
+                    if (owns_pixel) as_global(cold_scene().stage_flag)[gy * sc.width + gx] = 0.f;  // returns before statistics and accumulation
                     need_path = true;
                 } else
                 if (sc.max_depth > 0) {
@@ -916,10 +925,10 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
     }
     __syncthreads();
     if (STATS) {
-        if (tid < C_COUNT) atomicAdd(&cold_scene().counters[tid], block_counters[tid]);
+        if (tid < C_COUNT) atomicAdd(&as_global(cold_scene().counters)[tid], block_counters[tid]);
     } else if (tid < kBlockCounters) {
         const uint32_t k = tid / kSplitWords, c = tid % kSplitWords;
-        if (k == 0u || block_counters[tid] != 0ull) atomicAdd(&cold_scene().counters[k * C_COUNT + c], block_counters[tid]);
+        if (k == 0u || block_counters[tid] != 0ull) atomicAdd(&as_global(cold_scene().counters)[k * C_COUNT + c], block_counters[tid]);
     }
 }
 

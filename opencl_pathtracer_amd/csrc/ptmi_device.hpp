@@ -47,6 +47,19 @@ using namespace ptmi_internal;
 
 constexpr bool kDefaultArithmetic = PTMI_DEFAULT_ARITHMETIC != 0;
 
+// A pointer the compiler cannot trace back to a kernel argument - one read out of a structure in memory - is a GENERIC pointer
+// to it: its loads and atomics become flat_ instructions, which count on both wait counters, and while one may be pending every
+// wait the compiler places waits for everything (kernel_wavefront.hip: cold_scene).  Every pointer FIELD of a
+// DScene points into device memory; this reads the field as the global pointer it is.  (Casting the generic value to the
+// global address space and back tells the compiler nothing: it folds the pair of casts, and an assumption about
+// __builtin_amdgcn_is_shared / is_private does not survive to where the address spaces are inferred either.)
+#define PTMI_GLOBAL __attribute__((address_space(1)))
+template <class T>
+__device__ __forceinline__ T* as_global(T* const& field)
+{
+    return (T*)*static_cast<PTMI_GLOBAL T* const*>(static_cast<const void*>(&field));
+}
+
 struct V4 {
     float x, y, z, w;
 };

@@ -28,9 +28,10 @@ __device__ __forceinline__ void decode_slot(uint32_t slot, uint32_t width, uint3
 // The three statistics atomics of a finished path as the reference issues them (FullKernel.cl:1319-1331).
 __device__ __forceinline__ void count_path_in_histograms(const DScene& sc, uint32_t depth, uint32_t bbx, uint32_t tri)
 {
-    atomicAdd(&sc.hist_depths[depth], 1u);
-    if (bbx < PTMI_MAX_INTERSECTION_NUMBER) atomicAdd(&sc.hist_bbx[bbx], 1u);
-    if (tri < PTMI_MAX_INTERSECTION_NUMBER) atomicAdd(&sc.hist_tri[tri], 1u);
+    // (as_global: `sc` may itself lie in memory, as the wavefront kernel's cold scene does, and its pointers are generic then)
+    atomicAdd(&as_global(sc.hist_depths)[depth], 1u);
+    if (bbx < PTMI_MAX_INTERSECTION_NUMBER) atomicAdd(&as_global(sc.hist_bbx)[bbx], 1u);
+    if (tri < PTMI_MAX_INTERSECTION_NUMBER) atomicAdd(&as_global(sc.hist_tri)[tri], 1u);
 }
 
 // A sample of the RANDOM sampler lands on an arbitrary pixel `off`; the reference races there (:1339-1345), here every update
@@ -42,11 +43,12 @@ __device__ __forceinline__ void count_path_in_histograms(const DScene& sc, uint3
 __device__ __forceinline__ void add_random_sample(const DScene& sc, uint32_t off, V4 radiance, bool super_sampling, uint32_t iteration)
 {
     // (the atomics return what the accumulators held before: sumBefore / nRayBefore of :1339-1342)
-    const V4 before = v4(atomicAdd(&sc.image_color[4 * off + 0], radiance.x), atomicAdd(&sc.image_color[4 * off + 1], radiance.y),
-                         atomicAdd(&sc.image_color[4 * off + 2], radiance.z), atomicAdd(&sc.image_color[4 * off + 3], radiance.w));
-    const float n_before = atomicAdd(&sc.image_ray_nb[off], 1.f);
+    float* const color = &as_global(sc.image_color)[4 * off];  // (as_global: see count_path_in_histograms)
+    const V4 before = v4(atomicAdd(&color[0], radiance.x), atomicAdd(&color[1], radiance.y),
+                         atomicAdd(&color[2], radiance.z), atomicAdd(&color[3], radiance.w));
+    const float n_before = atomicAdd(&as_global(sc.image_ray_nb)[off], 1.f);
     if (super_sampling) {
-        float* const vp = &sc.image_v[4 * off];
+        float* const vp = &as_global(sc.image_v)[4 * off];
         if (iteration != 0u) {
             const V4 after = before + radiance;
             const float n_after = n_before + 1.f;

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Register budget of every render_wavefront_kernel instantiation (hipcc cross-compiles without a GPU): VGPRs, spilled VGPRs,
 scratch bytes, occupancy, and the number of scratch instructions INSIDE the traversal loop (depth-2 blocks), plus the static
-instruction mix of that loop.  usage: tools/kernel_resources.py [source tree, default the repo] [arithmetic 0|1, default 1]"""
+instruction mix of that loop, the kernel's flat instructions, and the waits of the node step: the s_waitcnt sequence from the
+step's four record loads to the first vmcnt(0) (the first wait must not be the one that waits for all four).
+usage: tools/kernel_resources.py [source tree, default the repo] [arithmetic 0|1, default 1]"""
 import os
 import re
 import subprocess
@@ -20,7 +22,8 @@ def key_of(m):
     return "".join(re.findall(r"Lb([01])E", m.group(1))) + ("b" + m.group(2) if m.group(2) not in (None, "256") else "") + ("c" if m.group(3) == "1" else "")
 
 
-def resources(tree=ROOT, arithmetic=1, extra=()):
+def compile_to_assembly(tree=ROOT, arithmetic=1, extra=()):
+    """kernel_wavefront.hip with the Makefile's flags -> (path of the assembly, hipcc's resource remarks)"""
     csrc = os.path.join(tree, "opencl_pathtracer_amd", "csrc")
     out = os.path.join(tempfile.mkdtemp(), "wf.s")
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
@@ -29,28 +32,77 @@ def resources(tree=ROOT, arithmetic=1, extra=()):
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode:
         raise RuntimeError(r.stderr[-3000:])
+    return out, r.stderr
+
+
+def kernel_blocks(asm_path):
+    """{instantiation key: [(loop depth of the block, [its instructions, comments stripped])]} in the order of the assembly"""
+    blocks, cur = {}, None
+    for line in open(asm_path):
+        m = re.match(NAME + r"\w*:", line)
+        if m:
+            cur = blocks.setdefault(key_of(m), [])
+            cur.append((0, []))
+        elif cur is None:
+            continue
+        elif line.startswith(".Lfunc_end"):
+            cur = None
+        elif re.match(r"(\.LBB|; %bb\.)", line):
+            d = re.search(r"Depth=(\d+)", line)
+            cur.append((int(d.group(1)) if d else 0, []))
+        elif re.match(r"\s+[a-z]", line) and not line.lstrip().startswith("."):
+            cur[-1][1].append(line.split(";")[0].strip())
+    return blocks
+
+
+def node_step_waits(blocks):
+    """The node step inside the traversal loop (the depth-2 blocks): the block that loads a record's four quads - four
+    global_load_dwordx4 from ONE address at offsets 0, 16, 32, 48 - and the s_waitcnt instructions behind them, in layout
+    order through the loop's following blocks (the compiler ends the loads' block at the branch between the two box tests),
+    up to the first that carries vmcnt(0).  -> (offsets in issue order, [operands of each wait], whether that vmcnt(0) stands
+    before the loop's next vector memory load and before its end), or None where the loop holds no such block."""
+    loop = [lines for depth, lines in blocks if depth == 2]
+    for b, lines in enumerate(loop):
+        loads = [(i, re.match(r"global_load_dwordx4 v\[\d+:\d+\], (\S+), (\S+?)(?: offset:(\d+))?$", l)) for i, l in enumerate(lines)]
+        loads = [(i, m.group(1) + " " + m.group(2), int(m.group(3) or 0)) for i, m in loads if m]
+        for k in range(len(loads) - 3):
+            group = loads[k:k + 4]
+            if len({base for _, base, _ in group}) != 1 or sorted(off for _, _, off in group) != [0, 16, 32, 48]:
+                continue
+            waits = []
+            for l in lines[group[-1][0] + 1:] + [l for later in loop[b + 1:] for l in later]:
+                if l.startswith("s_waitcnt "):
+                    waits.append(l.split(None, 1)[1])
+                    if "vmcnt(0)" in l:
+                        return [off for _, _, off in group], waits, True
+                elif re.match(r"(global|buffer|flat|scratch)_(load|atomic)", l):
+                    break
+            return [off for _, _, off in group], waits, False
+    return None
+
+
+def resources(tree=ROOT, arithmetic=1, extra=()):
+    out, remarks = compile_to_assembly(tree, arithmetic, extra)
     res = {}
-    for block in re.split(r"Function Name: ", r.stderr)[1:]:
+    for block in re.split(r"Function Name: ", remarks)[1:]:
         m = re.match(NAME, block)
         if not m:
             continue
         key = key_of(m)  # STATS PRE SS PLAIN NANSAFE [bN: lanes per workgroup] [c: the culling instantiation]
         res[key] = {k.strip(): int(v) for k, v in re.findall(r"remark: [^\n]*?\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", block)}
-    name, depth2 = None, False
-    for line in open(out):
-        m = re.match(NAME + r"\w*:", line)
-        if m:
-            name, depth2 = key_of(m), False
-            res[name]["loop"] = Counter()
-        elif re.match(r"(\.LBB|; %bb\.)", line):
-            depth2 = "Depth=2" in line
-        elif depth2 and name is not None and re.match(r"\s+[a-z]", line):
-            res[name]["loop"][line.split()[0]] += 1
-    for v in res.values():
-        c = v.pop("loop")
+    for name, blocks in kernel_blocks(out).items():
+        v = res[name]
+        c = Counter(l.split()[0] for depth, lines in blocks if depth == 2 for l in lines)
         tot = lambda p: sum(n for i, n in c.items() if i.startswith(p))
         v["loop scratch"] = tot("scratch_")
         v["loop VALU"], v["loop SALU"], v["loop LDS"], v["loop VMEM"] = tot("v_"), tot("s_"), tot("ds_"), tot("global_") + tot("buffer_")
+        # flat instructions: inside the traversal loop / on the way into it (the path-logic loop around it and the prologue:
+        # everything but the depth-0 blocks behind the last loop block)
+        last_loop = max((i for i, (depth, _) in enumerate(blocks) if depth > 0), default=-1)
+        v["loop flat"] = tot("flat_")
+        v["flat before loop"] = sum(l.startswith("flat_") for depth, lines in blocks[:last_loop + 1] if depth != 2 for l in lines)
+        v["flat"] = sum(l.startswith("flat_") for _, lines in blocks for l in lines)
+        v["node step"] = node_step_waits(blocks)
     return res
 
 
@@ -58,8 +110,10 @@ if __name__ == "__main__":
     tree = sys.argv[1] if len(sys.argv) > 1 else ROOT
     arith = int(sys.argv[2]) if len(sys.argv) > 2 else 1
     res = resources(tree, arith)
-    print("STATS PRE SS PLAIN NANSAFE | VGPRs spilled scratch occupancy | traversal loop: scratch VALU SALU LDS VMEM")
+    print("STATS PRE SS PLAIN NANSAFE | VGPRs spilled scratch occupancy | traversal loop: scratch VALU SALU LDS VMEM | flat: in the loop, "
+          "before it, kernel | node step: load offsets, then its waits")
     for k in sorted(res):
         v = res[k]
+        offsets, waits, closed = v["node step"] or ([], [], False)
         print("   ".join(k[:5]) + ("  " + k[5:] if len(k) > 5 else ""), "|", v["VGPRs"], v["VGPRs Spill"], v["ScratchSize"], v["Occupancy"], "|", v["loop scratch"], v["loop VALU"], v["loop SALU"],
-              v["loop LDS"], v["loop VMEM"])
+              v["loop LDS"], v["loop VMEM"], "|", v["loop flat"], v["flat before loop"], v["flat"], "|", ",".join(map(str, offsets)), "|", " / ".join(waits) + ("" if closed else " / (no vmcnt(0) before the next load)"))
