@@ -290,6 +290,32 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
         asm volatile("" : "+s"(p));
         return *(const DScene*)p;
     };
+    // ... and what every lane of a pass reads of them at ONE address and no kernel writes during a launch - the camera, the
+    // sky's rotation, the one light of the plain instantiations - through the CONSTANT address space (ptmi_device.hpp:
+    // as_constant): scalar loads.  As vector loads each was a round trip of its own through the L1 queue the traversal
+    // keeps full, repeated by every active lane for one and the same value ("The pass's memory chain").
+    // The pointers still go through the asm: a constant load may otherwise be hoisted out of the loops, and its value then
+    // holds scalar registers across the traversal loop, which has none to spare.
+    // What stays with cold_scene() and as_global: every address that differs per lane (the sky's face header, the pixels'
+    // accumulators, lights[light_idx] of the general instantiations) and everything the kernel WRITES.
+    auto cold_constants = [&]() {
+        const PTMI_CONSTANT DScene* p = as_constant(scene_in_memory);
+        asm volatile("" : "+s"(p));
+        return p;
+    };
+    // kOneLight: the light, by scalar loads - of a point light (all PLAIN admits) position, colour and power are used
+    auto one_light = [&]() {
+        const PTMI_CONSTANT ptmi_light* p = as_constant(sc.lights);
+        asm volatile("" : "+s"(p));
+        ptmi_light l;
+        l.position = ptmi_float4{p->position.x, p->position.y, p->position.z, p->position.w};
+        l.direction = ptmi_float4{0, 0, 0, 0};
+        l.color = ptmi_float4{p->color.x, p->color.y, p->color.z, p->color.w};
+        l.power = p->power;
+        l.cos_inner = l.cos_outer = 0;
+        l.type = PTMI_LIGHT_POINT;
+        return l;
+    };
     // The closest-hit record (point, s, t, triangle, side) changes only when a closer hit is accepted and is read
     // only by path logic: it lives in LDS in front of the stack, [field][lane], not in registers of the hot loop.
     uint32_t* const hit_mem = &stack_mem[tid];
@@ -697,6 +723,9 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
             if (!need_path) {
                 hit.point = load_hit_point();
                 const bool found = query_found();
+                // kOneLight: fetched ONCE per pass for the lit term and the shadow ray's set-up (nine scalar registers)
+                ptmi_light the_light = {};
+                if (kOneLight) the_light = one_light();
                 if (!shadow) {
                     // closest-hit query finished (FullKernel.cl:1252-1288)
                     if (found) {
@@ -708,7 +737,10 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
                         if (sc.n_lights > 0) start_shadow = true;
                         else do_scatter = true;
                     } else {
-                        radiance = mad(sky_color(cold_scene().sky, sc.texels, r.d), transfer, radiance);  // cl:1287
+                        // (the rotation: a scalar load; the header of the face a lane looks at and its texel: per lane)
+                        const PTMI_CONSTANT DScene* const cc = cold_constants();
+                        radiance = mad(sky_color(cc->sky.cos_rotation_angle, cc->sky.sin_rotation_angle, cold_scene().sky.sky_textures, sc.texels, r.d),
+                                       transfer, radiance);  // cl:1287
                         end_path = missed = true;
                     }
                 } else {
@@ -729,7 +761,7 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
                     check(dot(cam_d, sf.Ns) < 0 && dot(cam_d, sf.Ng) < 0, C_CHK_NORMALS);  // cl:1275
                     V4 gathered = kOneLight ? v4(0, 0, 0, 0) : direct;
                     if (lit) {
-                        ptmi_light light = sc.lights[kOneLight ? 0u : light_idx];
+                        ptmi_light light = kOneLight ? the_light : sc.lights[light_idx];
                         if (PLAIN) light.type = PTMI_LIGHT_POINT;
                         const float brdf = material_brdf(sf.mat.type, -r.d, sf.Ns, cam_d);
                         gathered = mad(v4(1, 1, 1, 1) * (light_power_toward(light, hit.point, sf.Ns) * brdf), v4(light.color), gathered);  // cl:945
@@ -760,7 +792,7 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
                 if (!kOneLight && shadow) light_idx++;  // (still set: this pass finished a shadow query and did not scatter)
                 if (start_shadow) {
                     // :932-944: ray from the hit point (no offset) towards light `light_idx`
-                    const ptmi_light light = sc.lights[kOneLight ? 0u : light_idx];
+                    const ptmi_light light = kOneLight ? the_light : sc.lights[light_idx];
                     const bool directional = !PLAIN && light.type == PTMI_LIGHT_DIRECTIONNAL;
                     const V4 full = directional ? -v4(light.direction) : v4(light.position) - hit.point;
                     r.o = hit.point;
@@ -768,6 +800,10 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
                     shadow = true;
                     new_direction = full; new_ray = true;
                 }
+                // (The compiler's vmcnt(0) at the join behind finish_path - for a load that is still pending on the path AROUND it -
+                // also waits for the two staging stores before the job request below can go out.  Tried: the region's loads
+                // waited for here instead, __builtin_amdgcn_s_waitcnt(0x0F70), which takes that wait away: 1057.9 -> 1058.6
+                // Msamples/s, one spread; not kept.  DESIGN.md 5, "The pass's memory chain".)
                 if (end_path) finish_path(missed);
             }
         }
@@ -826,9 +862,9 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
                 draw_sample(sc, gx, gy, it, seed, sample_x, sample_y);
                 check(sample_x >= -0.5f && sample_y >= -0.5f && sample_x <= 0.5f && sample_y <= 0.5f, C_CHK_SAMPLE);  // cl:1217
                 {
-                    const DScene& cs = cold_scene();  // camera: only needed here, once per path
-                    r.o = v4(cs.cam_pos);
-                    new_direction = mad(v4(cs.cam_up), sample_y, mad(v4(cs.cam_right), sample_x, v4(cs.cam_dir)));  // cl:1213
+                    const PTMI_CONSTANT DScene* const cs = cold_constants();  // camera: only needed here, once per path; scalar loads
+                    r.o = v4(cs->cam_pos);
+                    new_direction = mad(v4(cs->cam_up), sample_y, mad(v4(cs->cam_right), sample_x, v4(cs->cam_dir)));  // cl:1213
                 }
                 radiance = v4(0, 0, 0, 0);
                 transfer = v4(1, 1, 1, 1);

@@ -60,6 +60,19 @@ __device__ __forceinline__ T* as_global(T* const& field)
     return (T*)*static_cast<PTMI_GLOBAL T* const*>(static_cast<const void*>(&field));
 }
 
+// The twin for what a launch only READS and every lane reads at the same address - the scene record's camera and sky header,
+// the one light of the plain kernels: a pointer to the CONSTANT address space.  A load through it from a wave-uniform address is
+// a scalar load: one request of the wave to the scalar cache, its result in scalar registers, and nothing in the vector-memory
+// queue the traversal keeps full ("The pass's memory chain").  Only for memory no kernel writes while the launch
+// runs: the scalar cache is not kept coherent with vector stores; the host writes these records between launches.  Per-lane
+// addresses and everything a kernel writes stay with as_global.
+#define PTMI_CONSTANT __attribute__((address_space(4)))
+template <class T>
+__device__ __forceinline__ const PTMI_CONSTANT T* as_constant(const T* p)
+{
+    return (const PTMI_CONSTANT T*)p;
+}
+
 struct V4 {
     float x, y, z, w;
 };
@@ -68,6 +81,8 @@ __device__ __forceinline__ V4 v4(float x, float y, float z, float w) { return V4
 __device__ __forceinline__ V4 v4(const float* p) { return V4{p[0], p[1], p[2], p[3]}; }
 __device__ __forceinline__ V4 v4(const ptmi_float4& p) { return V4{p.x, p.y, p.z, p.w}; }
 __device__ __forceinline__ V4 v4(const float4& p) { return V4{p.x, p.y, p.z, p.w}; }
+__device__ __forceinline__ V4 v4(const PTMI_CONSTANT float* p) { return V4{p[0], p[1], p[2], p[3]}; }
+__device__ __forceinline__ V4 v4(const PTMI_CONSTANT ptmi_float4& p) { return V4{p.x, p.y, p.z, p.w}; }
 __device__ __forceinline__ V4 operator+(V4 a, V4 b) { return V4{a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w}; }
 __device__ __forceinline__ V4 operator-(V4 a, V4 b) { return V4{a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w}; }
 __device__ __forceinline__ V4 operator*(V4 a, V4 b) { return V4{a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w}; }
@@ -493,10 +508,13 @@ __device__ __forceinline__ V4 texture_pixel(const ptmi_texture& tex, const ptmi_
 }
 
 // Sky_GetColorValue + Sky_GetFaceColorValue, FullKernel.cl:438-512
-__device__ __forceinline__ V4 sky_color(const ptmi_sky& sky, const ptmi_uchar4* __restrict__ texels, V4 d)
+// (the rotation apart from the six faces' headers: every lane reads the same rotation, but the header of its own face - the
+// wavefront kernel fetches the first with a scalar load)
+__device__ __forceinline__ V4 sky_color(float cos_rotation_angle, float sin_rotation_angle, const ptmi_texture* sky_textures,
+                                        const ptmi_uchar4* __restrict__ texels, V4 d)
 {
-    const float x = mad(sky.cos_rotation_angle, d.x, -(sky.sin_rotation_angle * d.y));  // cl:441
-    const float y = mad(sky.sin_rotation_angle, d.x, sky.cos_rotation_angle * d.y);     // cl:442
+    const float x = mad(cos_rotation_angle, d.x, -(sin_rotation_angle * d.y));  // cl:441
+    const float y = mad(sin_rotation_angle, d.x, cos_rotation_angle * d.y);     // cl:442
     const float z = d.z;
     const float ax = fabsf(x), ay = fabsf(y), az = fabsf(z);
     int face = 0;
@@ -511,7 +529,11 @@ __device__ __forceinline__ V4 sky_color(const ptmi_sky& sky, const ptmi_uchar4* 
         if (y > 0) { face = 4; u = (1 + fdiv(x, y)) / 2; v = (1 + fdiv(z, y)) / 2; }
         else       { face = 2; u = (1 + fdiv(x, y)) / 2; v = (1 - fdiv(z, y)) / 2; }
     }
-    return texture_pixel(sky.sky_textures[face], texels, u, v);
+    return texture_pixel(sky_textures[face], texels, u, v);
+}
+__device__ __forceinline__ V4 sky_color(const ptmi_sky& sky, const ptmi_uchar4* __restrict__ texels, V4 d)
+{
+    return sky_color(sky.cos_rotation_angle, sky.sin_rotation_angle, sky.sky_textures, texels, d);
 }
 
 // Fresnel core shared by FullKernel.cl:192-217 (glass), :219-254 (water), :256-292 (varnish)

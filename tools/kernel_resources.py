@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Register budget of every render_wavefront_kernel instantiation (hipcc cross-compiles without a GPU): VGPRs, spilled VGPRs,
 scratch bytes, occupancy, and the number of scratch instructions INSIDE the traversal loop (depth-2 blocks), plus the static
-instruction mix of that loop, the kernel's flat instructions, and the waits of the node step: the s_waitcnt sequence from the
+instruction mix of that loop, the kernel's flat instructions, the memory chain of a path-logic pass (the outer loop's body:
+vector loads, scalar loads, full vector-memory waits), and the waits of the node step: the s_waitcnt sequence from the
 step's four record loads to the first vmcnt(0) (the first wait must not be the one that waits for all four).
 usage: tools/kernel_resources.py [source tree, default the repo] [arithmetic 0|1, default 1]"""
 import os
@@ -103,7 +104,18 @@ def resources(tree=ROOT, arithmetic=1, extra=()):
         v["flat before loop"] = sum(l.startswith("flat_") for depth, lines in blocks[:last_loop + 1] if depth != 2 for l in lines)
         v["flat"] = sum(l.startswith("flat_") for _, lines in blocks for l in lines)
         v["node step"] = node_step_waits(blocks)
+        v.update(outer_loop_memory(blocks))
     return res
+
+
+def outer_loop_memory(blocks):
+    """The body of the OUTER loop - the path-logic pass, the depth-1 blocks - as its memory chain shows in the assembly
+    ("The pass's memory chain"): vector loads from memory (global_ / buffer_; spill reloads are scratch_ and are
+    not counted), scalar loads, and the waits that let no vector memory operation stay outstanding (vmcnt(0))."""
+    pass_lines = [l for depth, lines in blocks if depth == 1 for l in lines]
+    return {"pass vector loads": sum(bool(re.match(r"(global|buffer)_load_", l)) for l in pass_lines),
+            "pass scalar loads": sum(bool(re.match(r"s_(buffer_)?load_", l)) for l in pass_lines),
+            "pass full waits": sum(l.startswith("s_waitcnt ") and "vmcnt(0)" in l for l in pass_lines)}
 
 
 if __name__ == "__main__":
@@ -111,9 +123,11 @@ if __name__ == "__main__":
     arith = int(sys.argv[2]) if len(sys.argv) > 2 else 1
     res = resources(tree, arith)
     print("STATS PRE SS PLAIN NANSAFE | VGPRs spilled scratch occupancy | traversal loop: scratch VALU SALU LDS VMEM | flat: in the loop, "
-          "before it, kernel | node step: load offsets, then its waits")
+          "before it, kernel | path-logic pass (the outer loop's body): vector loads, scalar loads, full vector-memory waits | "
+          "node step: load offsets, then its waits")
     for k in sorted(res):
         v = res[k]
         offsets, waits, closed = v["node step"] or ([], [], False)
         print("   ".join(k[:5]) + ("  " + k[5:] if len(k) > 5 else ""), "|", v["VGPRs"], v["VGPRs Spill"], v["ScratchSize"], v["Occupancy"], "|", v["loop scratch"], v["loop VALU"], v["loop SALU"],
-              v["loop LDS"], v["loop VMEM"], "|", v["loop flat"], v["flat before loop"], v["flat"], "|", ",".join(map(str, offsets)), "|", " / ".join(waits) + ("" if closed else " / (no vmcnt(0) before the next load)"))
+              v["loop LDS"], v["loop VMEM"], "|", v["loop flat"], v["flat before loop"], v["flat"], "|",
+              v["pass vector loads"], v["pass scalar loads"], v["pass full waits"], "|", ",".join(map(str, offsets)), "|", " / ".join(waits) + ("" if closed else " / (no vmcnt(0) before the next load)"))
