@@ -47,6 +47,40 @@ def recompute_aabb(t):
     t["AABB"] = box
 
 
+def moved_camera(sc, step=1):
+    """`sc` seen from a little to the side, the view tilted about the camera's right axis (the frame stays orthonormal)."""
+    out = copy.copy(sc)
+    a = np.float32(0.07 * step)
+    c, s = np.float32(np.cos(a)), np.float32(np.sin(a))
+    d, u = np.asarray(sc.cameraDirection, np.float32), np.asarray(sc.cameraUp, np.float32)
+    out.cameraPosition = (np.asarray(sc.cameraPosition, np.float32) + np.float32([0.11 * step, -0.05 * step, 0.02, 0])).astype(np.float32)
+    out.cameraDirection = (c * d + s * u).astype(np.float32)
+    out.cameraUp = (c * u - s * d).astype(np.float32)
+    return out
+
+
+BAD_TRIANGLES = ("zero_area", "nan_vertex", "unequal_w", "empty_aabb", "wrong_count")  # (the last: INVALID_ARGUMENT, the others: UNSUPPORTED)
+
+
+def bad_triangles(sc, kind):
+    """`sc`'s triangles with one defect that ptmi_update_triangles refuses."""
+    t = raw_copy(sc.triangulation)
+    if kind == "zero_area":
+        t["S3"][5] = t["S2"][5]
+        recompute_aabb(t)
+    elif kind == "nan_vertex":
+        t["S1"][2] = [np.nan, 0, 0, 1]
+    elif kind == "unequal_w":
+        t["S2"][7] = t["S2"][7] * np.float32([1, 1, 1, 2])
+    elif kind == "empty_aabb":
+        box = t["AABB"].copy()
+        box["isEmpty"][1] = 1
+        t["AABB"] = box
+    elif kind == "wrong_count":
+        t = t[:-1]
+    return t
+
+
 def bvh_refit(tris, bvh):
     """ptmi_bvh_refit on a byte copy of `bvh`: (status, message, the tree)."""
     lib = backend.load_library()

@@ -5,8 +5,6 @@ triangles with ptmi_bvh_refit's tree - which is code that existed before the upd
 be bit-equal: image, sample counts, the three histograms and ptmi_counters.  Refused updates must leave the old scene rendering
 as before.
 """
-import copy
-
 import numpy as np
 import pytest
 
@@ -29,16 +27,7 @@ def context(sc, **kw):
     return gpu_cases.context(sc, W, H, **kw)
 
 
-def moved_camera(sc, step=1):
-    """`sc` seen from a little to the side, the view tilted about the camera's right axis (the frame stays orthonormal)."""
-    out = copy.copy(sc)
-    a = np.float32(0.07 * step)
-    c, s = np.float32(np.cos(a)), np.float32(np.sin(a))
-    d, u = np.asarray(sc.cameraDirection, np.float32), np.asarray(sc.cameraUp, np.float32)
-    out.cameraPosition = (np.asarray(sc.cameraPosition, np.float32) + np.float32([0.11 * step, -0.05 * step, 0.02, 0])).astype(np.float32)
-    out.cameraDirection = (c * d + s * u).astype(np.float32)
-    out.cameraUp = (c * u - s * d).astype(np.float32)
-    return out
+moved_camera, _bad_triangles = U.moved_camera, U.bad_triangles  # (shared with the random call sequences: api_fuzz_cases.py)
 
 
 def set_camera(be, sc):
@@ -264,24 +253,6 @@ def test_two_listed_devices():
 
 
 # ---------------------------------------------------------------------------------------------- refusals
-
-def _bad_triangles(sc, kind):
-    t = U.raw_copy(sc.triangulation)
-    if kind == "zero_area":
-        t["S3"][5] = t["S2"][5]
-        U.recompute_aabb(t)
-    elif kind == "nan_vertex":
-        t["S1"][2] = [np.nan, 0, 0, 1]
-    elif kind == "unequal_w":
-        t["S2"][7] = t["S2"][7] * np.float32([1, 1, 1, 2])
-    elif kind == "empty_aabb":
-        box = t["AABB"].copy()
-        box["isEmpty"][1] = 1
-        t["AABB"] = box
-    elif kind == "wrong_count":
-        t = t[:-1]
-    return t
-
 
 def test_refused_updates_leave_the_old_scene_rendering():
     sc = scene("cornell")
