@@ -30,7 +30,7 @@
 //    comes through the cross-lane network (ds_bpermute), the results go back through one 64-bit LDS minimum per
 //    owner.  Triangle tests run at 96 % lane utilisation (a leaf of 3 triangles: one pass instead of three trips
 //    under a 30 % exec mask); node trips at 66 %.  (Round 1 ran MIXED trips instead, in which every traversing lane took
-//    one step per trip, node or triangle: what they measured stands beside the wait-debt table, launch_render_wavefront.)
+//    one step per trip, node or triangle: what they measured stands beside the wait-debt table, kernel_choice.h.)
 //  * Per ray the visit sequence is exactly the reference's (near child first, far child pushed, leaf
 //    triangles in index order, limit updated between tests, FullKernel.cl:620-702): only WHEN a lane
 //    takes its next step changes, never WHICH tests it makes or what they see (see leaf_pass for the one place
@@ -53,6 +53,7 @@
 // disassembly of the traversal loop).
 #include <hip/hip_runtime.h>
 
+#include "kernel_choice.h"
 #include "leaf_cull.h"
 #include "ptmi_device.hpp"
 #include "ptmi_shading.hpp"
@@ -136,10 +137,28 @@ struct DWarm {
     uint32_t wide_records;  // the record array is 4 GB or more: 64-bit addressing
     uint32_t russian_roulette;  // PTMI_FLAG_RUSSIAN_ROULETTE (non-parity mode)
     uint32_t source_seed;       // PTMI_FLAG_SOURCE_SEED (non-parity mode)
-    uint32_t wait_debt;         // lane-trips of waiting before a path-logic pass (launch_render_wavefront chooses it)
+    uint32_t wait_debt;         // lane-trips of waiting before a path-logic pass (kernel_choice.h: choose_wavefront)
     uint32_t split_paths;       // DScene::split_paths
     uint32_t leaf_cull;         // DScene::leaf_cull
 };
+// (host) the warm fields of `sc`, for a launch that waits `wait_debt` lane-trips
+inline DWarm warm_of(const DScene& sc, uint32_t wait_debt)
+{
+    DWarm warm{};
+    warm.nodes = sc.nodes; warm.tris = sc.tris; warm.big_leaves = sc.big_leaves; warm.tri_ids = sc.tri_ids; warm.shade = sc.shade;
+    warm.mats = sc.mats; warm.lights = sc.lights; warm.textures = sc.textures; warm.texels = sc.texels;
+    warm.root_ref = sc.root_ref; warm.width = sc.width; warm.height = sc.height; warm.max_depth = sc.max_depth;
+    warm.n_lights = sc.n_lights; warm.sampler = sc.sampler; warm.tris_precomputed = sc.tris_precomputed;
+    warm.histograms = sc.hist_depths != nullptr;
+    warm.boxes_ordered = sc.boxes_ordered;
+    warm.wide_records = sc.wide_records;
+    warm.russian_roulette = sc.russian_roulette;
+    warm.source_seed = sc.source_seed;
+    warm.wait_debt = wait_debt;
+    warm.split_paths = sc.split_paths;
+    warm.leaf_cull = sc.leaf_cull;
+    return warm;
+}
 
 // A finished path's three histogram bins in one word: depth (6 bits, < kStatDepthBins), box tests and triangle tests
 // (13 bits each; anything >= MAX_INTERSECTION_NUMBER = 5000 is not counted by the reference, stored as 8191).
@@ -259,7 +278,7 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
     constexpr bool kTos = !PLAIN;
     // Leaves beyond the limit are counted instead of tested (leaf_cull.h).  An instantiation of its own: a node step pays two
     // box distances for it, which a scene whose rays meet nothing behind their hits (the Cornell box) gets nothing back for -
-    // the launch picks it per scene (instance_for).  The statistics and SUPER_SAMPLING builds always hold the code and mask the
+    // the launch picks it per scene (choose_wavefront).  The statistics and SUPER_SAMPLING builds always hold the code and mask the
     // records' bits with sc.leaf_cull.
     static_assert(!CULL || PRE, "cull bits are computed for precomputed records only");
     constexpr bool kCull = CULL;
@@ -1184,19 +1203,11 @@ int launch_precompute_denominators_da(DTri* records, const uint32_t* tri_ids, ui
 }
 #endif
 
-static uint32_t clamp_levels(uint32_t stack_levels)
-{
-    if (stack_levels < 1) stack_levels = 1;
-    if (stack_levels > (uint32_t)PTMI_DEV_NS::kWfStack) stack_levels = PTMI_DEV_NS::kWfStack;
-    return stack_levels;
-}
-
-static size_t wavefront_lds_bytes(uint32_t stack_levels, int block)
-{
-    stack_levels = clamp_levels(stack_levels);
-    // closest-hit record + sentinel + stack (+ the keys and items of the leaf passes), per lane of the workgroup
-    return (size_t)(stack_levels + 1 + PTMI_DEV_NS::kHitRecordWords + PTMI_DEV_NS::kPassWordsPerLane) * block * sizeof(uint32_t);
-}
+// kernel_choice.h chooses the instantiation and sizes its LDS without seeing the kernel: what it assumes of it
+static_assert(ptmi_choice::kWideBlock == PTMI_DEV_NS::kWfBlock && ptmi_choice::kNarrowBlock == PTMI_DEV_NS::kWfBlockNarrow, "workgroup widths");
+static_assert(ptmi_choice::kMaxStackLevels == (uint32_t)PTMI_DEV_NS::kWfStack, "stack levels");
+static_assert(ptmi_choice::kLdsWordsBesideStack == 1 + PTMI_DEV_NS::kHitRecordWords + PTMI_DEV_NS::kPassWordsPerLane, "LDS words per lane");
+using ptmi_choice::wavefront_lds_bytes;
 
 // workgroups of instantiation `kernel` the current device holds at once (the persistent grid): registers and LDS decide
 template <class Kernel>
@@ -1227,7 +1238,8 @@ namespace {
 struct WavefrontLaunch {
     int device;          // the current device, and whether it has a place in the per-device caches below
     bool cached_device;
-    uint32_t lv, n_jobs;  // stack levels (clamped), jobs
+    ptmi_choice::WavefrontChoice choice;
+    uint32_t n_jobs;
     hipStream_t st;
     const DScene* scene_in_device_memory;
     PTMI_DEV_NS::DWarm warm;
@@ -1240,16 +1252,16 @@ constexpr int kMaxCachedDevices = 64;
 
 // Deep trees (23 levels and more): the wide workgroup's LDS no longer fits five times into a CU; the two production
 // instantiations are then launched in their narrow form (kWfBlockNarrow).  Asked once per device and depth.
-static bool five_wide_workgroups_fit(const WavefrontLaunch& w)
+static bool five_wide_workgroups_fit(int device, bool cached_device, uint32_t lv)
 {
     static std::atomic<int> wide_fits[kMaxCachedDevices][PTMI_BVH_MAX_DEPTH + 1];  // 0 = not asked, 1 = they fit, 2 = they do not
-    int fits = w.cached_device ? wide_fits[w.device][w.lv].load(std::memory_order_relaxed) : 0;
+    int fits = cached_device ? wide_fits[device][lv].load(std::memory_order_relaxed) : 0;
     if (fits == 0) {
         int n_cu = 0;
-        const int wide = resident_blocks_of(PTMI_DEV_NS::render_wavefront_kernel<false, true, false, true, false>, w.lv, PTMI_DEV_NS::kWfBlock);
-        const bool known = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, w.device) == hipSuccess && n_cu > 0 && wide > 0;
+        const int wide = resident_blocks_of(PTMI_DEV_NS::render_wavefront_kernel<false, true, false, true, false>, lv, PTMI_DEV_NS::kWfBlock);
+        const bool known = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && n_cu > 0 && wide > 0;
         fits = known && wide < 5 * n_cu ? 2 : 1;
-        if (w.cached_device) wide_fits[w.device][w.lv].store(fits, std::memory_order_relaxed);
+        if (cached_device) wide_fits[device][lv].store(fits, std::memory_order_relaxed);
     }
     return fits == 1;
 }
@@ -1257,49 +1269,24 @@ static bool five_wide_workgroups_fit(const WavefrontLaunch& w)
 // Launches one instantiation on its persistent grid on the CURRENT device (instantiations differ in registers, devices in CUs and
 // partition mode, hence in workgroups held at once): asked once per (instantiation, device, stack levels); host threads that
 // drive contexts of their own may race for an entry, and then write the same value.
-template <bool S, bool P, bool A, bool L, bool N, int B, bool C = false>
+// I: the instantiation's arguments by name (kernel_choice.h: Instance), which w.choice names too.
+template <class I>
 static void launch_instance(const WavefrontLaunch& w)
 {
-    auto kernel = PTMI_DEV_NS::render_wavefront_kernel<S, P, A, L, N, B, C>;
+    auto kernel = PTMI_DEV_NS::render_wavefront_kernel<I::stats, I::pre, I::ss, I::plain, I::nansafe, I::block, I::cull>;
+    constexpr int B = I::block;
+    const uint32_t lv = w.choice.stack_levels;
     static std::atomic<int> resident_cache[kMaxCachedDevices][PTMI_BVH_MAX_DEPTH + 1];
-    int resident = w.cached_device ? resident_cache[w.device][w.lv].load(std::memory_order_relaxed) : 0;
+    int resident = w.cached_device ? resident_cache[w.device][lv].load(std::memory_order_relaxed) : 0;
     if (resident == 0) {
-        resident = resident_blocks_of(kernel, w.lv, B);
-        if (w.cached_device) resident_cache[w.device][w.lv].store(resident, std::memory_order_relaxed);
+        resident = resident_blocks_of(kernel, lv, B);
+        if (w.cached_device) resident_cache[w.device][lv].store(resident, std::memory_order_relaxed);
     }
     if (w.cached_device) g_last_grid[w.device].store((uint32_t)B << 20 | (uint32_t)resident, std::memory_order_relaxed);
     uint32_t nb = (w.n_jobs + B - 1) / B;
     if (resident > 0 && nb > (uint32_t)resident) nb = (uint32_t)resident;
-    hipLaunchKernelGGL(kernel, dim3(nb), dim3(B), wavefront_lds_bytes(w.lv, B), w.st, w.scene_in_device_memory, w.warm, w.first_iteration,
-                       w.n_iterations, w.iteration_stride, w.n_jobs, w.job_counter, w.lv, w.stage, w.stage_stats);
-}
-
-// Which instantiation a launch gets, of those that exist.  The common case (no statistics, no adaptive sampling, records
-// that cannot yield NaN distances) pays for none of them; the statistics and SUPER_SAMPLING builds always carry the NaN check
-// (two instructions per accepted triangle).  `plain`: see the kernel's PLAIN (it implies precomputed records).  `narrow`: the
-// two production instantiations in workgroups of kWfBlockNarrow lanes (deep trees).
-using LaunchInstance = void (*)(const WavefrontLaunch&);
-static LaunchInstance instance_for(const DScene& sc, bool scheduler_stats, bool plain, bool narrow)
-{
-    constexpr int kWide = PTMI_DEV_NS::kWfBlock, kNarrow = PTMI_DEV_NS::kWfBlockNarrow;
-    const bool pre = sc.tris_precomputed != 0;
-    const bool cull = pre && sc.leaf_cull != 0u;  // (the host clears leaf_cull where culling is off or cannot pay: ptmi_scene_memory.cpp)
-    //                                               STATS  PRE    SS     PLAIN  NANSAFE
-    if (sc.super_sampling) return pre ? launch_instance<true, true, true, false, true, kWide, true> : launch_instance<true, false, true, false, true, kWide>;
-    if (scheduler_stats) return pre ? launch_instance<true, true, false, false, true, kWide, true> : launch_instance<true, false, false, false, true, kWide>;
-    if (sc.nan_safe) {
-        if (plain) return launch_instance<false, true, false, true, true, kWide>;
-        return pre ? launch_instance<false, true, false, false, true, kWide> : launch_instance<false, false, false, false, true, kWide>;
-    }
-    if (plain) {  // the common case, BASELINE's untextured scenes among them
-        if (cull) return narrow ? launch_instance<false, true, false, true, false, kNarrow, true> : launch_instance<false, true, false, true, false, kWide, true>;
-        return narrow ? launch_instance<false, true, false, true, false, kNarrow> : launch_instance<false, true, false, true, false, kWide>;
-    }
-    if (pre) {
-        if (cull) return narrow ? launch_instance<false, true, false, false, false, kNarrow, true> : launch_instance<false, true, false, false, false, kWide, true>;
-        return narrow ? launch_instance<false, true, false, false, false, kNarrow> : launch_instance<false, true, false, false, false, kWide>;
-    }
-    return launch_instance<false, false, false, false, false, kWide>;
+    hipLaunchKernelGGL(kernel, dim3(nb), dim3(B), w.choice.lds_bytes, w.st, w.scene_in_device_memory, w.warm, w.first_iteration,
+                       w.n_iterations, w.iteration_stride, w.n_jobs, w.job_counter, lv, w.stage, w.stage_stats);
 }
 
 }  // namespace
@@ -1317,49 +1304,29 @@ int PTMI_ARITH(launch_render_wavefront)(const DScene& sc, const DScene* scene_in
     }
     const uint32_t n_jobs = (uint32_t)jobs64;
     hipError_t e = hipMemsetAsync(job_counter, 0, PTMI_DEV_NS::kQueues * PTMI_DEV_NS::kQueueStride * sizeof(uint32_t), (hipStream_t)stream);
-    if (e == hipSuccess && sc.sampler == PTMI_SAMPLER_RANDOM) {
-        // PTMI_RANDOM_GIVE_UP=0 (tests, A/B): the give-up list starts full, so a path whose ray is not a number carries on with
-        // the ordered minimum as before round 4
-        const char* off = std::getenv("PTMI_RANDOM_GIVE_UP");
-        if (off && off[0] == '0')
-            e = hipMemsetD32Async((hipDeviceptr_t)(job_counter + 2), (int)PTMI_DEV_NS::kGiveUpListCap, 1, (hipStream_t)stream);
-    }
+    const ptmi_switches::Switches launch = ptmi_switches::read_switches(ptmi_switches::Moment::kLaunch);
+    // PTMI_RANDOM_GIVE_UP=0 (tests, A/B): the give-up list starts full, so a path whose ray is not a number carries on with
+    // the ordered minimum as before round 4
+    if (e == hipSuccess && sc.sampler == PTMI_SAMPLER_RANDOM && launch.random_give_up == '0')
+        e = hipMemsetD32Async((hipDeviceptr_t)(job_counter + 2), (int)PTMI_DEV_NS::kGiveUpListCap, 1, (hipStream_t)stream);
     if (e == hipSuccess) {
         WavefrontLaunch w{};
-        w.lv = clamp_levels(stack_levels); w.n_jobs = n_jobs; w.st = (hipStream_t)stream;
+        w.n_jobs = n_jobs; w.st = (hipStream_t)stream;
         w.scene_in_device_memory = scene_in_device_memory;
         w.first_iteration = first_iteration; w.n_iterations = n_iterations; w.iteration_stride = iteration_stride;
         w.job_counter = job_counter; w.stage = stage; w.stage_stats = stage_stats;
         w.cached_device = hipGetDevice(&w.device) == hipSuccess && w.device >= 0 && w.device < kMaxCachedDevices;
-        const uint32_t lv = w.lv;
-        PTMI_DEV_NS::DWarm& warm = w.warm;
-        warm.nodes = sc.nodes; warm.tris = sc.tris; warm.big_leaves = sc.big_leaves; warm.tri_ids = sc.tri_ids; warm.shade = sc.shade;
-        warm.mats = sc.mats; warm.lights = sc.lights; warm.textures = sc.textures; warm.texels = sc.texels;
-        warm.root_ref = sc.root_ref; warm.width = sc.width; warm.height = sc.height; warm.max_depth = sc.max_depth;
-        warm.n_lights = sc.n_lights; warm.sampler = sc.sampler; warm.tris_precomputed = sc.tris_precomputed;
-        warm.histograms = sc.hist_depths != nullptr;
-        warm.boxes_ordered = sc.boxes_ordered;
-        warm.wide_records = sc.wide_records;
-        warm.russian_roulette = sc.russian_roulette;
-        warm.source_seed = sc.source_seed;
-        warm.split_paths = sc.split_paths;
-        warm.leaf_cull = sc.leaf_cull;
-        const bool plain = sc.tris_precomputed && sc.plain_shading && sc.sampler == PTMI_SAMPLER_JITTERED && !sc.russian_roulette &&
-                           sc.n_lights == 1 && !sc.super_sampling && !scheduler_stats;
-        // lane-trips of waiting a wave tolerates before it spends a pass on path logic: 768 from tree depth 16 on, below that
-        // 512 (general path logic) or 320 (plain scenes: the cheaper a pass, the sooner it pays).  A launch parameter since
-        // round 2; the sweeps that chose it, on MI355X (Msamples/s: 1M triangles 1080p depth 22 / Cornell box 1080p d8 depth 5 /
-        // material mix 4K d16):
-        //   round 2, plain-scene specialisation (first two scenes):  192: - / 6360 / 2193    256: - / 6620 / 2317    320: - / 6670 / 2403
-        //                           384: - / 6600 / 2442    512: 960 / 6430 / 2491    640: 963 / 6190 / -    768: 976 / - / -    1024: 959 / - / -
-        //   round 2, leaf passes:   512: 885 / 5388 / 2344    768: 895 / 5172 / 2314    1024: 895 / 5121 / 2235
-        //   round 1's mixed trips (every traversing lane one step per trip, node or triangle: what leaf passes replaced):
-        //                           256: - / 4883 / 1876    384: 733 / - / 1969    512: 740 / 4804 / 1986    768: 742 / 4896 / 1944
-        //                           1024: 737 / 4845 / 1872    2048: - / 4840 / 1718
-        // (a fixed threshold of 8 waiting lanes instead of a debt measured 474 / 743 with an early build)
-        warm.wait_debt = lv >= 16u ? 768u : (plain ? 320u : 512u);
-        const bool narrow = !five_wide_workgroups_fit(w) && std::getenv("PTMI_WIDE_WORKGROUPS") == nullptr;  // (developer switch: A/B runs)
-        instance_for(sc, scheduler_stats, plain, narrow)(w);
+        const bool five_wide_fit = five_wide_workgroups_fit(w.device, w.cached_device, ptmi_choice::clamp_levels(stack_levels));
+        w.choice = ptmi_choice::choose_wavefront(sc, scheduler_stats, stack_levels, five_wide_fit, launch);
+        w.warm = PTMI_DEV_NS::warm_of(sc, w.choice.wait_debt);
+        if (!ptmi_choice::with_instance(w.choice, [&w](auto instance) { launch_instance<decltype(instance)>(w); })) {
+            const ptmi_choice::WavefrontChoice& c = w.choice;
+            if (err)
+                *err = "no render_wavefront_kernel<STATS " + std::to_string(c.stats) + ", PRE " + std::to_string(c.pre) + ", SS " + std::to_string(c.ss) +
+                       ", PLAIN " + std::to_string(c.plain) + ", NANSAFE " + std::to_string(c.nansafe) + ", BLOCK " + std::to_string(c.block) +
+                       ", CULL " + std::to_string(c.cull) + "> exists";
+            return PTMI_ERR_INTERNAL;
+        }
         e = hipGetLastError();
         // behind the launch, on its stream: the paths it gave up, if any, traced again (both return at once when there is none)
         const dim3 redo_block(PTMI_DEV_NS::kBlock);

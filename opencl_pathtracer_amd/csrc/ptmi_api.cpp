@@ -13,6 +13,7 @@
 #include <cstring>
 #include <mutex>
 
+#include "kernel_choice.h"
 #include "ptmi_context.h"
 
 using namespace ptmi_internal;
@@ -94,6 +95,7 @@ int ptmi_setup_context(ptmi_ctx** out, const ptmi_config* cfg)
         ptmi_release(ctx);
         return fail(nullptr, PTMI_ERR_HIP, msg);
     }
+    const ptmi_switches::Switches setup = ptmi_switches::read_switches(ptmi_switches::Moment::kSetup);
     // iterations per launch: at most 16, fewer for very large images (32-bit job ids, staging array <= 4 GiB)
     {
         const uint64_t tiles = (uint64_t)((cfg->image_width + 7u) / 8u) * ((cfg->image_height + 7u) / 8u);
@@ -103,16 +105,14 @@ int ptmi_setup_context(ptmi_ctx** out, const ptmi_config* cfg)
         if (by_jobs < cap) cap = by_jobs;
         if (by_bytes < cap) cap = by_bytes;
         ctx->iterations_per_launch = cap < 1 ? 1u : (uint32_t)cap;
-        // env: test switch - a lower cap, so that small images take the launch plans of very large ones (1..32; never higher)
-        if (const char* v = std::getenv("PTMI_ITERATIONS_PER_LAUNCH")) {
-            const long want = std::strtol(v, nullptr, 10);
-            if (want >= 1 && want <= 32 && (uint32_t)want < ctx->iterations_per_launch) ctx->iterations_per_launch = (uint32_t)want;
-        }
+        // PTMI_ITERATIONS_PER_LAUNCH: a lower cap, so that small images take the launch plans of very large ones (1..32; never higher)
+        const int want = setup.iterations_per_launch;
+        if (want >= 1 && want <= 32 && (uint32_t)want < ctx->iterations_per_launch) ctx->iterations_per_launch = (uint32_t)want;
     }
-    // env: developer switch - 0: the wavefront kernel fetches and tests the triangles of every leaf it reaches (leaf_cull.h);
+    // PTMI_LEAF_CULL - 0: the wavefront kernel fetches and tests the triangles of every leaf it reaches (leaf_cull.h);
     // 1: it culls the leaves a node step chooses itself, 2: also the ones it would push - both in every scene whose records
-    // carry the bits, also where upload_scene would not expect it to pay (anything else reads as 1, as it always did)
-    if (const char* v = std::getenv("PTMI_LEAF_CULL")) ctx->leaf_cull = v[0] == '0' ? 0 : v[0] == '2' ? 2 : 1;
+    // carry the bits, also where choose_upload would not expect it to pay
+    ctx->leaf_cull = ptmi_choice::leaf_cull_setting(setup);
     *out = ctx;
     return PTMI_OK;
 }

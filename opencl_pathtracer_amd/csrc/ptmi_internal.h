@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <string>
 
+#include "dev_switches.h"
 #include "ptmi.h"
 #include "ptmi_hd.h"
 #ifdef __HIPCC__  // (host code that is built without HIP reads this header too: it gets everything but launch_status)
@@ -46,10 +47,8 @@ inline int stack_kernel_grid(uint32_t stack_levels, uint64_t wanted, const char*
     const size_t by_lds = (160u * 1024u) / *lds_bytes;
     const int per_cu = (int)(by_lds < 8 ? by_lds : 8);
     uint64_t cap = 4ull * (uint64_t)(cus > 0 ? cus : 1) * (uint64_t)(per_cu > 0 ? per_cu : 1);
-    if (const char* v = std::getenv(cap_env)) {  // env: test switch
-        const long want = std::strtol(v, nullptr, 10);
-        if (want >= 1 && (uint64_t)want < cap) cap = (uint64_t)want;
-    }
+    const int want = ptmi_switches::read_switch(cap_env);
+    if (want >= 1 && (uint64_t)want < cap) cap = (uint64_t)want;
     *blocks = (uint32_t)(wanted > cap ? cap : wanted);
     return PTMI_OK;
 }

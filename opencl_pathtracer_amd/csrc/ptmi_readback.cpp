@@ -94,18 +94,12 @@ RcclApi& rccl_api()
 }
 constexpr int kNcclFloat32 = 7, kNcclSum = 0;  // rccl.h: ncclDataType_t / ncclRedOp_t
 
-const char* reduce_mode()
-{
-    const char* e = std::getenv("PTMI_REDUCE");
-    return e ? e : "";
-}
-
 // devices[0]'s ctx->d_reduced = sum over the devices of their share of the image of ring slot `slot`, by ONE ncclReduce per
 // device (root = devices[0]), each on its device's copy stream behind that device's snapshot.  PTMI_ERR_UNSUPPORTED = this
 // context cannot use RCCL (library absent, a device listed twice, initialisation refused): the caller falls back to peer copies.
 int rccl_reduce_snapshots(ptmi_ctx* ctx, uint32_t slot)
 {
-    if (ctx->rccl_state < 0 || std::strcmp(reduce_mode(), "peer") == 0) return PTMI_ERR_UNSUPPORTED;
+    if (ctx->rccl_state < 0) return PTMI_ERR_UNSUPPORTED;
     RcclApi& api = rccl_api();
     const int G = (int)ctx->n_dev();
     if (ctx->rccl_state == 0) {
@@ -163,7 +157,8 @@ int gather_snapshot(ptmi_ctx* ctx, uint32_t slot, const float** image)
     ON_DEVICE(ctx, lead);
     const int lead_src = lead.ring.shown(slot);
     HIP_TRY(ctx, hipStreamWaitEvent(lead.copy_stream, lead.snapshot_ready[lead_src], 0));
-    if (ctx->n_dev() == 1 && std::strcmp(reduce_mode(), "rccl-always") != 0) {
+    const int reduce = ptmi_switches::read_switches(ptmi_switches::Moment::kReadback).reduce;
+    if (ctx->n_dev() == 1 && reduce != ptmi_switches::kReduceRcclAlways) {
         *image = lead.d_snapshot[lead_src];
         return PTMI_OK;
     }
@@ -171,7 +166,7 @@ int gather_snapshot(ptmi_ctx* ctx, uint32_t slot, const float** image)
     // Which path: peer copies + the sum kernel in device order, unless the caller opted into the collective (PTMI_REDUCE=rccl /
     // rccl-always, above).  The images of a progressive per-image loop (ptmi_render_snapshots: ONE device's share is new per
     // image) are cheaper through the incremental peer copies anyway, which move 1 / (G - 1) of what a reduce would.
-    const bool collective = std::strncmp(reduce_mode(), "rccl", 4) == 0;
+    const bool collective = reduce != 0;
     if (int rc = collective ? rccl_reduce_snapshots(ctx, slot) : (int)PTMI_ERR_UNSUPPORTED) {
         if (rc != PTMI_ERR_UNSUPPORTED) return rc;
         if (ctx->n_dev() == 1) {  // (rccl-always on a box without the library)

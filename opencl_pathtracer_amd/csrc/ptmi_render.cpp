@@ -9,6 +9,8 @@
 #include "ptmi_context.h"
 
 using namespace ptmi_internal;
+using ptmi_switches::Moment;
+using ptmi_switches::read_switches;
 
 int ptmi_internal::fold_events(ptmi_ctx* ctx, DeviceState& d)
 {
@@ -53,12 +55,6 @@ int snapshots_up_to(ptmi_ctx* ctx, DeviceState& d, SnapshotPlan& plan, uint32_t 
 // caller (PTMI_RENDER_AHEAD, default 2, 0 = never, at most kStageSets - 2: beside them one launch whose calls are coming, and one
 // set for a call that finds nothing), and CALLS one of them may render for (PTMI_RENDER_AHEAD_CALLS, default 4).
 static_assert(kAheadIterations == PTMI_COUNTER_SPLITS, "a launch ahead counts per call: at most that many calls");  // (stage_sets.h)
-uint32_t env_in(const char* name, int fallback, int lo, int hi)
-{
-    const char* e = std::getenv(name);
-    const int v = e ? std::atoi(e) : fallback;
-    return (uint32_t)(v < lo ? lo : (v > hi ? hi : v));
-}
 
 // Stage set `set` able to hold `iterations` iterations (radiance float4 + one statistics word per path), or `at_least` where the
 // device does not have the memory for that many.  Growing it waits for whatever may still use the old arrays.
@@ -131,15 +127,16 @@ int render_on_device(ptmi_ctx* ctx, DeviceState& d, uint32_t first, uint32_t n, 
     const bool staged = !megakernel && ctx->cfg.sampler != PTMI_SAMPLER_RANDOM;
     // launch streams of their own (for SHORT launches only: long ones side by side get in each other's way): only where the
     // launch neither reads nor writes the accumulators (staged results, no adaptive sampling), on the context's own stream,
-    // and unless switched off (PTMI_SERIAL_LAUNCHES: developer A/B switch)
-    static const bool serial_env = std::getenv("PTMI_SERIAL_LAUNCHES") != nullptr;
+    // and unless switched off (PTMI_SERIAL_LAUNCHES: read ONCE per process, unlike every other switch)
+    static const bool serial_env = read_switches(Moment::kProcess).serial_launches != 0;
+    const ptmi_switches::Switches call = read_switches(Moment::kRenderCall);
     const bool may_overlap = staged && !ctx->cfg.super_sampling && d.stream == d.own_stream && !serial_env;
     // rendering ahead (per device: with G devices each sees every G-th call, stride G): nothing but staged results leaves the
     // kernel (the histograms of very deep paths are atomics inside it), and the caller has not asked for an image per iteration
     const bool ahead_allowed = !plan && !(d.ds.hist_depths && ctx->cfg.ray_max_depth >= 64);
     const StageNeed need = d.schedule.begin({first, n, stride, ctx->iterations_per_launch, ctx->cfg.super_sampling != 0, may_overlap,
-                                             ahead_allowed, env_in("PTMI_RENDER_AHEAD", 2, 0, kStageSets - 2),
-                                             env_in("PTMI_RENDER_AHEAD_CALLS", PTMI_COUNTER_SPLITS, 1, PTMI_COUNTER_SPLITS),
+                                             ahead_allowed, (uint32_t)ptmi_switches::clamped(call.render_ahead, 2, 0, kStageSets - 2),
+                                             (uint32_t)ptmi_switches::clamped(call.render_ahead_calls, PTMI_COUNTER_SPLITS, 1, PTMI_COUNTER_SPLITS),
                                              (ctx->cfg.flags & PTMI_FLAG_SCHEDULER_STATS) != 0});
     if (staged) {
         // staging arrays, grown on demand: room for launches ahead only once they are due, and only where the device has it

@@ -8,22 +8,23 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "leaf_cull.h"
+#include "kernel_choice.h"
 #include "ptmi_context.h"
 #include "scene_layout.h"
 
 using namespace ptmi_internal;
+using ptmi_switches::Moment;
+using ptmi_switches::read_switches;
 
-// one path per lane (kernels.hip) instead of the wavefront kernel: asked for, or needed by the scene - records that can yield
-// NaN distances (literal_kernel_reason) rendered with the RANDOM sampler, whose samples are not staged, so that a path the
-// wavefront kernel gives up could not be traced again; with the other samplers such a scene runs the wavefront kernel's
-// NANSAFE instantiation (PTMI_LITERAL_KERNEL=1: the one-path-per-lane kernel as a whole, as before round 4, for A/B runs)
+// what kernel_choice.h reads of the context
+static ptmi_choice::ContextTraits traits_of(const ptmi_ctx* ctx)
+{
+    return {ctx->cfg.sampler, ctx->cfg.flags, ctx->cfg.super_sampling, ctx->cfg.lights_size, ctx->leaf_cull};
+}
+
 bool ptmi_internal::one_path_per_lane(const ptmi_ctx* ctx)
 {
-    if ((ctx->cfg.flags & PTMI_FLAG_MEGAKERNEL) != 0) return true;
-    if (ctx->literal_kernel_reason.empty()) return false;
-    const char* force = std::getenv("PTMI_LITERAL_KERNEL");
-    return ctx->cfg.sampler == PTMI_SAMPLER_RANDOM || (force && force[0] == '1');
+    return ptmi_choice::one_path_per_lane(traits_of(ctx), !ctx->literal_kernel_reason.empty(), read_switches(Moment::kKernelKind));
 }
 
 // Before the scene memory of device `d` is rewritten: a launch ahead may still be reading it (the stage sets' scene records
@@ -127,10 +128,12 @@ int upload_scene(ptmi_ctx* ctx, DeviceState& d, const Relayout& lay, const ptmi_
     ON_DEVICE(ctx, d);
     DScene& ds = d.ds;
     ds = DScene{};
+    ptmi_choice::choose_upload({lay.tris_precomputed, lay.plain_shading, lay.boxes_ordered, !lay.literal_kernel_reason.empty(), lay.cullable_leaves,
+                                lay.recs.size(), lay.nan_walk_box_tests, lay.nan_walk_tri_tests, lay.nan_walk_last_tri},
+                               traits_of(ctx), read_switches(Moment::kUpload), ds);
     if (int rc = upload(ctx, d, lay.recs, &ds.tris)) return rc;
     ds.nodes = reinterpret_cast<const DNode*>(ds.tris);  // same array: a reference is an index of 64-byte records
     ds.n_records = (uint32_t)lay.recs.size();
-    ds.wide_records = (lay.recs.size() > (1u << 26) || std::getenv("PTMI_WIDE_RECORDS") != nullptr) ? 1u : 0u;  // env: test switch
     if (int rc = upload(ctx, d, lay.tri_ids, &ds.tri_ids)) return rc;
     if (default_arithmetic(ctx) && lay.tris_precomputed) {
         // the records' reciprocal determinants in the reference's default arithmetic: a device instruction's values
@@ -172,7 +175,6 @@ int upload_scene(ptmi_ctx* ctx, DeviceState& d, const Relayout& lay, const ptmi_
     ds.hist_bbx = hist ? d.d_hist + ctx->cfg.ray_max_depth + 1 : nullptr;
     ds.hist_tri = hist ? d.d_hist + ctx->cfg.ray_max_depth + 1 + PTMI_MAX_INTERSECTION_NUMBER : nullptr;
     ds.counters = d.d_counters;
-    ds.super_sampling = ctx->cfg.super_sampling ? 1u : 0u;
     if (ds.super_sampling) {
         float* dx = nullptr;
         if (int rc = scene_alloc(ctx, d, ctx->color_bytes(), ds.image_v)) return rc;
@@ -186,30 +188,10 @@ int upload_scene(ptmi_ctx* ctx, DeviceState& d, const Relayout& lay, const ptmi_
     std::memcpy(ds.cam_dir, &sc->camera_direction, 16);
     std::memcpy(ds.cam_right, &sc->camera_right, 16);
     std::memcpy(ds.cam_up, &sc->camera_up, 16);
-    ds.tris_precomputed = lay.tris_precomputed ? 1u : 0u;
-    ds.plain_shading = lay.plain_shading ? 1u : 0u;
-    ds.nan_safe = lay.literal_kernel_reason.empty() ? 0u : 1u;
-    ds.nan_walk_box_tests = lay.nan_walk_box_tests; ds.nan_walk_tri_tests = lay.nan_walk_tri_tests; ds.nan_walk_last_tri = lay.nan_walk_last_tri;
-    if (std::getenv("PTMI_WALK_NAN_RAYS") != nullptr) ds.nan_walk_box_tests = ds.nan_walk_tri_tests = 0xFFFFFFFFu;  // developer switch: A/B and tests
-    ds.boxes_ordered = (lay.boxes_ordered && std::getenv("PTMI_GENERIC_BOXES") == nullptr) ? 1u : 0u;  // env: developer switch for A/B runs
-    // (the records carry cull bits exactly when they are precomputed and their distances are numbers: scene_layout.cpp)
-    // The culling instantiation pays two box distances per node step (+47 VALU instructions of 283 in the loop) and gets them back
-    // where rays walk through leaves behind their hits: 1M triangles +3.5 %, 4M +10 %; in the Cornell box, where what a ray hits
-    // is the last thing along it, nothing is culled and the kernel LOSES 4.5 %.  So a scene of few leaves keeps the
-    // kernel without the code.  A threshold, not a prediction: a large scene of closed rooms would still pay for nothing.
-    constexpr uint32_t kCullMinLeaves = 1024;
-    const bool cull_bits = lay.tris_precomputed && lay.literal_kernel_reason.empty();
-    const bool cull = ctx->leaf_cull < 0 ? lay.cullable_leaves >= kCullMinLeaves : ctx->leaf_cull != 0;
-    // (forced to 1, the kernel culls only the leaves a node step chooses itself - A/B against the pushed ones in one binary)
-    ds.leaf_cull = (cull && cull_bits) ? (ptmi_cull::kCullChild1 | ptmi_cull::kCullChild2 | (ctx->leaf_cull == 1 ? 0u : ptmi_cull::kCullPushed)) : 0u;
     ds.root_ref = lay.root_ref;
     ds.width = ctx->cfg.image_width;
     ds.height = ctx->cfg.image_height;
     ds.max_depth = ctx->cfg.ray_max_depth;
-    ds.n_lights = ctx->cfg.lights_size;
-    ds.sampler = ctx->cfg.sampler;
-    ds.russian_roulette = (ctx->cfg.flags & PTMI_FLAG_RUSSIAN_ROULETTE) ? 1u : 0u;
-    ds.source_seed = (ctx->cfg.flags & PTMI_FLAG_SOURCE_SEED) ? 1u : 0u;
     return upload_scene_records(ctx, d);
 }
 

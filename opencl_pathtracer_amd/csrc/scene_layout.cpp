@@ -1,5 +1,6 @@
 // scene_layout.cpp - validation and re-layout of a scene for the device (see scene_layout.h).  No device call in this file.
 #include "scene_layout.h"
+#include "kernel_choice.h"
 #include "scene_refit_common.h"
 
 #include <cmath>
@@ -147,7 +148,8 @@ int build_layout(const ptmi_config& cfg, const ptmi_scene* sc, Relayout& out, st
     }
     // The common untextured Lambert scene (BASELINE's Cornell box and 1M-triangle scene): the wavefront kernel has a
     // specialisation whose path logic holds neither the other four material types nor textures nor the other light types.
-    out.plain_shading = std::getenv("PTMI_GENERIC_SHADING") == nullptr;  // developer switch for A/B runs and tests
+    const ptmi_switches::Switches upload = ptmi_switches::read_switches(ptmi_switches::Moment::kUpload);
+    out.plain_shading = ptmi_choice::plain_shading_after_switch(true, upload);
     for (uint32_t i = 0; i < sc->materiaux_size && out.plain_shading; i++)
         if (sc->materiaux[i].type != PTMI_MAT_STANDART || !sc->materiaux[i].is_simple_color) out.plain_shading = false;
     for (uint32_t i = 0; i < sc->lights_size && out.plain_shading; i++)
@@ -169,7 +171,7 @@ int build_layout(const ptmi_config& cfg, const ptmi_scene* sc, Relayout& out, st
     // Ray-independent part of the triangle test, if every triangle keeps the importers' convention of equal w
     // on its three vertices (then the edge vectors have w = +0 exactly).  Same operations, same order, same
     // rounding as the kernel's generic form: dot() = fma chain over four components (ptmi_device.hpp).
-    out.tris_precomputed = std::getenv("PTMI_GENERIC_TRIANGLES") == nullptr;  // developer switch for A/B runs
+    out.tris_precomputed = ptmi_choice::tris_precomputed_after_switch(true, upload);
     for (uint32_t i = 0; i < nt && out.tris_precomputed; i++)
         if (!ptmi_refit::triangle_keeps_equal_w(sc->triangulation[i])) out.tris_precomputed = false;  // edge vectors need w = +0 exactly
     if (out.tris_precomputed)
