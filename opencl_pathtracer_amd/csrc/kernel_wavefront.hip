@@ -674,12 +674,14 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
     int n_t, n_i, n_p;
     bool any_lane;
     unsigned long long dead_lanes = 0ull;  // (lanes only die in path logic: the mask is taken there)
+    unsigned long long step_mask = 0ull;   // kMaskedStep: the lanes of want_inner as the survey's ballot has them (scalar registers)
     auto survey = [&]() {
         pending = tri_i < tri_end;
         const bool has_node = cur < REF_DEAD;
         const unsigned long long b_t = __builtin_amdgcn_ballot_w64(pending), b_n = __builtin_amdgcn_ballot_w64(has_node), b_dead = dead_lanes;
         const unsigned long long m_t = b_t, m_i = b_n & ~b_t, m_p = ~(b_t | b_n | b_dead);
         want_inner = !pending & has_node;
+        step_mask = m_i;
         want_post = !pending & !has_node & (cur != REF_DEAD);
         any_lane = (m_t | m_i | m_p) != 0ull;
         n_t = __popcll(m_t); n_i = __popcll(m_i); n_p = __popcll(m_p);
@@ -712,14 +714,52 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
         // next node as soon as the step has chosen it, before the wave has counted its lanes and decided what the next trip
         // is - 895 -> 724: the requests of lanes that turn out to wait are extra L1 traffic, and the loop-carried
         // registers cost sixteen copies per trip.)
+        // A trip's KIND as the node step's EXEC MASK, not as a branch around it (kMaskedStep).  As `if (pass) { leaf_pass();
+        // survey(); continue; } if (want_inner) node_step(); survey();` the two alternatives meet in one flow block of the
+        // structurised loop, the cursor a node step leaves (p_bbx, p_tri, tri_end, tri_i, cur, sp) reaches that block as PHIs
+        // and the coalescer does not fold them into the home registers: every node trip began with a full vmcnt(0) and six
+        // v_mov into temporaries, and ended with a second vmcnt(0) and six v_mov back, all under the full exec mask
+        // (tests/test_trip_loop_copies.py reads them off the assembly).  Here the leaf pass alone stays behind the uniform
+        // branch; the node step follows it in straight line under the mask of the lanes at inner nodes - the survey's own
+        // ballot, or nothing after a pass - which goes through an opaque asm so that the compiler cannot thread the branch back
+        // around the step; the step then updates the cursor in place and one survey() closes both kinds of trip.  The
+        // flagship's loop (<0,1,0,1,0,256,1>, default arithmetic; vector / scalar instructions / v_mov, static):
+        // 335 / 226 / 40 -> 313 / 208 / 24.  MI355X, 1M triangles 1080p depth 10, same box, alternating, two runs each
+        // (profiles/trip_loop_copies_ab.txt), Msamples/s:
+        //   branch around the step (as before):                                1058.95 / 1058.24
+        //   the hold as a per-lane predicate through a "+v" asm (316 / 209 / 24): 1066.87 / 1068.61   (a v_cndmask and a v_cmp per trip)
+        //   the mask (this form):                                              1088.90 / 1090.38   (+2.9 %; as committed, another
+        //   session, three runs each: 1061.30 / 1060.49 / 1061.18 -> 1088.33 / 1087.00 / 1088.37, +2.5 %)
+        //   ... and the leaf pass's three-way result (closest hit / shadow hit / shadow miss) as selects instead of branches,
+        //   which takes two more v_mov and three scalar instructions out of a pass (310 / 205 / 22): 1087.56 / 1084.68 - not kept.
+        // Not measured, worse by count: the mask as all-or-nothing ANDed with want_inner (314 / 210 / 24).  The cull rule's
+        // `first` and `certified` (node_step) as selects on the hit masks: 314 / 211 / 29, with near / far intermediates
+        // 315 / 208 / 24 - both more than the 0 / 1 integers they replace, not kept.
+        // In every plain instantiation; of the general ones in those that cull or run in workgroups of 64 lanes.  The general
+        // instantiations of 256 lanes without culling keep the branch: under the mask the allocator spills more than
+        // tests/test_path_logic_loads.py pins for them (default arithmetic <0,0,0,0,0> 30 for 29 and <0,1,0,0,1> 44 for 26,
+        // strict <0,1,0,0,0> 58 for 57, each with one full wait more in the pass), and the strict <0,0,0,0,1> reloads a
+        // fourth spilled register inside this loop (tests/test_resources.py allows it three).
+        constexpr bool kMaskedStep = PLAIN || CULL || BLOCK == kWfBlockNarrow;
         while (!to_path_logic()) {
-            if (pass_is_due()) {
-                leaf_pass(pending);
+            if (!kMaskedStep) {
+                if (pass_is_due()) {
+                    leaf_pass(pending);
+                    survey();
+                    continue;
+                }
+                if (STATS) { trips_i++; lanes_i += n_i; }
+                if (want_inner) node_step();
                 survey();
                 continue;
             }
-            if (STATS) { trips_i++; lanes_i += n_i; }
-            if (want_inner) node_step();
+            unsigned long long steppers = step_mask;
+            if (pass_is_due()) {
+                leaf_pass(pending);
+                steppers = 0ull;
+            } else if (STATS) { trips_i++; lanes_i += n_i; }
+            asm volatile("" : "+s"(steppers));
+            if (__builtin_amdgcn_inverse_ballot_w64(steppers)) node_step();
             survey();
         }
         wait_debt = 0;
@@ -913,6 +953,16 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
                     limit = INFINITY;
                     new_ray = true;
                 } else {
+                    // (Plain shading, default arithmetic: the zero is made HERE.  As the prologue's zero, held for this one
+                    // store across both loops, it is a quad the allocator spills once the node step runs under its mask - the
+                    // flagship's kernel spilled eight registers instead of four.  The allocator's doing, not the code's: in the
+                    // strict build the same lines COST the same kernel four spilled registers, and the general instantiations
+                    // more; so they are compiled where they pay, tools/kernel_resources.py.)
+                    if (PLAIN && kDefaultArithmetic) {
+                        float zero = 0.f;
+                        asm volatile("" : "+v"(zero));
+                        radiance = v4(zero, zero, zero, zero);
+                    }
                     finish_path(false);  // depth 0: the bounce loop never runs (:1248), radiance 0, depth bin 0
                 }
             }

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Register budget of every render_wavefront_kernel instantiation (hipcc cross-compiles without a GPU): VGPRs, spilled VGPRs,
 scratch bytes, occupancy, and the number of scratch instructions INSIDE the traversal loop (depth-2 blocks), plus the static
-instruction mix of that loop, the kernel's flat instructions, the memory chain of a path-logic pass (the outer loop's body:
+instruction mix of that loop, what a trip of it costs beyond its work (v_mov, the two trip paths' instruction counts, the register
+copies and full waits around the node step: trip_loop_copies), the kernel's flat instructions, the memory chain of a path-logic pass (the outer loop's body:
 vector loads, scalar loads, full vector-memory waits), and the waits of the node step: the s_waitcnt sequence from the
 step's four record loads to the first vmcnt(0) (the first wait must not be the one that waits for all four).
 usage: tools/kernel_resources.py [source tree, default the repo] [arithmetic 0|1, default 1]"""
@@ -82,6 +83,134 @@ def node_step_waits(blocks):
     return None
 
 
+def kernel_cfg(asm_path):
+    """{instantiation key: [block]} in the order of the assembly, block = dict(label, header: it heads the traversal loop,
+    loop: it belongs to that loop (the depth-2 loop), lines: its instructions, succ: indices of the blocks it can go on to)."""
+    kernels, cur = {}, None
+    for line in open(asm_path):
+        m = re.match(NAME + r"\w*:", line)
+        if m:
+            cur = kernels.setdefault(key_of(m), [])
+            cur.append(dict(label=None, header=False, loop=False, lines=[]))
+        elif cur is None:
+            continue
+        elif line.startswith(".Lfunc_end"):
+            cur = None
+        elif re.match(r"(\.LBB\d+_\d+:|; %bb\.\d+:)", line):
+            label = line.split(":")[0]
+            cur.append(dict(label=label[1:] if label.startswith(".") else None, header=False, loop="Depth=2" in line and "Parent Loop" not in line, lines=[]))
+        elif "Inner Loop Header: Depth=2" in line:  # (the comment line behind the header's label)
+            cur[-1]["header"] = cur[-1]["loop"] = True
+        elif re.match(r"\s+[a-z]", line) and not line.lstrip().startswith("."):
+            cur[-1]["lines"].append(line.split(";")[0].strip())
+    for blocks in kernels.values():
+        at = {b["label"]: i for i, b in enumerate(blocks) if b["label"]}
+        for i, b in enumerate(blocks):
+            succ, falls = [], True
+            for l in b["lines"]:
+                m = re.match(r"s_c?branch\w* \.(LBB\d+_\d+)$", l)
+                if m:
+                    succ.append(at[m.group(1)])
+                falls = not re.match(r"(s_branch|s_endpgm|s_setpc)", l)
+            if falls and i + 1 < len(blocks):
+                succ.append(i + 1)
+            b["succ"] = succ
+    return kernels
+
+
+def _reach(blocks, start, allowed, forward=True):
+    """indices reachable from `start` through `allowed` blocks, never going on THROUGH the loop header (a trip ends there)"""
+    if forward:
+        nxt = lambda i: [] if blocks[i]["header"] and i != start else blocks[i]["succ"]
+    else:
+        pred = {}
+        for i, b in enumerate(blocks):
+            for s in b["succ"]:
+                if not blocks[s]["header"]:
+                    pred.setdefault(s, []).append(i)
+        nxt = lambda i: pred.get(i, [])
+    seen, todo = {start}, [start]
+    while todo:
+        for j in nxt(todo.pop()):
+            if j in allowed and j not in seen:
+                seen.add(j)
+                todo.append(j)
+    return seen
+
+
+def _is_record_block(lines):
+    loads = [re.match(r"global_load_dwordx4 v\[\d+:\d+\], (\S+), (\S+?)(?: offset:(\d+))?$", l) for l in lines]
+    loads = [(m.group(1) + " " + m.group(2), int(m.group(3) or 0)) for m in loads if m]
+    return any(len({b for b, _ in loads[k:k + 4]}) == 1 and sorted(o for _, o in loads[k:k + 4]) == [0, 16, 32, 48] for k in range(len(loads) - 3))
+
+
+def trip_paths(blocks):
+    """The two kinds of trip of the traversal loop as block sets of kernel_cfg's blocks: every block that lies on a way from the
+    loop header through the node step's record loads back to the header WITHOUT a block of the leaf pass's ray fetch
+    (ds_bpermute), and the other way round.  -> dict(header, loop, node: the record block, node_path, leaf_path) of indices;
+    None where the loop has no record block."""
+    loop = {i for i, b in enumerate(blocks) if b["loop"]}
+    header = next((i for i in loop if blocks[i]["header"]), None)
+    node = next((i for i in sorted(loop) if _is_record_block(blocks[i]["lines"])), None)
+    leaf = {i for i in loop if any(l.startswith("ds_bpermute") for l in blocks[i]["lines"])}
+    if header is None or node is None or not leaf:
+        return None
+
+    def through(marks, avoid):
+        allowed = loop - avoid
+        ends = {i for i in allowed if header in blocks[i]["succ"]}  # (the back edges)
+        from_header = _reach(blocks, header, allowed)
+        to_header = set().union(*[_reach(blocks, e, allowed, forward=False) for e in ends]) if ends else set()
+        path = set()
+        for m in marks:
+            before = from_header & _reach(blocks, m, allowed, forward=False)
+            after = _reach(blocks, m, allowed) & to_header
+            if m in from_header and m in to_header:
+                path |= before | after
+        return path
+
+    return dict(header=header, loop=loop, node=node, node_path=through({node}, leaf), leaf_path=through(leaf, {node}))
+
+
+def _mix(lines):
+    vector = sum(l.startswith("v_") for l in lines)
+    scalar = sum(l.startswith("s_") and not re.match(r"s_(waitcnt|nop)\b", l) for l in lines)
+    return vector, scalar
+
+
+REG_COPY = re.compile(r"v_mov_b(32|64)_e32 v\[?\d+(:\d+\])?, v\[?\d+")  # a v_mov between two vector registers (not a constant)
+
+
+def trip_loop_copies(blocks):
+    """What a trip of the traversal loop costs beyond its work, read off the assembly ("The trip loop's copies"):
+    the loop's v_mov_b32 count and scratch accesses, the vector / scalar instructions (without waits and nops) of the node-trip
+    path and of the leaf-pass path from the loop header to the back edge, and the register-to-register v_mov on the node trip's
+    way IN (header to the first record load) and OUT (behind the step's last LDS operation to the back edge)."""
+    p = trip_paths(blocks)
+    if p is None:
+        return None
+    loop_lines = [l for i in sorted(p["loop"]) for l in blocks[i]["lines"]]
+    lines_of = lambda idx: [l for i in sorted(idx) for l in blocks[i]["lines"]]
+    node, allowed = p["node"], p["node_path"]
+    # in: the path's blocks in front of the record block, and that block up to its first record load
+    before = (_reach(blocks, node, allowed, forward=False) - {node}) & allowed
+    first_load = next(k for k, l in enumerate(blocks[node]["lines"]) if l.startswith("global_load_dwordx4"))
+    way_in = lines_of(before) + blocks[node]["lines"][:first_load]
+    # out: behind the last LDS operation of the step (in layout order among the path's blocks behind the record block)
+    behind = _reach(blocks, node, allowed)
+    last = max((i for i in behind if any(l.startswith("ds_") for l in blocks[i]["lines"])), default=None)
+    way_out = None
+    if last is not None:
+        k = max(k for k, l in enumerate(blocks[last]["lines"]) if l.startswith("ds_"))
+        way_out = blocks[last]["lines"][k + 1:] + lines_of((_reach(blocks, last, allowed) - {last}) & behind)
+    return {"loop v_mov": sum(l.startswith("v_mov_b32") for l in loop_lines),
+            "loop scratch": sum(l.startswith("scratch_") for l in loop_lines),
+            "node trip": _mix(lines_of(p["node_path"])), "leaf pass": _mix(lines_of(p["leaf_path"])),
+            "copies in": [l for l in way_in if REG_COPY.match(l)],
+            "copies out": None if way_out is None else [l for l in way_out if REG_COPY.match(l)],
+            "full waits in": sum(l.startswith("s_waitcnt") and "vmcnt(0)" in l for l in way_in)}
+
+
 def resources(tree=ROOT, arithmetic=1, extra=()):
     out, remarks = compile_to_assembly(tree, arithmetic, extra)
     res = {}
@@ -105,6 +234,8 @@ def resources(tree=ROOT, arithmetic=1, extra=()):
         v["flat"] = sum(l.startswith("flat_") for _, lines in blocks for l in lines)
         v["node step"] = node_step_waits(blocks)
         v.update(outer_loop_memory(blocks))
+    for name, blocks in kernel_cfg(out).items():
+        res[name]["trip loop"] = trip_loop_copies(blocks)
     return res
 
 
@@ -118,16 +249,25 @@ def outer_loop_memory(blocks):
             "pass full waits": sum(l.startswith("s_waitcnt ") and "vmcnt(0)" in l for l in pass_lines)}
 
 
+def trip_loop_text(t):
+    if t is None:
+        return "(no node step in the loop)"
+    out = "-" if t["copies out"] is None else len(t["copies out"])
+    return f'{t["loop v_mov"]} {t["node trip"][0]} {t["node trip"][1]} {t["leaf pass"][0]} {t["leaf pass"][1]} {len(t["copies in"])} {t["full waits in"]} {out}'
+
+
 if __name__ == "__main__":
     tree = sys.argv[1] if len(sys.argv) > 1 else ROOT
     arith = int(sys.argv[2]) if len(sys.argv) > 2 else 1
     res = resources(tree, arith)
     print("STATS PRE SS PLAIN NANSAFE | VGPRs spilled scratch occupancy | traversal loop: scratch VALU SALU LDS VMEM | flat: in the loop, "
           "before it, kernel | path-logic pass (the outer loop's body): vector loads, scalar loads, full vector-memory waits | "
-          "node step: load offsets, then its waits")
+          "node step: load offsets, then its waits | trip loop: v_mov in the loop; node-trip path vector, scalar instructions; leaf-pass path "
+          "vector, scalar; register copies on a node trip's way in (header to the first record load), full vector-memory waits there, "
+          "copies on its way out (behind the step's last LDS operation to the back edge)")
     for k in sorted(res):
         v = res[k]
         offsets, waits, closed = v["node step"] or ([], [], False)
         print("   ".join(k[:5]) + ("  " + k[5:] if len(k) > 5 else ""), "|", v["VGPRs"], v["VGPRs Spill"], v["ScratchSize"], v["Occupancy"], "|", v["loop scratch"], v["loop VALU"], v["loop SALU"],
               v["loop LDS"], v["loop VMEM"], "|", v["loop flat"], v["flat before loop"], v["flat"], "|",
-              v["pass vector loads"], v["pass scalar loads"], v["pass full waits"], "|", ",".join(map(str, offsets)), "|", " / ".join(waits) + ("" if closed else " / (no vmcnt(0) before the next load)"))
+              v["pass vector loads"], v["pass scalar loads"], v["pass full waits"], "|", ",".join(map(str, offsets)), "|", " / ".join(waits) + ("" if closed else " / (no vmcnt(0) before the next load)"), "|", trip_loop_text(v["trip loop"]))
