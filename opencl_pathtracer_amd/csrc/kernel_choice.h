@@ -42,11 +42,11 @@ struct ContextTraits {
 inline bool tris_precomputed_after_switch(bool scene_allows, const Switches& upload) { return scene_allows && !upload.generic_triangles; }
 inline bool plain_shading_after_switch(bool scene_allows, const Switches& upload) { return scene_allows && !upload.generic_shading; }
 
-// PTMI_LEAF_CULL as the context keeps it: 0, 1 or 2 (anything else reads as 1, as it always did); -1 = unset
+// PTMI_LEAF_CULL as the context keeps it: 0, 1, 2 or 3 (anything else reads as 1, as it always did); -1 = unset
 inline int leaf_cull_setting(const Switches& setup)
 {
     if (setup.leaf_cull == ptmi_switches::kUnset) return -1;
-    return setup.leaf_cull == '0' ? 0 : setup.leaf_cull == '2' ? 2 : 1;
+    return setup.leaf_cull == '0' ? 0 : setup.leaf_cull == '2' ? 2 : setup.leaf_cull == '3' ? 3 : 1;
 }
 
 // The chosen fields of DScene (the others are pointers, sizes and copies of the configuration: upload_scene).
@@ -72,8 +72,12 @@ inline void choose_upload(const LayoutTraits& lay, const ContextTraits& ctx, con
     constexpr uint32_t kCullMinLeaves = 1024;
     const bool cull_bits = lay.tris_precomputed && !lay.nan_records;
     const bool cull = ctx.leaf_cull < 0 ? lay.cullable_leaves >= kCullMinLeaves : ctx.leaf_cull != 0;
-    // (forced to 1, the kernel culls only the leaves a node step chooses itself - A/B against the pushed ones in one binary)
-    ds.leaf_cull = (cull && cull_bits) ? (ptmi_cull::kCullChild1 | ptmi_cull::kCullChild2 | (ctx.leaf_cull == 1 ? 0u : ptmi_cull::kCullPushed)) : 0u;
+    // (forced to 1, the kernel culls only the leaves a node step chooses itself - A/B against the pushed ones in one binary;
+    // forced to 3, it culls as with 2 but honours the tight certificate alone - A/B against the wide tier.  The gate counts
+    // the leaves of either tier: LayoutTraits::cullable_leaves.)
+    ds.leaf_cull = (cull && cull_bits) ? (ptmi_cull::kCullChild1 | ptmi_cull::kCullChild2 | (ctx.leaf_cull == 1 ? 0u : ptmi_cull::kCullPushed) |
+                                          (ctx.leaf_cull == 3 ? ptmi_cull::kCullTightOnly : 0u))
+                                       : 0u;
 }
 
 // ---- the kernel kind ----------------------------------------------------------------------------------------------------------

@@ -139,7 +139,8 @@ struct DWarm {
     uint32_t source_seed;       // PTMI_FLAG_SOURCE_SEED (non-parity mode)
     uint32_t wait_debt;         // lane-trips of waiting before a path-logic pass (kernel_choice.h: choose_wavefront)
     uint32_t split_paths;       // DScene::split_paths
-    uint32_t leaf_cull;         // DScene::leaf_cull
+    uint32_t leaf_cull;         // DScene::leaf_cull as a mask of three record bits, and by how much a record's word is shifted down
+    uint32_t cull_shift;        // to meet it: the tier a launch looks at (leaf_cull.h: kernel_cull_mask, kernel_cull_shift)
 };
 // (host) the warm fields of `sc`, for a launch that waits `wait_debt` lane-trips
 inline DWarm warm_of(const DScene& sc, uint32_t wait_debt)
@@ -156,7 +157,8 @@ inline DWarm warm_of(const DScene& sc, uint32_t wait_debt)
     warm.source_seed = sc.source_seed;
     warm.wait_debt = wait_debt;
     warm.split_paths = sc.split_paths;
-    warm.leaf_cull = sc.leaf_cull;
+    warm.leaf_cull = ptmi_cull::kernel_cull_mask(sc.leaf_cull);
+    warm.cull_shift = ptmi_cull::kernel_cull_shift(sc.leaf_cull);  // (the wide tier's bits - the leaves of either tier - unless the scene keeps to the tight one)
     return warm;
 }
 
@@ -635,12 +637,16 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
         bool culled = false, far_counted = false;
         if (kCull) {
             // (the ray's own part of the rule was evaluated where the ray was set up: bits 3 to 5 of dir_signs)
-            const uint32_t cull_bits = n.cull & (dir_signs >> 3) & sc.leaf_cull;
+            // The record's word shifted down to the tier this launch looks at - the wide tier's three bits, which hold the
+            // leaves of either tier (leaf_cull.h), or the tight tier's - and from there the tests of a single tier: "the child's
+            // bit", and "the child's bit and the pushed bit" as one compare.  ONE rule, the wide one, for the leaves of both
+            // tiers: a margin per child would cost a select of two constants per box in every node step.
+            const uint32_t cull_bits = (n.cull >> sc.cull_shift) & (dir_signs >> 3) & sc.leaf_cull;
             const bool first = fwd ? h1 : !h2;  // which child the step chooses, when it chooses one
             const bool certified = (cull_bits & (first ? ptmi_cull::kCullChild1 : ptmi_cull::kCullChild2)) != 0u;
-            culled = (h1 | h2) & certified & ptmi_cull::box_is_beyond(first ? d2_1 : d2_2, limit);
+            culled = (h1 | h2) & certified & ptmi_cull::box_is_beyond_wide(first ? d2_1 : d2_2, limit);
             const bool far_certified = (cull_bits & ptmi_cull::kCullPushed) != 0u && (cull_bits & (fwd ? ptmi_cull::kCullChild2 : ptmi_cull::kCullChild1)) != 0u;
-            far_counted = h1 & h2 & far_certified & ptmi_cull::box_is_beyond(fwd ? d2_2 : d2_1, limit);
+            far_counted = h1 & h2 & far_certified & ptmi_cull::box_is_beyond_wide(fwd ? d2_2 : d2_1, limit);
         }
         // (every choice as a select on the two hit masks themselves: combined into new booleans first - both, neither - the
         // compiler builds them as 0 / 1 integers in vector registers: seven instructions more per step)

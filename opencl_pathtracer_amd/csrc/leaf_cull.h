@@ -14,6 +14,9 @@
 // eps_abs <= kEpsAbsMax and kappa <= kKappaMax (what the certificate bounds), so that nsd >= (1 - 8u) ((1 - kappa) D - eps_abs)^2,
 // which the rule's two margins put above `limit`.  The state of the query after the leaf is then known without reading a record:
 // its triangle count goes up by the leaf's count and nothing else changes.
+// The claim holds for any pair of margins (kRel, kAbs) with the gates (kKappaMax, kEpsAbsMax) its two inequalities allow.  There
+// are two such tiers, the tight one above and the wide one (leaf_is_cullable_wide, leaf_cull_rule_wide); the kernel applies the
+// wide rule to the leaves of both (a tight certificate implies the wide one).
 #ifndef PTMI_LEAF_CULL_H
 #define PTMI_LEAF_CULL_H
 
@@ -32,6 +35,15 @@ namespace ptmi_cull {
 constexpr float kRel = 1.001f, kAbs = 0.01f, kMaxOrigin = 0x1p+41f;
 // what the certificate may grant: with eta = (kRel - 1) / 2,  (1 - kappa)^2 (1 - eta) kRel >= 1 + 40u  and  eps_abs^2 / eta <= 0.99 kAbs
 constexpr double kKappaMax = 0x1p-13, kEpsAbsMax = 2.0e-3;
+// The WIDE pair, the one the kernel applies: the culled leaves lie between the hit distance d and d^2 along the ray (the
+// reference compares a linear parameter with a squared distance), so a margin of a per cent in D2 loses next to nothing, and it
+// buys a kappa gate 16 times as wide - thin triangles, whose conditioning is what kappa measures, are most of what the tight
+// gate refuses (tris1m: 18.1 % of the leaves without a certificate, 1.2 % with this one; profiles/leaf_cull_potential_tris1m.json).
+// The same two inequalities with eta = (kRelWide - 1) / 2 = 0.005:  (1 - 2^-9)^2 * 0.995 * 1.01 = 1.00103 >= 1 + 40u  and
+// (1.5e-2)^2 / 0.005 = 0.045 <= 0.99 * 0.05 = 0.0495.  kRel <= kRelWide, kAbs <= kAbsWide and both gates are wider: the wide
+// rule implies the tight rule and a tight certificate the wide one (a leaf of either tier may be culled under the wide rule).
+constexpr float kRelWide = 1.01f, kAbsWide = 0.05f;
+constexpr double kKappaWideMax = 0x1p-9, kEpsAbsWideMax = 1.5e-2;
 
 // DNode::cull of an inner record: the children that are cullable leaves, and "this record's bits were computed" (a refit
 // recomputes the bits of the records that carry them and leaves the others alone: scene_refit_common.h)
@@ -39,6 +51,18 @@ constexpr uint32_t kCullChild1 = 1u, kCullChild2 = 2u, kCullComputed = 4u;
 // DScene::leaf_cull, the mask the kernel ANDs a record's bits with: the children it may cull where the step chooses them itself,
 // and - in the position of kCullComputed, which every record that carries a child bit has set - "also where it would push them".
 constexpr uint32_t kCullPushed = kCullComputed;
+// ... and the same three for the wide certificate, kCullWideShift above: the children that are leaves of the wide tier (set
+// beside the tight bit where a leaf has both: a tight certificate implies the wide one) and a copy of "computed".  So
+// `cull >> kCullWideShift` reads as the three tight bits do, for the wide tier, and the kernel's tests are the same
+// instructions whichever tier a launch looks at.
+constexpr uint32_t kCullWideShift = 3u;
+constexpr uint32_t kCullWide1 = kCullChild1 << kCullWideShift, kCullWide2 = kCullChild2 << kCullWideShift, kCullWideComputed = kCullComputed << kCullWideShift;
+// DScene::leaf_cull only: the kernel looks at the tight bits alone (PTMI_LEAF_CULL=3, for A/B runs in one binary)
+constexpr uint32_t kCullTightOnly = 64u;
+// What a launch hands the kernel, from DScene::leaf_cull: by how much it shifts a record's word down before it ANDs it with the
+// three mask bits - the wide tier's bits, which hold the leaves of either tier, unless the scene keeps to the tight one.
+constexpr uint32_t kernel_cull_shift(uint32_t scene_leaf_cull) { return (scene_leaf_cull & kCullTightOnly) ? 0u : kCullWideShift; }
+constexpr uint32_t kernel_cull_mask(uint32_t scene_leaf_cull) { return scene_leaf_cull & (kCullChild1 | kCullChild2 | kCullPushed); }
 
 PTMI_HD float box_distance2(const float lo[3], const float hi[3], float ox, float oy, float oz)
 {
@@ -84,6 +108,15 @@ PTMI_HD bool box_is_beyond(float d2, float limit)
 PTMI_HD bool leaf_cull_rule(float d2, float limit, float ox, float oy, float oz, float ow, float dw)
 {
     return box_is_beyond(d2, limit) && ray_may_cull(ox, oy, oz, ow, dw);
+}
+// the wide pair's (what node_step evaluates, for the leaves of both tiers)
+PTMI_HD bool box_is_beyond_wide(float d2, float limit)
+{
+    return d2 > fmaf(limit, kRelWide, kAbsWide);  // (false for a NaN)
+}
+PTMI_HD bool leaf_cull_rule_wide(float d2, float limit, float ox, float oy, float oz, float ow, float dw)
+{
+    return box_is_beyond_wide(d2, limit) && ray_may_cull(ox, oy, oz, ow, dw);
 }
 
 // ---- the certificate (double precision, at upload and in a refit) --------------------------------------------------------------
@@ -169,6 +202,12 @@ PTMI_HD bool triangle_certified(const ptmi_triangle& t, const float lo[3], const
     return triangle_slack(t, lo, hi, &eps_abs, &kappa) && eps_abs <= kEpsAbsMax && kappa <= kKappaMax;
 }
 
+PTMI_HD bool triangle_certified_wide(const ptmi_triangle& t, const float lo[3], const float hi[3])
+{
+    double eps_abs, kappa;
+    return triangle_slack(t, lo, hi, &eps_abs, &kappa) && eps_abs <= kEpsAbsWideMax && kappa <= kKappaWideMax;
+}
+
 // Is the child behind `ref`, with the box the record holds for it, a leaf the kernel may cull?  An ordinary leaf (not flagged
 // empty, one to six triangles in the reference itself) whose triangles are all certified.  tri_at(k): its k-th triangle.
 template <class TriAt>
@@ -182,15 +221,50 @@ PTMI_HD bool leaf_is_cullable(uint32_t ref, const float lo[3], const float hi[3]
         if (!triangle_certified(tri_at(k), lo, hi)) return false;
     return true;
 }
+// ... under the wide rule?
+template <class TriAt>
+PTMI_HD bool leaf_is_cullable_wide(uint32_t ref, const float lo[3], const float hi[3], TriAt tri_at)
+{
+    using namespace ptmi_internal;
+    if (!(ref & REF_LEAF) || (ref & REF_EMPTY)) return false;
+    const uint32_t count = ref_leaf_count(ref);
+    if (count == 0u || count == REF_COUNT_BIG) return false;
+    for (uint32_t k = 0; k < count; k++)
+        if (!triangle_certified_wide(tri_at(k), lo, hi)) return false;
+    return true;
+}
+
+// Both answers from one evaluation of each triangle's slack (a refit asks per record): bit 0 = leaf_is_cullable, bit 1 =
+// leaf_is_cullable_wide.
+template <class TriAt>
+PTMI_HD uint32_t leaf_cull_tiers(uint32_t ref, const float lo[3], const float hi[3], TriAt tri_at)
+{
+    using namespace ptmi_internal;
+    if (!(ref & REF_LEAF) || (ref & REF_EMPTY)) return 0u;
+    const uint32_t count = ref_leaf_count(ref);
+    if (count == 0u || count == REF_COUNT_BIG) return 0u;
+    uint32_t tiers = 3u;
+    for (uint32_t k = 0; k < count && tiers != 0u; k++) {
+        double eps_abs, kappa;
+        if (!triangle_slack(tri_at(k), lo, hi, &eps_abs, &kappa)) return 0u;
+        if (!(eps_abs <= kEpsAbsMax && kappa <= kKappaMax)) tiers &= ~1u;
+        if (!(eps_abs <= kEpsAbsWideMax && kappa <= kKappaWideMax)) tiers &= ~2u;
+    }
+    return tiers;
+}
 
 // DNode::cull of inner record `d`, from the boxes and references it holds; tri_of_record(r): the triangle behind leaf record r.
 template <class TriOfRecord>
 PTMI_HD uint32_t record_cull_bits(const ptmi_internal::DNode& d, TriOfRecord tri_of_record)
 {
     const uint32_t start1 = d.ref1 & ptmi_internal::REF_INDEX_MASK_LEAF, start2 = d.ref2 & ptmi_internal::REF_INDEX_MASK_LEAF;
-    uint32_t bits = kCullComputed;
-    if (leaf_is_cullable(d.ref1, d.lo1, d.hi1, [&](uint32_t k) -> const ptmi_triangle& { return tri_of_record(start1 + k); })) bits |= kCullChild1;
-    if (leaf_is_cullable(d.ref2, d.lo2, d.hi2, [&](uint32_t k) -> const ptmi_triangle& { return tri_of_record(start2 + k); })) bits |= kCullChild2;
+    uint32_t bits = kCullComputed | kCullWideComputed;
+    const uint32_t tiers1 = leaf_cull_tiers(d.ref1, d.lo1, d.hi1, [&](uint32_t k) -> const ptmi_triangle& { return tri_of_record(start1 + k); });
+    const uint32_t tiers2 = leaf_cull_tiers(d.ref2, d.lo2, d.hi2, [&](uint32_t k) -> const ptmi_triangle& { return tri_of_record(start2 + k); });
+    if (tiers1 & 1u) bits |= kCullChild1;
+    if (tiers2 & 1u) bits |= kCullChild2;
+    if (tiers1 & 2u) bits |= kCullWide1;
+    if (tiers2 & 2u) bits |= kCullWide2;
     return bits;
 }
 

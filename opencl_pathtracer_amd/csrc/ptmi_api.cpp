@@ -111,7 +111,7 @@ int ptmi_setup_context(ptmi_ctx** out, const ptmi_config* cfg)
     }
     // PTMI_LEAF_CULL - 0: the wavefront kernel fetches and tests the triangles of every leaf it reaches (leaf_cull.h);
     // 1: it culls the leaves a node step chooses itself, 2: also the ones it would push - both in every scene whose records
-    // carry the bits, also where choose_upload would not expect it to pay
+    // carry the bits, also where choose_upload would not expect it to pay; 3: as 2, but only the leaves of the certificate's tight tier
     ctx->leaf_cull = ptmi_choice::leaf_cull_setting(setup);
     *out = ctx;
     return PTMI_OK;

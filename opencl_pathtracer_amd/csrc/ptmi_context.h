@@ -117,7 +117,7 @@ struct ptmi_ctx : ptmi_internal::ContextScene {
     std::vector<ptmi_internal::DeviceState> dev;  // dev[0] = devices[0]: where partial images are summed and read back from
     std::string err;
     uint32_t iterations_per_launch = ptmi_internal::kMaxIterationsPerLaunch;
-    int leaf_cull = -1;  // PTMI_LEAF_CULL at set-up: 0 = never cull leaves, 1 = direct leaves / 2 = direct and pushed leaves wherever the records carry bits; unset (-1): both, where it can pay
+    int leaf_cull = -1;  // PTMI_LEAF_CULL at set-up: 0 = never cull leaves, 1 = direct leaves / 2 = direct and pushed leaves wherever the records carry bits, 3 = as 2 by the tight tier's bits alone; unset (-1): both, where it can pay
     // RCCL communicators, one per device of the context (single process, ncclCommInitAll): the sum of the devices' partial
     // images is an ncclReduce over xGMI where librccl is present and the devices are distinct (ptmi_readback.cpp)
     std::vector<void*> rccl_comms;

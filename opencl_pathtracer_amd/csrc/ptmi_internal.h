@@ -113,7 +113,7 @@ struct DNode {
     uint32_t ref1, ref2;
     uint32_t axis;  // cutAxis
     union {
-        uint32_t cull;  // which children are leaves the wavefront kernel may count untested (leaf_cull.h: kCullChild1 ...); 0 = none
+        uint32_t cull;  // which children are leaves the wavefront kernel may count untested (leaf_cull.h: kCullChild1 ..., kCullWide1 ...: three bits per tier of the certificate); 0 = none
         uint32_t pad;   // the name this word had while it was padding: sources written against it still compile
     };
 };
@@ -218,7 +218,7 @@ struct DScene {
     uint32_t boxes_ordered;    // every non-empty child box is finite with pMin <= pMax (see box_hit_ordered)
     uint32_t russian_roulette; // PTMI_FLAG_RUSSIAN_ROULETTE
     uint32_t source_seed;      // PTMI_FLAG_SOURCE_SEED
-    uint32_t leaf_cull;        // mask of the DNode::cull bits the wavefront kernel honours (leaf_cull.h): 3 = the children, + 4 = also where they would be pushed; 0 = culling is off
+    uint32_t leaf_cull;        // mask of the DNode::cull bits the wavefront kernel honours (leaf_cull.h): 3 = the children, + 4 = also where they would be pushed, + 64 = by the tight tier's bits alone (what the kernel gets of it: kernel_cull_mask, kernel_cull_shift); 0 = culling is off
 };
 
 // The integrator's device code exists once per ARITHMETIC MODE (ptmi_device.hpp: strict / the reference's default OpenCL

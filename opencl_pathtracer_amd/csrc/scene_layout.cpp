@@ -258,7 +258,8 @@ int build_layout(const ptmi_config& cfg, const ptmi_scene* sc, Relayout& out, st
         d.ref1 = r1; d.ref2 = r2; d.axis = n.cut_axis; d.cull = 0;  // inner children: index patched in when they are emitted
         // which of the two are leaves no triangle of which can be accepted from beyond the limit (leaf_cull.h)
         if (cull_bits) d.cull = ptmi_cull::record_cull_bits(d, [&](uint32_t r) -> const ptmi_triangle& { return sc->triangulation[out.tri_ids[r]]; });
-        out.cullable_leaves += ((d.cull & ptmi_cull::kCullChild1) ? 1u : 0u) + ((d.cull & ptmi_cull::kCullChild2) ? 1u : 0u);
+        // (of either tier: a leaf of the tight one carries the wide bit too)
+        out.cullable_leaves += ((d.cull & ptmi_cull::kCullWide1) ? 1u : 0u) + ((d.cull & ptmi_cull::kCullWide2) ? 1u : 0u);
         // the short slab test (box_hit_ordered) needs finite, ordered boxes; anything else keeps the literal form
         for (int k = 0; k < 3; k++) {
             if (!(r1 & REF_EMPTY) && !(std::isfinite(d.lo1[k]) && std::isfinite(d.hi1[k]) && d.lo1[k] <= d.hi1[k])) out.boxes_ordered = false;
