@@ -1,0 +1,53 @@
+#!/usr/bin/env python3
+"""A few samples per pixel, filtered on the device: the raw and the denoised image side by side.
+
+    python examples/denoise.py --scene cornell --width 512 --height 512 --spp 4
+    python examples/denoise.py --scene matmix --sigma-position 0.5 --out matmix     # -> matmix_raw.bmp, matmix_denoised.bmp
+
+Renders --spp iterations of a scene and filters the mean image with ptmi_denoise: an edge-avoiding a-trous wavelet filter guided
+by the first-hit albedo, normal and position of the same iterations, which the call renders itself.  --sigma-position is in
+scene units.  Only the filtered image crosses the bus, 16 bytes per pixel; the raw one is read here for the comparison.
+"""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import opencl_pathtracer_amd as pt  # noqa: E402
+from opencl_pathtracer_amd import output, structs as S  # noqa: E402
+
+
+def main():
+    d = pt.backend.DENOISE_DEFAULTS
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--scene", default="cornell", help="cornell | mayalike | matmix | tris<N>[k|m] (opencl_pathtracer_amd.scenes.build)")
+    ap.add_argument("--width", type=int, default=512)
+    ap.add_argument("--height", type=int, default=512)
+    ap.add_argument("--spp", type=int, default=4)
+    ap.add_argument("--passes", type=int, default=d["passes"])
+    ap.add_argument("--sigma-color", type=float, default=d["sigma_color"])
+    ap.add_argument("--sigma-normal", type=float, default=d["sigma_normal"])
+    ap.add_argument("--sigma-position", type=float, default=d["sigma_position"])
+    ap.add_argument("--no-demodulation", action="store_true", help="filter the image itself, not the image divided by the albedo")
+    ap.add_argument("--out", default="denoise", help="prefix of the BMPs")
+    ap.add_argument("--device", type=int, default=0)
+    args = ap.parse_args()
+
+    w, h, n = args.width, args.height, max(args.spp, 1)
+    scene = pt.bvh_create(pt.scenes.build(args.scene, w, h))
+    be = pt.Backend().setup_context(w, h, 4, scene.lightsSize, S.JITTERED, device=args.device, flags=pt.backend.FLAG_DEFAULT_ARITHMETIC)
+    be.initialize_memory(scene)
+    be.render(0, n)
+    color, count = be.read_image()
+    denoised = be.denoise(passes=args.passes, sigma_color=args.sigma_color, sigma_normal=args.sigma_normal, sigma_position=args.sigma_position,
+                          demodulate=not args.no_demodulation, guide_first_iteration=0, guide_iterations=n)
+    be.release()
+
+    output.save_bmp(args.out + "_raw.bmp", color, count)
+    output.save_bmp(args.out + "_denoised.bmp", denoised)  # (already a mean: its fourth word is the sample count)
+    print(f"{args.out}_raw.bmp, {args.out}_denoised.bmp: {w}x{h}, {n} samples per pixel, {args.passes} passes")
+
+
+if __name__ == "__main__":
+    main()

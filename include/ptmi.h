@@ -389,6 +389,69 @@ int ptmi_render_guides(ptmi_ctx* ctx, uint32_t first_iteration, uint32_t n_itera
  * ptmi_query_rays_device. */
 int ptmi_render_guides_device(ptmi_ctx* ctx, uint32_t first_iteration, uint32_t n_iterations, const ptmi_guides* device_planes);
 
+/* ---- denoising the image on the device ------------------------------------- */
+
+/* The stage between the accumulators and the display: an edge-avoiding a-trous wavelet filter of the MEAN image, guided by the
+ * first-hit planes above.  A 5 x 5 B3-spline footprint at steps 1, 2, 4, 8, 16 (pass k uses step 1 << k); a tap counts less
+ * the further it is from the centre pixel in colour, shading normal and position, and is never taken across the hit mask.  With
+ * PTMI_DENOISE_DEMODULATE_ALBEDO the image is divided by the albedo before the filter and multiplied back after it, so that
+ * texture detail is not blurred.  sigma_position is in SCENE UNITS (a distance between first hits), sigma_normal a distance
+ * between unit normals, sigma_color one between (demodulated) colours; it halves with every pass.
+ *
+ * THE ARITHMETIC, the same in both arithmetic modes of a context.  Every operation is one IEEE binary32 operation in the
+ * written order: no contraction, correctly rounded division, denormals kept, no transcendental.
+ * dot3(v) = (v.x*v.x + v.y*v.y) + v.z*v.z;  color / ray_nb = the image planes;  albedo, normal, position, hit_count = guide
+ * planes summed over guide_iterations iterations;  B = {0.375f, 0.25f, 0.0625f}.
+ *   prepass, pixel p:  n = ray_nb[p];  m = n > 0 ? color[p].xyz / n : 0;  G = (float)guide_iterations;  a = albedo[p].xyz / G;
+ *       h = hit_count[p];  hit = h > 0;  nrm = hit ? normal[p].xyz / h : 0;  pos = hit ? position[p].xyz / h : 0;
+ *       d_c = a_c > 1e-3f ? a_c : 1e-3f per channel with the flag (a NaN albedo gives 1e-3), d = 1 without;  e0 = m / d.
+ *   pass k = 0 .. passes-1, s = 1 << k, from e(k):  inv_c = (float)(1 << 2k) / (sigma_color * sigma_color),
+ *       inv_n = 1.f / (sigma_normal * sigma_normal), inv_p = 1.f / (sigma_position * sigma_position), computed on the host in
+ *       float.  sw = 0, se = 0;  for dy = -2..2 (outer), dx = -2..2 (inner), q = (x + s*dx, y + s*dy):
+ *         skipped when q is outside the image or hit_q != hit_p;  b = B[|dy|] * B[|dx|];
+ *         xc = dot3(e_q - e_p) * inv_c;  xn = dot3(nrm_q - nrm_p) * inv_n;  xp = dot3(pos_q - pos_p) * inv_p;
+ *         w = b / (((1.f + xc) * (1.f + xn)) * (1.f + xp));  skipped when !(w > 0) (a NaN anywhere, an overflow to b / inf);
+ *         sw = sw + w;  se_c = se_c + w * e_q,c.
+ *       e(k+1) = sw > 0 ? se / sw : e_p: a pixel whose own value is not a number keeps it and never reaches a neighbour.
+ *   output:  out[p] = (e.x * d.x, e.y * d.y, e.z * d.z, n), e the last pass's; with passes = 0 that is e0 * d.
+ * Where a word of the result is a NaN its sign and payload mean nothing, as everywhere here.
+ *
+ * A DENOISE CALL TOUCHES NOTHING THAT HAS BEEN RENDERED: accumulators, histograms, ptmi_counters, scheduler statistics, the
+ * caller's snapshot slots and launches rendered ahead stay as they are - the promise of the ray queries and the guide calls.
+ * Scratch on devices[0], allocated by the first call and freed by ptmi_release (a context that never denoises pays nothing):
+ * 56 bytes per pixel of feature planes for either form, and for ptmi_denoise 68 more (its guide planes, 52, and the result, 16).
+ * PTMI_ERR_STATE before ptmi_initialize_memory; PTMI_ERR_INVALID_ARGUMENT for a NULL struct, a wrong struct_size, passes > 5,
+ * an unknown flag, a non-zero reserved word, guide_iterations of 0 or >= 2^24 (the planes' counts are exact floats below
+ * that), a sigma that is not finite and > 0, a missing plane or a device pointer that is not 16-byte aligned.  After any error
+ * the context renders as before. */
+#define PTMI_DENOISE_DEMODULATE_ALBEDO 1u
+#define PTMI_DENOISE_UNTILED 2u /* steps 1 and 2 read every tap from memory instead of a tile staged in LDS: the same words, for A/B */
+typedef struct ptmi_denoise_params {
+    uint32_t struct_size;           /* = sizeof(ptmi_denoise_params) */
+    uint32_t passes;                /* 0..5: pass k uses step 1 << k */
+    uint32_t flags;                 /* PTMI_DENOISE_* */
+    uint32_t guide_first_iteration; /* ptmi_denoise only: the guides are rendered for [guide_first_iteration, + guide_iterations) */
+    uint32_t guide_iterations;      /* >= 1, < 2^24: how many iterations the guide planes sum */
+    float sigma_color, sigma_normal, sigma_position; /* each finite and > 0 */
+    uint32_t reserved[2];           /* 0 */
+} ptmi_denoise_params;
+
+/* Host form: filters the image ptmi_read_image would return at this moment (on a multi-device context the devices' shares are
+ * summed first, as for ptmi_read_display), with guides rendered for the iterations the struct names, exactly as
+ * ptmi_render_guides would; image_out is float4[W*H] = (filtered mean r, g, b, the sample count), filled when the call returns -
+ * directly where the caller has page-locked it (ptmi_pin_host_buffer).  PTMI_ERR_UNSUPPORTED with the RANDOM sampler, as for
+ * ptmi_render_guides. */
+int ptmi_denoise(ptmi_ctx* ctx, const ptmi_denoise_params* params, float* image_out);
+/* Device form: every pointer is a device address, 16-byte aligned; asynchronous on the context's stream (ptmi_set_stream's,
+ * where one was given), ordered like ptmi_render_guides_device: the calls that rewrite scene records wait for it.
+ * device_guides carries albedo, normal, position and hit_count (ids is ignored), filled by ptmi_render_guides_device over
+ * guide_iterations iterations: the caller may reuse them for as long as camera and geometry stand still.  d_image_color and
+ * d_image_ray_nb are both given - any float4 sum plane and float count plane: a snapshot, another context's image, a tensor - or
+ * both NULL: the context's own accumulators (PTMI_ERR_UNSUPPORTED on a multi-device context, as for
+ * ptmi_device_accumulators).  d_image_out (float4[W*H]) MUST NOT ALIAS AN INPUT; the library cannot check that. */
+int ptmi_denoise_device(ptmi_ctx* ctx, const ptmi_denoise_params* params, const ptmi_guides* device_guides,
+                        const void* d_image_color, const void* d_image_ray_nb, void* d_image_out);
+
 /* ---- measurement / plumbing -------------------------------------------- */
 
 int ptmi_get_counters(ptmi_ctx* ctx, ptmi_counters* out);

@@ -96,6 +96,20 @@ class Guides(C.Structure):
 GUIDE_PLANES = ("albedo", "normal", "position", "hit_count", "ids")  # ptmi_guides, in the struct's order
 
 
+class DenoiseParams(C.Structure):
+    """ptmi_denoise_params: the filter of ptmi_denoise / ptmi_denoise_device (ptmi.h states its arithmetic)."""
+    _fields_ = [("struct_size", C.c_uint32), ("passes", C.c_uint32), ("flags", C.c_uint32), ("guide_first_iteration", C.c_uint32),
+                ("guide_iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_position", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
+DENOISE_DEMODULATE_ALBEDO, DENOISE_UNTILED = 1, 2  # ptmi.h: PTMI_DENOISE_*
+# The shipped defaults: the RMSE minimum against a 1024-spp render of the Cornell box at 4 spp, over the grid of
+# profiles/denoise_quality_cornell.json (tests/test_denoise_gpu.py holds them to it).  sigma_position is in scene units.
+# That box is 555 units wide: scale sigma_position with the scene (about 3 % of its extent).
+DENOISE_DEFAULTS = dict(passes=5, sigma_color=8.0, sigma_normal=1.0, sigma_position=16.0)
+
+
 BVH_FALLBACK_NONE, BVH_FALLBACK_STALE_AXIS, BVH_FALLBACK_HOST_ERROR, BVH_FALLBACK_RECORDS = 0, 1, 2, 3
 
 
@@ -134,7 +148,8 @@ ABI_SYMBOLS = ["ptmi_setup_context", "ptmi_initialize_memory", "ptmi_render", "p
                "ptmi_device_variance", "ptmi_last_error",
                "ptmi_abi_version", "ptmi_device_count", "ptmi_device_share", "ptmi_bvh_create",
                "ptmi_bvh_create_device", "ptmi_set_camera", "ptmi_update_triangles", "ptmi_bvh_refit",
-               "ptmi_query_rays", "ptmi_query_rays_device", "ptmi_render_guides", "ptmi_render_guides_device"]
+               "ptmi_query_rays", "ptmi_query_rays_device", "ptmi_render_guides", "ptmi_render_guides_device",
+               "ptmi_denoise", "ptmi_denoise_device"]
 
 QUERY_CLOSEST, QUERY_ANY = 0, 1  # ptmi.h: PTMI_QUERY_*
 
@@ -193,6 +208,8 @@ def load_library():
     lib.ptmi_query_rays_device.argtypes = [vp, u32, vp, u32, vp]
     lib.ptmi_render_guides.argtypes = [vp, u32, u32, C.POINTER(Guides)]
     lib.ptmi_render_guides_device.argtypes = [vp, u32, u32, C.POINTER(Guides)]
+    lib.ptmi_denoise.argtypes = [vp, C.POINTER(DenoiseParams), vp]
+    lib.ptmi_denoise_device.argtypes = [vp, C.POINTER(DenoiseParams), C.POINTER(Guides), vp, vp, vp]
     lib.ptmi_device_share.argtypes = [u32, u32, u32, u32, C.POINTER(u32), C.POINTER(u32)]
     lib.ptmi_device_share.restype = None
     _lib = lib
@@ -421,6 +438,44 @@ class Backend:
                 raise PtmiError(-1, f"unknown guide plane {name!r}: one of {GUIDE_PLANES}")
             setattr(g, name, address)
         self._check(self._lib.ptmi_render_guides_device(self._ctx, first_iteration, n_iterations, C.byref(g)))
+
+    # -- the filter between the accumulators and the display (no counterpart in the reference) --
+    @staticmethod
+    def denoise_params(passes=None, sigma_color=None, sigma_normal=None, sigma_position=None, demodulate=True, guide_first_iteration=0,
+                       guide_iterations=1, untiled=False):
+        """A ``DenoiseParams``; what is None takes its value from ``DENOISE_DEFAULTS``."""
+        given = dict(passes=passes, sigma_color=sigma_color, sigma_normal=sigma_normal, sigma_position=sigma_position)
+        v = {k: DENOISE_DEFAULTS[k] if x is None else x for k, x in given.items()}
+        flags = (DENOISE_DEMODULATE_ALBEDO if demodulate else 0) | (DENOISE_UNTILED if untiled else 0)
+        return DenoiseParams(C.sizeof(DenoiseParams), v["passes"], flags, guide_first_iteration, guide_iterations, v["sigma_color"],
+                             v["sigma_normal"], v["sigma_position"])
+
+    def denoise(self, out=None, **params):
+        """The mean image, filtered on the device by ``passes`` a-trous passes guided by the first-hit planes of iterations
+        [guide_first_iteration, guide_first_iteration + guide_iterations): float32[H,W,4] = (r, g, b, sample count).  Keywords as
+        for ``denoise_params`` (``sigma_position`` is in scene units); ``out`` = an array to fill (e.g. a page-locked one).  Touches
+        nothing that has been rendered."""
+        h, w = self.cfg.image_height, self.cfg.image_width
+        image = np.empty((h, w, 4), np.float32) if out is None else out
+        if image.dtype != np.float32 or image.shape != (h, w, 4) or not image.flags.c_contiguous:
+            raise PtmiError(-1, f"out must be a contiguous float32 array of shape {(h, w, 4)}")
+        p = self.denoise_params(**params)
+        self._check(self._lib.ptmi_denoise(self._ctx, C.byref(p), image.ctypes.data_as(C.c_void_p)))
+        return image
+
+    def denoise_device(self, out, guides, image_color=None, image_ray_nb=None, **params):
+        """The same between device addresses (e.g. ``tensor.data_ptr()``), 16-byte aligned: ``out`` float4[W*H], ``guides`` a dict
+        with the ``albedo``, ``normal``, ``position`` and ``hit_count`` planes ``render_guides_device`` filled over
+        ``guide_iterations`` iterations, and the image's sum and count planes (both None: the context's own accumulators).
+        Asynchronous on the context's stream; ``out`` must not alias an input."""
+        g = Guides(C.sizeof(Guides), 0)
+        for name, address in guides.items():
+            if name not in GUIDE_PLANES:
+                raise PtmiError(-1, f"unknown guide plane {name!r}: one of {GUIDE_PLANES}")
+            setattr(g, name, address)
+        p = self.denoise_params(**params)
+        self._check(self._lib.ptmi_denoise_device(self._ctx, C.byref(p), C.byref(g), C.c_void_p(image_color), C.c_void_p(image_ray_nb),
+                                                  C.c_void_p(out)))
 
     # -- one launch of the loop body of OpenCL_RunKernel, generalised to a range ----------
     def render(self, first_iteration, n_iterations):

@@ -292,6 +292,9 @@ void ptmi_release(ptmi_ctx* ctx)
     if (!ctx->dev.empty()) (void)hipSetDevice(ctx->dev[0].device);
     ctx->query_buffers.release();
     ctx->guide_buffers.release();
+    ctx->denoise_buffers.release();
+    if (ctx->d_denoise_features) (void)hipFree(ctx->d_denoise_features);
+    if (ctx->denoise_ordered) (void)hipEventDestroy(ctx->denoise_ordered);
     destroy_rccl_communicators(ctx);
     for (auto& r : ctx->pinned_host) (void)hipHostUnregister(r.p);
     (void)hipGetLastError();

@@ -1,5 +1,5 @@
 // ptmi_context.h - the state behind a ptmi_ctx, grouped by WHEN IT DIES, and what the host units of libptmi.so share
-// (ptmi_api.cpp, ptmi_scene_memory.cpp, ptmi_render.cpp, ptmi_readback.cpp, ptmi_query.cpp, ptmi_guides.cpp).  Private: not ABI, never installed.
+// (ptmi_api.cpp, ptmi_scene_memory.cpp, ptmi_render.cpp, ptmi_readback.cpp, ptmi_query.cpp, ptmi_guides.cpp, ptmi_denoise.cpp).  Private: not ABI, never installed.
 //
 // Two lifetimes.  PER SCENE (DeviceScene, ContextScene): free_scene_memory() frees what the struct owns and assigns a
 // value-initialised one, so a new per-scene field needs no line anywhere else.  PER CONTEXT (the members DeviceState and ptmi_ctx
@@ -129,6 +129,13 @@ struct ptmi_ctx : ptmi_internal::ContextScene {
     // ptmi_query_rays: rays, and `cap` bytes of hits behind them, on the device; the hits land.  ptmi_render_guides: the planes
     // of one call behind one another, in the same layout on the device and where they land
     ptmi_internal::RoundTrip query_buffers, guide_buffers;
+    // ptmi_denoise / ptmi_denoise_device (ptmi_denoise.cpp), on devices[0], allocated by the first call that needs them: the
+    // feature planes between the filter's passes, 56 bytes per pixel, for either form; for the host form a round trip of 68 more
+    // (the result, which lands, then the guide planes it renders); and the event that orders the host form of a multi-device
+    // context, which runs on the copy stream, behind a device-form call in flight on the main stream
+    char* d_denoise_features = nullptr;
+    ptmi_internal::RoundTrip denoise_buffers;
+    hipEvent_t denoise_ordered = nullptr;
 
     ptmi_internal::ContextScene& scene() { return *this; }
     uint32_t n_dev() const { return (uint32_t)dev.size(); }
@@ -254,6 +261,7 @@ int fold_events(ptmi_ctx* ctx, DeviceState& d);
 // ptmi_readback.cpp
 int snapshot_device(ptmi_ctx* ctx, DeviceState& d, uint32_t slot, int* buffer = nullptr);
 int snapshot_all(ptmi_ctx* ctx, uint32_t slot);
+int gather_snapshot(ptmi_ctx* ctx, uint32_t slot, const float** image);
 void destroy_rccl_communicators(ptmi_ctx* ctx);
 
 }  // namespace ptmi_internal

@@ -278,6 +278,21 @@ int launch_guides_da(const DScene& sc, const DGuides& planes, uint32_t first_ite
 int launch_display_bgr(const float* image_color, const float* image_ray_nb, uint8_t* out, uint32_t width, uint32_t height,
                        uint32_t row_stride, void* stream, std::string* err);
 
+// denoise.hip (compiled once: the filter's arithmetic is the same in both modes): the prepass and `passes` a-trous passes of
+// ptmi_denoise on DEVICE pointers, all on `stream`.  `features` = 56 bytes per pixel of scratch (two e planes, g1, g2); the
+// sigmas arrive as the reciprocals the contract has the host compute in float.  tiled: steps 1 and 2 stage their tile in LDS.
+struct DenoiseJob {
+    const float *color, *ray_nb;                          // float4[W*H] sums, float[W*H] counts
+    const float *albedo, *normal, *position, *hit_count;  // the guide sums over guide_iterations iterations
+    void* features;
+    float* out;  // float4[W*H]
+    uint32_t width, height, passes;
+    bool demodulate, tiled;
+    float guide_iterations;  // (float)guide_iterations
+    float inv_c[5], inv_n, inv_p;
+};
+int launch_denoise(const DenoiseJob& job, void* stream, std::string* err);
+
 // display.hip: out[i] = ((parts[0][i] + parts[1][i]) + parts[2][i]) + ...  in this fixed order (the accumulators of the devices
 // that shared a render, summed on the first one: ptmi_read_image / ptmi_read_snapshot); n_parts <= PTMI_MAX_DEVICES
 int launch_sum_images(float* out, const float* const* parts, uint32_t n_parts, size_t n_floats, void* stream, std::string* err);

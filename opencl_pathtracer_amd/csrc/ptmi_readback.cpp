@@ -144,10 +144,12 @@ int rccl_reduce_snapshots(ptmi_ctx* ctx, uint32_t slot)
     return PTMI_OK;
 }
 
+}  // namespace
+
 // The image of ring slot `slot` on devices[0], ordered on dev[0].copy_stream: the slot itself for one device; for several,
 // every other device's snapshot copied over (each on its own stream, so the transfers use their own xGMI links at the same
-// time) and the sum of all of them, in device order, in ctx->d_reduced.
-int gather_snapshot(ptmi_ctx* ctx, uint32_t slot, const float** image)
+// time) and the sum of all of them, in device order, in ctx->d_reduced.  (ptmi_denoise.cpp gathers through it too.)
+int ptmi_internal::gather_snapshot(ptmi_ctx* ctx, uint32_t slot, const float** image)
 {
     DeviceState& lead = ctx->dev[0];
     const size_t npix = ctx->npix();
@@ -211,8 +213,6 @@ int gather_snapshot(ptmi_ctx* ctx, uint32_t slot, const float** image)
     *image = ctx->d_reduced;
     return PTMI_OK;
 }
-
-}  // namespace
 
 void ptmi_internal::destroy_rccl_communicators(ptmi_ctx* ctx)
 {
