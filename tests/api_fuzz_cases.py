@@ -1,4 +1,4 @@
-"""Random C-ABI call sequences that also move the scene, trace rays and render guides (test_api_fuzz_model.py on the CPU,
+"""Random C-ABI call sequences that also move the scene, trace rays, render guides and denoise (test_api_fuzz_model.py on the CPU,
 test_api_fuzz_scene_gpu.py on the GPU): a generator of scripts, the model of what a script means, and the executor that plays
 a script against a backend and compares everything it reads with the model.  Pure Python and numpy; the product is imported
 only to build scenes (and for its error class and ring size), as the other case modules do.
@@ -12,10 +12,26 @@ write, sync, kernel_time, display, pin) it holds
     ("bad_camera", which)                  an infinite position (0) or a NaN up vector (1): refused
     ("query", any_hit, batch, route)       the first `batch` of the scene's rays, through host arrays or device pointers
     ("guides", first, n, planes, route)    ptmi_render_guides for n iterations from `first`, a subset of the planes
+    ("denoise", first, n, passes, sigmas, demodulate, untiled, route)
+                                           the filter, guided by n iterations from `first`: 0 to 5 passes, one of SIGMA_SETS
 and any of these also BETWEEN two calls of a walk (the last field of a walk: ((call index, operation), ...)), which is when
 launches for calls that have not been made yet are in flight, directly behind a burst, behind an upload, and between a snapshot
-and the read of its slot.  A call through device pointers is not waited for: what it wrote is collected and compared after the
-NEXT operation, so that the next operation - an update, a camera, an upload - runs while it may still be in flight.
+and the read of its slot; a denoise also directly behind a write, a clear or a display.  A call through device pointers is not
+waited for: what it wrote is collected and compared after the NEXT operation, so that the next operation - an update, a camera,
+an upload - runs while it may still be in flight.
+
+The filter.  Its expected value is denoise_cases.denoise, the NumPy float32 restatement, of arrays that are themselves held
+against the model: one arithmetic, every word equal, a NaN where the yardstick has one, and no tolerance on any device count.
+    * route "host": ptmi_denoise first, on whatever the operations before it left in flight (every other time into a third
+      array that is pinned and unpinned with the other two); then ptmi_read_image and ptmi_render_guides.  The image must be the
+      model's (same_image), the four planes the guide yardstick's, and the filtered image the yardstick of exactly those arrays.
+      That holds bit for bit on several devices, where the model's colour sums do not, and does not rest on the few pixels
+      whose albedo the guide yardstick leaves out.
+    * route "device" (one device): ptmi_render_guides_device into four tensors, then ptmi_denoise_device on the context's own
+      accumulators, neither waited for.  Collected: the planes against the guide yardstick, the result against the yardstick
+      of those planes and a copy of the model's accumulators taken at the call.
+    * route "planes" (any device count): the same with sum and count planes of the caller's (seeded_image: some counts are 0).
+A denoise changes nothing in the model.
 
 The states.  A state is (scene name, camera id, triangle version).  Camera c is scene_update_cases.moved_camera(anchor, step=c),
 version 0 the triangles as built, versions 1 and 2 scene_update_cases.displaced of them (seeds VERSION_SEEDS, amplitude 0.02).
@@ -37,8 +53,8 @@ name, c, t) uploads exactly that scene, so a script reaches a state by upload as
 
 The model.  Accumulators, counts, histograms and totals are the sums of the oracle's per-iteration results, on the yardstick
 scene of the state each iteration was rendered in, since the last clear / upload / write; a slot holds the accumulators as they
-were when its snapshot was queued.  A refused call, a query and a guides call change nothing; a camera or an update keeps what
-was rendered.  A super-sampling model runs the oracle statefully on its own arrays instead.
+were when its snapshot was queued.  A refused call, a query, a guides call and a denoise change nothing; a camera or an update
+keeps what was rendered.  A super-sampling model runs the oracle statefully on its own arrays instead.
 """
 import copy
 import warnings
@@ -46,6 +62,7 @@ import warnings
 import numpy as np
 
 from opencl_pathtracer_amd import PtmiError, backend, bvh_create, scenes, structs as S
+import denoise_cases as DN
 import guide_cases as G
 import oracle_ffi as O
 import ray_query_cases as Q
@@ -63,8 +80,16 @@ BATCHES = (1, 257, 1100)  # (one ray, below the 1024-ray floor of the context's 
 GUIDE_FIRSTS = (0, 1)
 RING = backend.USER_SNAPSHOT_SLOTS
 INVALID_ARGUMENT, STATE, UNSUPPORTED = -1, -6, -7
-NEW_OPS = ("camera", "update", "bad_update", "bad_camera", "query", "guides")
+NEW_OPS = ("camera", "update", "bad_update", "bad_camera", "query", "guides", "denoise")
+NEW_OP_WEIGHTS = (0.17, 0.19, 0.08, 0.07, 0.17, 0.16, 0.16)
+DENOISE_PLANES = ("albedo", "normal", "position", "hit_count")  # (the planes the filter reads)
+DENOISE_PASSES = (0, 1, 2, 3, 4, 5)
+# the sigmas of test_denoise_gpu.py (its SIGMAS) and the shipped defaults
+SIGMA_SETS = {"narrow": dict(sigma_color=0.6, sigma_normal=0.5, sigma_position=1.5),
+              "defaults": {key: backend.DENOISE_DEFAULTS[key] for key in ("sigma_color", "sigma_normal", "sigma_position")}}
+DENOISE_ROUTES = ("host", "device", "planes")
 N_OPS, N_OPS_SUPER_SAMPLING = 120, 70
+GENERATOR_SEED = 2  # (of every script's draws: chosen so that test_api_fuzz_model.py's coverage conditions and defect tests hold)
 HIT_FIELDS = ("point", "squared_distance", "s", "t", "triangle_id", "front", "box_tests", "triangle_tests")
 TOTALS = tuple(name for name, _ in O.PtoTotals._fields_)
 
@@ -242,7 +267,7 @@ class Model:
 
 class _Generator:
     def __init__(self, seed, devices, cap, super_sampling):
-        self.rs = np.random.RandomState([int(seed), 2 if super_sampling else 1])
+        self.rs = np.random.RandomState([int(seed), 2 if super_sampling else 1, GENERATOR_SEED])
         self.multi, self.ss = bool(devices), super_sampling
         self.bursts = not flags_of(seed, super_sampling)[1]  # (ptmi_render_snapshots wants the wavefront kernel)
         self.few = RING if seed % 2 else 6  # (even seeds: six slots, so that snapshots overwrite each other all the time)
@@ -253,9 +278,21 @@ class _Generator:
     def choice(self, items):
         return items[int(self.rs.randint(0, len(items)))]
 
+    def denoise(self):
+        rs = self.rs
+        first = GUIDE_FIRSTS[int(rs.rand() < 0.15)]  # (as for guides: the yardstick's iterations are traced once and kept)
+        n = int(rs.choice([1, 1, 1, 2, 3]))
+        passes, sigmas = self.choice(DENOISE_PASSES), self.choice(sorted(SIGMA_SETS))
+        demodulate, untiled = bool(rs.rand() < 0.5), bool(rs.rand() < 0.5)
+        # the context's own accumulators through device pointers: one device only (several: refused, test_denoise_gpu.py)
+        route = str(rs.choice(DENOISE_ROUTES, p=[0.6, 0.0, 0.4] if self.multi else [0.4, 0.3, 0.3]))
+        return ("denoise", first, n, passes, sigmas, demodulate, untiled, route)
+
     def new_op(self):
         rs = self.rs
-        kind = str(rs.choice(NEW_OPS, p=[0.2, 0.22, 0.1, 0.08, 0.2, 0.2]))
+        kind = str(rs.choice(NEW_OPS, p=NEW_OP_WEIGHTS))
+        if kind == "denoise":
+            return self.denoise()
         if kind == "camera":
             return ("camera", self.choice(CAMERAS))
         if kind == "update":
@@ -338,9 +375,11 @@ class _Generator:
             return [("read_image", bool(rs.rand() < 0.5))]
         if op == "upload":
             return [self.upload()] + ([self.new_op()] if rs.rand() < 0.6 else [])
+        # the filter on accumulators that were just written, emptied or shown (the display shares the host form's internal slot)
+        behind = [self.denoise()] if op in ("write", "clear", "display") and rs.rand() < 0.35 else []
         if op == "write":
-            return [("write", int(rs.randint(0, 1 << 30)), int(rs.randint(0, 9)))]
-        return [(op,)]  # statistics, counters, clear, sync, kernel_time, display, pin, variance, save, resume
+            return [("write", int(rs.randint(0, 1 << 30)), int(rs.randint(0, 9)))] + behind
+        return [(op,)] + behind  # statistics, counters, clear, sync, kernel_time, display, pin, variance, save, resume
 
 
 def script(seed, devices, cap, super_sampling=False):
@@ -382,6 +421,38 @@ class HostIO:
         got = be.render_guides(first, n, planes=planes)
         return lambda: got
 
+    def denoise(self, be, first, n, image, params):
+        """-> a function that returns (the filtered image, the four guide planes it was guided by).  image None: the backend's
+        accumulators, through be.denoise.  The host calls have no way to pass image planes: (colour sums, counts) are filtered
+        here, by the yardstick on the backend's guide planes, so that route checks nothing of a backend without a device."""
+        guides = be.render_guides(first, n, planes=DENOISE_PLANES)
+        if image is None:
+            got = be.denoise(**params)
+        else:
+            got = denoise_yardstick(image, guides, params)
+        return lambda: (got, guides)
+
+
+def denoise_parameters(op):
+    """The keywords of Backend.denoise / denoise_device for a ("denoise", ...) operation."""
+    _, first, n, passes, sigmas, demodulate, untiled, _ = op
+    return dict(passes=passes, demodulate=demodulate, untiled=untiled, guide_first_iteration=first, guide_iterations=n, **SIGMA_SETS[sigmas])
+
+
+def denoise_yardstick(image, guides, params):
+    """denoise_cases.denoise of (colour sums, counts) and the four guide planes under the keywords of denoise_parameters
+    (`untiled` chooses a kernel, not an arithmetic)"""
+    return DN.denoise(image[0], image[1], **{name: guides[name] for name in DENOISE_PLANES}, passes=params["passes"],
+                      flags=DN.DEMODULATE if params["demodulate"] else 0, guide_iterations=params["guide_iterations"],
+                      sigma_color=params["sigma_color"], sigma_normal=params["sigma_normal"], sigma_position=params["sigma_position"])
+
+
+def seeded_image(seed):
+    """Colour sums uniform in [0, 4) with per-pixel sample counts from 0 to 8, some of them 0: the planes a caller hands the filter"""
+    rs = np.random.RandomState(seed)
+    color = rs.uniform(0, 4, (H, W, 4)).astype(np.float32)
+    return color, rs.randint(0, 9, (H, W)).astype(np.float32)
+
 
 def bad_camera(sc, which):
     bad = copy.copy(sc)
@@ -394,8 +465,8 @@ def bad_camera(sc, which):
 
 def run(script_ops, be, model, io=None, exact=True):
     """Plays `script_ops` against `be` (a Backend with its context set up, or something that looks like one) and holds everything
-    it reads against `model`.  `io`: how calls through device pointers are made, an object with query() and guides() that
-    return a function to collect the result with (HostIO: through the host calls).  `exact`: colour sums bit for bit (one
+    it reads against `model`.  `io`: how calls through device pointers are made, an object with query(), guides() and denoise()
+    that return a function to collect the result with (HostIO: through the host calls).  `exact`: colour sums bit for bit (one
     device); else within the association error of several devices' partial sums.  Raises Mismatch with the last 40 calls.
     Returns the number of operations made, per kind."""
     from opencl_pathtracer_amd import output
@@ -403,6 +474,8 @@ def run(script_ops, be, model, io=None, exact=True):
     world, m = model.world, model
     history, made, pending = [], {}, []
     pinned = [np.empty((H, W, 4), np.float32), np.empty((H, W), np.float32)]
+    pinned_result = np.empty((H, W, 4), np.float32)  # (where every other host-route denoise lands; pinned and unpinned with the two)
+    host_denoises = [0]
     is_pinned = [False]
     saved = [None]
 
@@ -493,6 +566,40 @@ def run(script_ops, be, model, io=None, exact=True):
                 pending.append(lambda: compare(collect()))
             else:
                 compare(be.render_guides(first, n, planes=planes))
+        elif kind == "denoise":
+            route, params = op[7], denoise_parameters(op)
+            first, n = op[1], op[2]
+            want_planes, excluded = world.planes(m.state, m.da, first, n)
+
+            def compare(got, image, guides):
+                check(set(guides) == set(DENOISE_PLANES), f"denoise: planes {sorted(guides)}", op)
+                msg = G.describe_difference(guides, want_planes, excluded)
+                check(not msg, "denoise: the guide planes: " + msg, op)
+                msg = DN.describe_difference(got, denoise_yardstick(image, guides, params))
+                check(not msg, f"denoise ({route}): " + msg, op)
+
+            if route == "host":
+                # first the call, on whatever the operations before it left in flight; then what it had to filter
+                host_denoises[0] += 1
+                out = pinned_result if host_denoises[0] % 2 else None
+                if out is not None:
+                    out.fill(-1.0)
+                got = be.denoise(out=out, **params)
+                image = be.read_image()
+                guides = be.render_guides(first, n, planes=DENOISE_PLANES)
+                same_image(image, m.color, m.count, "image behind a denoise", op)
+                compare(got, image, guides)
+            else:
+                # through device pointers, not waited for: the context's accumulators as the model has them now (one device:
+                # exact), or planes of the caller's
+                image = (m.color.copy(), m.count.copy()) if route == "device" else seeded_image([len(history), first, n, op[3]])
+                collect = io.denoise(be, first, n, None if route == "device" else image, params)
+
+                def collected():
+                    got, guides = collect()
+                    compare(got, image, guides)
+
+                pending.append(collected)
         elif kind == "render":
             be.render(op[1], op[2])
             m.render(op[1], op[2])
@@ -542,7 +649,7 @@ def run(script_ops, be, model, io=None, exact=True):
                 be.write_variance(saved[0][2])
                 m.write(*saved[0])
         elif kind == "pin":
-            for a in pinned:
+            for a in pinned + [pinned_result]:
                 (be.unpin_host_buffer if is_pinned[0] else be.pin_host_buffer)(a)
             is_pinned[0] = not is_pinned[0]
         elif kind == "sync":
@@ -583,7 +690,7 @@ def run(script_ops, be, model, io=None, exact=True):
     for collect in pending:
         collect()
     if is_pinned[0]:
-        for a in pinned:
+        for a in pinned + [pinned_result]:
             be.unpin_host_buffer(a)
     made.pop("walk call", None)
     made.pop("final image", None)

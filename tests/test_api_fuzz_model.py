@@ -1,7 +1,9 @@
 """The random scene call sequences of api_fuzz_cases.py, checked without a GPU: the conditions their inputs must meet for a stale
 scene to be noticed, what the shipped scripts cover, and that the executor catches a backend with a defect.  The backend here is
-a fake made of the same oracle and yardstick data as the model, with one switch per defect.  A failed condition is mended by
-choosing other seeds in api_fuzz_cases.py (VERSION_SEEDS, RAY_SEED, the generator's), never by relaxing the condition."""
+a fake made of the same oracle and yardstick data as the model, with one switch per defect; its filter is the yardstick of
+denoise_cases.py on its own image and guide planes, so a defect in what the filter reads, guides itself by or leaves behind is
+a switch like the others.  A failed condition is mended by choosing other seeds in api_fuzz_cases.py (VERSION_SEEDS, RAY_SEED,
+GENERATOR_SEED), never by relaxing the condition."""
 import itertools
 
 import numpy as np
@@ -67,6 +69,41 @@ def test_states_are_distinguishable(name, da):
             assert same == (a[2] == b[2]), (a, b, any_hit)
             if a[2] != b[2]:  # ... and already in the 257 rays of the middle batch
                 assert not np.array_equal(Q.words(WORLD.hits(a, da)[1][any_hit][:257]), Q.words(WORLD.hits(b, da)[1][any_hit][:257])), (a, b)
+
+
+def filtered(state, da, sigmas, demodulate, passes):
+    """the filter's yardstick on iteration 0's image, guided by iteration 0's planes"""
+    color, count = WORLD.per_iteration(state, da, 0)[:2]
+    params = dict(F.SIGMA_SETS[sigmas], passes=passes, demodulate=demodulate, guide_iterations=1)
+    return F.denoise_yardstick((color, count), WORLD.planes(state, da, 0, 1)[0], params)
+
+
+FILTERS = [(sigmas, demodulate) for sigmas in sorted(F.SIGMA_SETS) for demodulate in (False, True)]
+
+
+@ARITHMETICS
+@pytest.mark.parametrize("name", F.SCENES)
+def test_the_filter_has_something_to_do(name, da):
+    """Five passes change at least a quarter of the pixels against none, in every state, with either set of sigmas, demodulated
+    or not: a filter that ran fewer passes, or none, is seen.  The quarter is a condition on the scenes and sigmas chosen (the
+    yardstick alone gives at least 0.35 on every one of them), not a measurement of any filter."""
+    for state in STATES[name]:
+        for sigmas, demodulate in FILTERS:
+            five, none = (filtered(state, da, sigmas, demodulate, passes).view(np.uint32)[..., :3] for passes in (5, 0))
+            changed = (five != none).any(axis=2).mean()
+            assert changed >= 0.25, (state, sigmas, demodulate, changed)
+
+
+@ARITHMETICS
+@pytest.mark.parametrize("name", F.SCENES)
+def test_filtered_states_are_distinguishable(name, da):
+    """The filtered iteration-0 images of any two states of a scene differ, whichever of the scripts' filters made them: a
+    filter guided by, or fed from, a stale scene is seen."""
+    for sigmas, demodulate in FILTERS:
+        for passes in (0, 5):
+            images = {state: filtered(state, da, sigmas, demodulate, passes).view(np.uint32) for state in STATES[name]}
+            for a, b in itertools.combinations(STATES[name], 2):
+                assert not np.array_equal(images[a], images[b]), (a, b, sigmas, demodulate, passes)
 
 
 @ARITHMETICS
@@ -152,31 +189,83 @@ def test_script_coverage():
         assert {"camera", "update", "query", "guides"} <= kinds, (seed, kinds)
         union |= kinds
     assert {"variance", "resume", "snapshot", "read_slot", "upload", "bad_update", "bad_camera"} <= union, union
+    denoise_coverage()
+
+
+def denoise_coverage():
+    """What the shipped scripts ask of the filter: every pass count, both sigma sets with and without demodulation, both kernels
+    of steps 1 and 2, all three routes, and a call directly behind each operation that changes what the filter reads."""
+    passes, sigma_flags, untiled, routes, behind, lazy_copy = set(), set(), set(), set(), set(), set()
+    nansafe = next_to_display = 0
+    for (seed, cap, ids), ops in shipped_scripts():
+        # the calls in the order they are made: an operation inside a walk, and the one behind a walk, follow a call of the walk
+        made, behind_a_walk_call = [], False
+        for op, in_walk in F.flat(ops):
+            made += [("walk call",), op] if in_walk or behind_a_walk_call else [op]
+            behind_a_walk_call = in_walk or op[0] == "walk"
+        name = None
+        for i, op in enumerate(made):
+            if op[0] == "upload":
+                name = op[1]
+            if op[0] != "denoise":
+                continue
+            _, first, n, p, sigmas, demodulate, tiles_off, route = op
+            assert first in F.GUIDE_FIRSTS and 1 <= n <= 3 and sigmas in F.SIGMA_SETS and route in F.DENOISE_ROUTES
+            passes.add(p)
+            sigma_flags.add((sigmas, demodulate))
+            if p >= 1:
+                untiled.add(tiles_off)
+            routes.add(route)
+            nansafe += name in F.NANSAFE
+            before, after = made[i - 1], made[i + 1] if i + 1 < len(made) else ("end",)
+            next_to_display += "display" in (before[0], after[0])
+            behind.add("write of count 0" if before[0] == "write" and before[2] == 0 else before[0])
+        for i, op in enumerate(ops):  # (not inside a walk: a snapshot, the denoise, the read of that slot)
+            if op[0] == "denoise" and op[7] == "host" and ops[i - 1][0] == "snapshot" and i + 1 < len(ops) and ops[i + 1][:2] == ("read_slot", ops[i - 1][1]):
+                lazy_copy.add(ids)
+    assert passes == set(F.DENOISE_PASSES), passes
+    assert sigma_flags == {(s, d) for s in F.SIGMA_SETS for d in (False, True)}, sigma_flags
+    assert untiled == {False, True} and routes == set(F.DENOISE_ROUTES), (untiled, routes)
+    assert {"two", "three"} <= lazy_copy, lazy_copy
+    assert {"update", "camera", "bad_update", "clear", "write of count 0"} <= behind, behind
+    assert nansafe and next_to_display, (nansafe, next_to_display)
+    for seed in F.SUPER_SAMPLING_SEEDS:
+        assert any(op[0] == "denoise" for op, _ in F.flat(F.script(seed, None, None, super_sampling=True))), seed
 
 
 # ---------------------------------------------------------------------------------------------- a backend with defects
 
 DEFECTS = ("guides ignore the last camera", "queries ignore the last update", "the next two renders keep the old camera",
-           "a refused update rewrites the triangles", "a query adds to the counters", "a guides call clears the accumulators")
+           "a refused update rewrites the triangles", "a query adds to the counters", "a guides call clears the accumulators",
+           "the filter's guides ignore the last camera", "the filter's guides ignore the last update",
+           "the filter reads the accumulators as they were before the last render", "a denoise call leaves its result in the accumulators",
+           "several devices: a denoise overwrites the slot of the last snapshot", "the filter ignores the demodulation flag")
 READS = {"read_image", "read_slot", "statistics", "counters", "display", "walk", "walk call", "final image"}
-# defect: (the operations at which it may come to light, the operation that must be among the calls reported with it)
-SURFACES = {DEFECTS[0]: ({"guides"}, "camera"), DEFECTS[1]: ({"query"}, "update"), DEFECTS[2]: (READS, "camera"),
-            DEFECTS[3]: (READS | {"query", "guides"}, "bad_update"), DEFECTS[4]: ({"counters", "walk"}, "query"), DEFECTS[5]: (READS, "guides")}
+# defect: (the operations at which it may come to light, the operations of which one must be among the calls reported with it)
+# (a host-route denoise reads the image behind its own call, so what a denoise leaves in the accumulators may show there first)
+SURFACES = {DEFECTS[0]: ({"guides"}, {"camera"}), DEFECTS[1]: ({"query"}, {"update"}), DEFECTS[2]: (READS, {"camera"}),
+            DEFECTS[3]: (READS | {"query", "guides", "denoise"}, {"bad_update"}), DEFECTS[4]: ({"counters", "walk"}, {"query"}),
+            DEFECTS[5]: (READS | {"denoise"}, {"guides"}),
+            DEFECTS[6]: ({"denoise"}, {"camera"}), DEFECTS[7]: ({"denoise"}, {"update"}),
+            DEFECTS[8]: ({"denoise"}, {"render", "walk", "walk call", "burst"}), DEFECTS[9]: (READS | {"denoise"}, {"denoise"}),
+            DEFECTS[10]: ({"read_slot"}, {"denoise"}), DEFECTS[11]: ({"denoise"}, {"denoise"})}
 
 
 class FakeBackend:
     """The Backend methods the executor uses, answered from a model of its own."""
 
-    def __init__(self, default_arithmetic, megakernel=False, super_sampling=False, defect=None):
+    def __init__(self, default_arithmetic, megakernel=False, super_sampling=False, defect=None, n_devices=1):
         assert defect is None or defect in DEFECTS
         self.m = F.Model(WORLD, default_arithmetic, super_sampling)
-        self.megakernel, self.defect = megakernel, defect
+        self.megakernel, self.defect, self.n_devices = megakernel, defect, n_devices
         self.guide_camera = self.query_version = self.stale = None
+        self.filter_camera = self.filter_version = self.before_render = self.last_slot = None
 
     def initialize_memory(self, scene):
         self.m.upload(scene.fuzz_state)
         _, self.guide_camera, self.query_version = scene.fuzz_state
-        self.stale = None
+        _, self.filter_camera, self.filter_version = scene.fuzz_state
+        self.stale = self.before_render = self.last_slot = None
 
     def literal_kernel_reason(self):
         return "records that can yield NaN distances" if self.m.state[0] in F.NANSAFE else None
@@ -197,6 +286,8 @@ class FakeBackend:
         self.m.state = (name, c, version)
         if self.defect != DEFECTS[0]:
             self.guide_camera = c
+        if self.defect != DEFECTS[6]:
+            self.filter_camera = c
 
     def update_triangles(self, tris):
         name, camera, version = self.m.state
@@ -207,12 +298,14 @@ class FakeBackend:
         found = [t for t in F.VERSIONS if tris is WORLD.triangles(name, t)]
         if not found:
             if self.defect == DEFECTS[3]:  # (what bad triangles render has no yardstick: another version stands for them)
-                self.query_version = (version + 1) % 3
+                self.query_version = self.filter_version = (version + 1) % 3
                 self.m.state = (name, camera, self.query_version)
             raise PtmiError(F.UNSUPPORTED, "ptmi_update_triangles: a triangle is refused")
         self.m.state = (name, camera, found[0])
         if self.defect != DEFECTS[1]:
             self.query_version = found[0]
+        if self.defect != DEFECTS[7]:
+            self.filter_version = found[0]
         return {}
 
     def query_rays(self, origins, directions, max_squared_distance=None, any_hit=False, out=None):
@@ -229,7 +322,23 @@ class FakeBackend:
             self.m.reset()
         return {p: want[p].copy() for p in planes}
 
+    def denoise(self, out=None, **params):
+        """denoise_cases.denoise of the model's own image and the planes render_guides would return"""
+        name = self.m.state[0]
+        want, _ = WORLD.planes((name, self.filter_camera, self.filter_version), self.m.da, params["guide_first_iteration"], params["guide_iterations"])
+        image = self.before_render if self.defect == DEFECTS[8] and self.before_render else (self.m.color, self.m.count)
+        result = F.denoise_yardstick(image, want, dict(params, demodulate=params["demodulate"] or self.defect == DEFECTS[11]))
+        if self.defect == DEFECTS[9]:
+            self.m.write(result, result[..., 3])
+        if self.defect == DEFECTS[10] and self.n_devices > 1 and self.last_slot in self.m.slots:
+            self.m.slots[self.last_slot] = (result.copy(), result[..., 3].copy())
+        if out is None:
+            return result
+        out[...] = result
+        return out
+
     def _render_state(self):
+        self.before_render = (self.m.color.copy(), self.m.count.copy()) if self.defect == DEFECTS[8] else None
         if not self.stale:
             return None
         name, _, version = self.m.state
@@ -249,9 +358,11 @@ class FakeBackend:
         for k in range(n):
             self.m.render(first + k, 1, state)
             self.m.snapshot((slot + k) % F.RING)
+        self.last_slot = (slot + n - 1) % F.RING
 
     def snapshot(self, slot):
         self.m.snapshot(slot)
+        self.last_slot = slot
 
     @staticmethod
     def _out(arrays, out):
@@ -274,6 +385,7 @@ class FakeBackend:
 
     def write_image(self, color, count):
         self.m.write(color, count)
+        self.before_render = None
 
     def write_variance(self, variance):
         self.m.variance = variance.copy()
@@ -286,6 +398,7 @@ class FakeBackend:
 
     def clear(self):
         self.m.reset()
+        self.before_render = None
 
     def read_display(self):
         rgb = output.to_display_rgb(self.m.color, self.m.count)
@@ -308,7 +421,8 @@ class FakeBackend:
 def play(seed, cap, ids, defect=None, super_sampling=False):
     da, megakernel = F.flags_of(seed, super_sampling)
     ops = F.script(seed, F.DEVICES[ids], cap, super_sampling)
-    return F.run(ops, FakeBackend(da, megakernel, super_sampling, defect), F.Model(WORLD, da, super_sampling), exact=ids == "one")
+    fake = FakeBackend(da, megakernel, super_sampling, defect, n_devices=len(F.DEVICES[ids] or [0]))
+    return F.run(ops, fake, F.Model(WORLD, da, super_sampling), exact=ids == "one")
 
 
 def test_every_shipped_script_passes_on_a_backend_without_defects():
@@ -323,7 +437,7 @@ def test_every_shipped_script_passes_on_a_backend_without_defects():
 
 @pytest.mark.parametrize("defect", DEFECTS)
 def test_a_defect_is_caught(defect):
-    where, culprit = SURFACES[defect]
+    where, culprits = SURFACES[defect]
     for seed, cap, ids in F.shipped_cases():
         try:
             play(seed, cap, ids, defect)
@@ -332,7 +446,7 @@ def test_a_defect_is_caught(defect):
             # an upload undoes every one of these defects: the culprit must lie between the last upload and the mismatch
             kinds = [op[0] for op in e.history]
             since_upload = kinds[len(kinds) - kinds[::-1].index("upload"):] if "upload" in kinds else kinds
-            assert culprit in since_upload, str(e)
+            assert culprits & set(since_upload), str(e)
             assert " ".join(str(op) for op in e.history[-3:]) in str(e)  # (the calls are in the message)
             return
     pytest.fail(f"no shipped script notices that {defect}")

@@ -67,15 +67,17 @@ def yardstick_of(be, first, n, **params):
 
 # ---------------------------------------------------------------------------------------------- the kernels against the yardstick
 
-SIZES = [(1, 1), (5, 3), (33, 9), (70, 37), (130, 66)]
+SIZES = [(1, 1), (5, 3), (33, 9), (64, 16), (70, 37), (130, 66)]
 
 
-@pytest.mark.parametrize("passes", [0, 1, 3, 5])
+@pytest.mark.parametrize("passes", [0, 1, 2, 3, 4, 5])
 @pytest.mark.parametrize("size", SIZES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_synthetic_planes(size, passes):
-    """One pixel; less than one footprint; a ragged row of tiles; more than one tile each way with ragged edges; and an image in
+    """One pixel; less than one footprint; a ragged row of tiles; two tiles by two of the tiled form's 32 x 8 (one by four
+    workgroups of the direct form's 64 x 4) with nothing ragged; more than one tile each way with ragged edges; and an image in
     which step 16 reaches across several tiles and out of the image.  With and without demodulation, steps 1 and 2 from the LDS
-    tile and from memory."""
+    tile and from memory; every pass count, so that each step's kernel is also the last one, which stores the re-modulated
+    image."""
     w, h = size
     planes, g = D.synthetic(w, h, seed=w * 1000 + h)
     tensors = {name: to_device(a) for name, a in planes.items()}
