@@ -284,6 +284,13 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
     // records' bits with sc.leaf_cull.
     static_assert(!CULL || PRE, "cull bits are computed for precomputed records only");
     constexpr bool kCull = CULL;
+    // Which culling instantiations take the counting step (cull_step, below): the plain ones and the general one of 64 lanes.
+    // The general instantiations of 256 lanes (production and statistics) keep the rule inside node_step as it was: under the
+    // counting step the allocator spills more of <0,1,0,0,0,256,1> than tests/test_path_logic_loads.py pins (default arithmetic
+    // 41 registers for 28, strict 62 for 57, with four / two full waits more in the pass).  Node-trip path, vector / scalar
+    // instructions (tools/kernel_resources.py; DESIGN.md 5, "The node step's diet"): plain 170 / 104 -> 156 / 100, general 64
+    // lanes 180 / 104 -> 162 / 100.
+    constexpr bool kCountStep = CULL && (PLAIN || BLOCK == kWfBlockNarrow);
     extern __shared__ __attribute__((aligned(16))) uint32_t stack_mem[];
     // (the statistics build: one block with every counter, its launches never render for several calls)
     constexpr uint32_t kBlockCounters = STATS ? (uint32_t)C_COUNT : PTMI_COUNTER_SPLITS * kSplitWords;
@@ -371,7 +378,7 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
     bool exact_boxes = false;  // this ray needs the literal box test (see box_hit_ordered)
     bool wave_exact = true;    // ... and so does some ray of this wave (wave-uniform, refreshed after every path-logic pass)
     uint32_t cur = REF_IDLE, tri_i = 0, tri_end = 0;
-    uint32_t dir_signs = 0;  // bit k: direction component k > 0 (which child of a node cut along k is the near one); bits 3, 4: see node_step
+    uint32_t dir_signs = 0;  // bit k: direction component k > 0 (which child of a node cut along k is the near one); bits 3 to 5: the cull bits this ray honours (ray set-up; read by node_step and cull_step)
     uint32_t* sp = stack_floor;  // the top entry (the sentinel when the stack is empty)
     uint32_t tos = REF_NONE;     // kTos: ... and its value; invariant tos == *sp
     // the point of the closest hit, as path logic needs it when a query has finished
@@ -601,12 +608,88 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
             if (tri_i >= tri_end && ref_is_leaf(cur)) enter_leaf(false);
         }
     };
+    // The node step of the instantiations that cull leaves (kCull), behind the record's loads.
+    // A child of the record is COUNTED instead of visited when the ray hit its box, the record certifies it as a leaf of the
+    // tier the launch looks at, the box - still in the step's registers - lies beyond the limit (leaf_cull.h: then every triangle
+    // of it is rejected) and the step may judge it:
+    //   * as the child it chooses (the near one, or the only one hit).  Closest-hit and shadow queries alike (acceptance is
+    //     `nsd <= limit` for both, cl:537; a shadow query that accepts nothing counts the whole leaf);
+    //   * as the FAR child of a step that hits both, where it would be pushed: a closest-hit query's limit only shrinks, so the
+    //     rule still holds when the entry would be popped, and every entry such a query pushes is popped and tested in full, so
+    //     the count is the same sum.  Not in a shadow query, which ends at its first accepted triangle with the leaves on its
+    //     stack uncounted (its rays do not carry kCullPushed).
+    // The lane adds the counted children's triangles in ONE update, and the step goes on as if the ray had MISSED them: that
+    // leaves the state the walk reaches after the leaf's last pass (a counted chosen child: what would have been pushed takes its
+    // place, or the step pops; a counted far child: not pushed), through the pops an ordinary step has - no pop of its own for a
+    // culled leaf, and none behind it.
+    // Counted and dropped (node-trip path of <0,1,0,1,0,256,1>, default arithmetic, vector / scalar; this form 156 / 100, the
+    // parent 170 / 104; profiles/node_step_diet_ab.txt):
+    //   the record's bits tested by and / compare and ANDed with the hit masks: 0 / 1 integers in vector registers, 168 / 91;
+    //   the decisions on ballots, inverse_ballot for the selects: 162 / 103 (a ballot of anything but one compare is a
+    //     v_cndmask and a v_cmp, and with the record passed as a NodeView its references went through scratch);
+    //   the signs from bit 31 down (`word << axis` puts the axis' own into the sign bit), cull bits in bits 0 to 2: 156 / 99,
+    //     five spilled registers for four;
+    //   the threshold kept beside the limit, made where the limit is written: 154 / 101, the leaf pass 147 vector instructions
+    //     for 146, nine spilled registers in the strict build;
+    //   ONE uniform branch between the two box tests (a scalar word instead of `wave_exact`): 157 / 97, 25 v_mov in the loop
+    //     for 24, eight spilled registers in the strict build, the ordered test behind two taken branches;
+    //   without the opaque asm between the two distances: 153 / 101, ten spilled registers in the strict build.
+    auto cull_step = [&](const float4 a, const float4 b, const float4 c, const float4 d) {
+        const NodeView n = node_view(a, b, c, d);
+        // the squared distances of the origin from the two boxes: either test makes them from its own slab differences (three
+        // medians and three multiply-adds each; leaf_cull.h: box_distance2_from_slabs)
+        float d2_1 = 0, d2_2 = 0;
+        bool hit1, hit2;
+        if (!wave_exact) {
+            hit1 = box_hit_ordered(n.lo1, n.hi1, r, limit, &d2_1);
+            // (the first distance made HERE, before the second box's differences exist: left alone, the compiler holds both
+            // boxes' differences at once - spilled registers around the loop, tools/kernel_resources.py: plain 8 -> 5, 64 lanes 9 -> 4)
+            asm volatile("" : "+v"(d2_1));
+            hit2 = box_hit_ordered(n.lo2, n.hi2, r, limit, &d2_2);
+        } else {
+            hit1 = box_hit(n.lo1, n.hi1, (n.ref1 & REF_EMPTY) != 0, r, limit, &d2_1);
+            hit2 = box_hit(n.lo2, n.hi2, (n.ref2 & REF_EMPTY) != 0, r, limit, &d2_2);
+        }
+        p_bbx += 2;
+        // dir[cutAxis] > 0 (:663) from the ray's word of the three signs
+        const bool fwd = ((dir_signs >> n.axis) & 1u) != 0;
+        // The record's word shifted down to the tier this launch looks at - the wide tier's three bits, which hold the leaves of
+        // either tier (leaf_cull.h), or the tight tier's - and ANDed with what this ray honours of them in this launch (bits 3
+        // to 5 of its word, made where the ray is set up).  kCullPushed is the highest of the three.
+        const uint32_t cull_bits = (n.cull >> sc.cull_shift) & (dir_signs >> 3);
+        static_assert(ptmi_cull::kCullChild1 == 1u && ptmi_cull::kCullChild2 == 2u && ptmi_cull::kCullPushed == 4u, "the tests below");
+        const bool may_push = cull_bits >= ptmi_cull::kCullPushed;
+        // "certified and beyond" as ONE compare per child (leaf_cull.h: certified_and_beyond_wide).  ONE rule, the wide one, for
+        // the leaves of both tiers: a margin per child would cost a select of two constants per box.
+        const float beyond = -ptmi_cull::cull_threshold_wide(limit);
+        // (the far child of a step that hits both and may not count what it would push is the one child the rule does not judge)
+        const bool chosen_only = hit1 & hit2 & !may_push;
+        const bool counted1 = hit1 & ptmi_cull::certified_and_beyond_wide(cull_bits, d2_1, beyond) & !(chosen_only & !fwd);
+        const bool counted2 = hit2 & ptmi_cull::certified_and_beyond_wide(cull_bits >> 1, d2_2, beyond) & !(chosen_only & fwd);
+        const uint32_t n_counted = (counted1 ? ref_leaf_count(n.ref1) : 0u) + (counted2 ? ref_leaf_count(n.ref2) : 0u);
+        p_tri += n_counted;
+        if (STATS) culled_items += n_counted;
+        const bool go1 = hit1 & !counted1, go2 = hit2 & !counted2;
+        const uint32_t far_ref = fwd ? n.ref2 : n.ref1;
+        sp[kWfBlock] = far_ref;
+        const uint32_t child = fwd ? (go1 ? n.ref1 : n.ref2) : (go2 ? n.ref2 : n.ref1);  // near child if the ray goes there, else the far one
+        // both: the far child becomes the top; one: nothing moves; none: the step pops (and the pop replaces `cur`)
+        cur = child;
+        if (kTos) tos = go1 ? (go2 ? far_ref : tos) : tos;
+        sp = go1 ? (go2 ? sp + kWfBlock : sp) : sp;
+        if (!(go1 | go2)) pop();
+        if (ref_is_leaf(cur)) enter_leaf(false);  // (the triangle range of a lane that takes node steps is free)
+    };
     // one inner-node step of the calling lanes (:660-697)
     // (always the 64-bit address form: one instruction more than a scalar base + 32-bit byte offset, which only serves a record
     // array below 4 GB; measured faster - 851 vs 837 Msamples/s - than choosing between the two)
     auto node_step = [&]() {
         const float4* const rec = reinterpret_cast<const float4*>(&sc.tris[cur & REF_INDEX_MASK_INNER]);
         const float4 a = rec[0], b = rec[1], c = rec[2], d = rec[3];
+        if constexpr (kCountStep) {
+            cull_step(a, b, c, d);
+            return;
+        }
         const NodeView n = node_view(a, b, c, d);
         // dir[cutAxis] > 0 (:663) from a per-ray word of the three signs (one bit test; selected from the three sign masks
         // the box tests hold it took three compares and five scalar instructions)
@@ -977,8 +1060,9 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
                 dir_signs = (r.d.x > 0 ? 1u : 0u) | (r.d.y > 0 ? 2u : 0u) | (r.d.z > 0 ? 4u : 0u);
                 // ... and, above the signs, the cull bits of a node record this ray honours (leaf_cull.h: ray_may_cull): the two
                 // children, and - a closest-hit query only - the bit that lets a step count the far child instead of pushing it
+                // (kCountStep: ... of those this launch looks at, sc.leaf_cull)
                 if (kCull && ptmi_cull::ray_may_cull(r.o.x, r.o.y, r.o.z, r.o.w, r.d.w))
-                    dir_signs |= (ptmi_cull::kCullChild1 | ptmi_cull::kCullChild2 | (shadow ? 0u : ptmi_cull::kCullPushed)) << 3;
+                    dir_signs |= ((ptmi_cull::kCullChild1 | ptmi_cull::kCullChild2 | (shadow ? 0u : ptmi_cull::kCullPushed)) & (kCountStep ? sc.leaf_cull : ~0u)) << 3;
                 // A ray that is not a number - a refraction at |cos| = 1 + 1 ulp takes the square root of a negative (cl:235),
                 // a hit on a fake plane 1e30 away overflows - makes every triangle test compute a NaN distance, and the
                 // reference ACCEPTS those (its rejections are comparisons, cl:533-567): from then on nothing is "too far" and

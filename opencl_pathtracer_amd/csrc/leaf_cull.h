@@ -110,9 +110,31 @@ PTMI_HD bool leaf_cull_rule(float d2, float limit, float ox, float oy, float oz,
     return box_is_beyond(d2, limit) && ray_may_cull(ox, oy, oz, ow, dw);
 }
 // the wide pair's (what node_step evaluates, for the leaves of both tiers)
+// (the right-hand side by itself: it changes only with the limit, and a node step judges two boxes against it)
+PTMI_HD float cull_threshold_wide(float limit)
+{
+    return fmaf(limit, kRelWide, kAbsWide);
+}
 PTMI_HD bool box_is_beyond_wide(float d2, float limit)
 {
-    return d2 > fmaf(limit, kRelWide, kAbsWide);  // (false for a NaN)
+    return d2 > cull_threshold_wide(limit);  // (false for a NaN)
+}
+// "The record certifies the child AND its box lies beyond" as ONE compare (what the kernel's counting step evaluates per child):
+// bit 0 of `certified` becomes the sign of the distance - which is never negative - and -d2 < -threshold is d2 > threshold;
+// an uncertified child keeps a key >= 0, which is never below a negated threshold that is not positive.
+// PRECONDITION: neg_threshold <= 0 or a NaN, i.e. neg_threshold = -cull_threshold_wide(limit) of a limit that is not negative
+// (the kernel's limits are squared distances, a linear distance or +inf; then the threshold is at least kAbsWide).  For a
+// limit below -kAbsWide / kRelWide the negated threshold is positive and an UNCERTIFIED child nearer than it would compare
+// true: not what this function is for (tests/test_node_step_diet.py pins both sides of that line).
+// False for a NaN on either side, as box_is_beyond_wide is.
+PTMI_HD bool certified_and_beyond_wide(uint32_t certified, float d2, float neg_threshold)
+{
+    uint32_t bits;
+    __builtin_memcpy(&bits, &d2, sizeof bits);
+    bits |= certified << 31;
+    float key;
+    __builtin_memcpy(&key, &bits, sizeof key);
+    return key < neg_threshold;
 }
 PTMI_HD bool leaf_cull_rule_wide(float d2, float limit, float ox, float oy, float oz, float ow, float dw)
 {
