@@ -341,6 +341,57 @@ int ptmi_query_rays(ptmi_ctx* ctx, uint32_t kind, const ptmi_ray* rays, uint32_t
  * rewrite the scene; the caller orders its own reads of d_hits behind the stream (or calls ptmi_synchronize). */
 int ptmi_query_rays_device(ptmi_ctx* ctx, uint32_t kind, const void* d_rays, uint32_t n_rays, void* d_hits);
 
+/* ---- full paths along the caller's rays ------------------------------------ */
+
+/* What light arrives along rays of the caller's own: other camera models (thin lens, orthographic, fisheye, panorama, stereo,
+ * per-ray motion blur), light probes and irradiance bakes, a radiance readout at a picked point.  Ray i is traced for the
+ * iterations it = first_iteration, ..., first_iteration + n_iterations - 1, in that order, and each one is Kernel_Main's path
+ * (FullKernel.cl:1180-1331) with its camera ray replaced by the caller's:
+ *   index   = first_index + i + it * index_stride, modulo 2^32: the gx + gy * W + it * W * H of InitializeRandomSeed;
+ *   seed    = InitializeRandomSeed of that index, with the compiled reference's zero rule (PTMI_FLAG_SOURCE_SEED is honoured);
+ *   sampler = the context's sampler is then drawn as Kernel_Main draws it and the values are discarded: two random() for
+ *             JITTERED and RANDOM, none for UNIFORM.  There is no SUPER_SAMPLING stop-criterion draw: SUPER_SAMPLING is ignored;
+ *   ray     = Ray3D_Create of (origin, direction), exactly as in ptmi_query_rays; max_squared_distance and reserved are NOT
+ *             read (Kernel_Main's segments start unlimited);
+ *   loop    = Kernel_Main's bounce loop from there: ray_max_depth, every light at every hit, the materials, the sky,
+ *             PTMI_FLAG_RUSSIAN_ROULETTE, in the context's arithmetic, against the geometry the context holds NOW.
+ * sums[i].radiance starts at +0 and adds each path's radiance in iteration order, all four components; the five counts add what
+ * ptmi_counters would have gained from those paths.  So with the built-in camera's rays, first_index = 0 and index_stride = W*H,
+ * ray gy * W + gx gets bit for bit the radiance ptmi_render adds to that pixel (JITTERED and UNIFORM).  With RANDOM the result
+ * is still the ray's own: nothing "lands" anywhere.  Where a word is a NaN its sign and payload mean nothing, as for
+ * ptmi_ray_hit.  A scene with a ptmi_literal_kernel_reason is served, as by the ray queries.
+ * ONE LANE OWNS ONE RAY FOR ALL ITS ITERATIONS: a caller with few rays and many iterations gets more parallelism by repeating
+ * the ray with different first_index.  n_iterations is at most PTMI_MAX_PATH_ITERATIONS, which bounds the time of one launch
+ * on a shared device: a caller who wants more chains calls (first_iteration moving on) and adds the sums itself.
+ * A CALL TOUCHES NOTHING THAT HAS BEEN RENDERED, with the same list as the ray queries: accumulators, histograms, ptmi_counters,
+ * scheduler statistics, snapshots and launches rendered ahead stay as they are.  Both calls run on devices[0] of a multi-device
+ * context, on its main stream (ptmi_set_stream's, where one was given); the calls that rewrite scene records wait for that
+ * stream first.
+ * PTMI_ERR_STATE before ptmi_initialize_memory; PTMI_ERR_INVALID_ARGUMENT for NULL params, a wrong struct_size, a non-zero
+ * reserved word, n_iterations > PTMI_MAX_PATH_ITERATIONS, NULL rays or sums with work to do, or a device pointer that is not
+ * 16-byte aligned; n_rays == 0 or n_iterations == 0 is PTMI_OK, launches nothing and writes nothing.  After any error the
+ * context renders as before. */
+#define PTMI_MAX_PATH_ITERATIONS 4096u
+typedef struct ptmi_path_params {   /* 32 bytes */
+    uint32_t struct_size;           /* = sizeof(ptmi_path_params) */
+    uint32_t first_iteration, n_iterations;   /* n_iterations <= PTMI_MAX_PATH_ITERATIONS */
+    uint32_t first_index, index_stride;
+    uint32_t reserved[3];           /* 0 */
+} ptmi_path_params;
+
+typedef struct ptmi_path_sum {      /* 48 bytes: three 16-byte quads, like ptmi_ray_hit */
+    ptmi_float4 radiance;           /* sum over the iterations */
+    uint32_t segments, surface_hits, shadow_rays, reserved;   /* the ptmi_counters terms of these paths alone */
+    uint64_t box_tests, triangle_tests;
+} ptmi_path_sum;
+
+/* Host arrays: as for ptmi_query_rays - a scratch buffer of the context's own (allocated by the first call, grown on demand,
+ * freed by ptmi_release: a context that never asks pays nothing), and the sums come down straight into `sums` where the caller
+ * has page-locked it (ptmi_pin_host_buffer). */
+int ptmi_trace_paths(ptmi_ctx* ctx, const ptmi_path_params* params, const ptmi_ray* rays, uint32_t n_rays, ptmi_path_sum* sums);
+/* Device pointers, 16-byte aligned: asynchronous on the context's stream, ordered like ptmi_query_rays_device. */
+int ptmi_trace_paths_device(ptmi_ctx* ctx, const ptmi_path_params* params, const void* d_rays, uint32_t n_rays, void* d_sums);
+
 /* ---- first-hit guide buffers ----------------------------------------------- */
 
 /* What the camera sees, per pixel, without rendering it: albedo, shading normal and position planes (denoiser inputs), a hit

@@ -103,6 +103,14 @@ class DenoiseParams(C.Structure):
                 ("sigma_position", C.c_float), ("reserved", C.c_uint32 * 2)]
 
 
+class PathParams(C.Structure):
+    """ptmi_path_params: which iterations ptmi_trace_paths traces for every ray, and the index its seeds come from."""
+    _fields_ = [("struct_size", C.c_uint32), ("first_iteration", C.c_uint32), ("n_iterations", C.c_uint32),
+                ("first_index", C.c_uint32), ("index_stride", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+MAX_PATH_ITERATIONS = 4096  # ptmi.h: PTMI_MAX_PATH_ITERATIONS
+
 DENOISE_DEMODULATE_ALBEDO, DENOISE_UNTILED = 1, 2  # ptmi.h: PTMI_DENOISE_*
 # The shipped defaults: the RMSE minimum against a 1024-spp render of the Cornell box at 4 spp, over the grid of
 # profiles/denoise_quality_cornell.json (tests/test_denoise_gpu.py holds them to it).  sigma_position is in scene units.
@@ -149,7 +157,7 @@ ABI_SYMBOLS = ["ptmi_setup_context", "ptmi_initialize_memory", "ptmi_render", "p
                "ptmi_abi_version", "ptmi_device_count", "ptmi_device_share", "ptmi_bvh_create",
                "ptmi_bvh_create_device", "ptmi_set_camera", "ptmi_update_triangles", "ptmi_bvh_refit",
                "ptmi_query_rays", "ptmi_query_rays_device", "ptmi_render_guides", "ptmi_render_guides_device",
-               "ptmi_denoise", "ptmi_denoise_device"]
+               "ptmi_denoise", "ptmi_denoise_device", "ptmi_trace_paths", "ptmi_trace_paths_device"]
 
 QUERY_CLOSEST, QUERY_ANY = 0, 1  # ptmi.h: PTMI_QUERY_*
 
@@ -206,6 +214,8 @@ def load_library():
     lib.ptmi_bvh_refit.argtypes = [vp, u32, vp, u32]
     lib.ptmi_query_rays.argtypes = [vp, u32, vp, u32, vp]
     lib.ptmi_query_rays_device.argtypes = [vp, u32, vp, u32, vp]
+    lib.ptmi_trace_paths.argtypes = [vp, C.POINTER(PathParams), vp, u32, vp]
+    lib.ptmi_trace_paths_device.argtypes = [vp, C.POINTER(PathParams), vp, u32, vp]
     lib.ptmi_render_guides.argtypes = [vp, u32, u32, C.POINTER(Guides)]
     lib.ptmi_render_guides_device.argtypes = [vp, u32, u32, C.POINTER(Guides)]
     lib.ptmi_denoise.argtypes = [vp, C.POINTER(DenoiseParams), vp]
@@ -401,6 +411,34 @@ class Backend:
         ``d_hits``: asynchronous on the context's stream."""
         self._check(self._lib.ptmi_query_rays_device(self._ctx, QUERY_ANY if any_hit else QUERY_CLOSEST, C.c_void_p(d_rays), n,
                                                      C.c_void_p(d_hits)))
+
+    # -- full paths along rays of the caller's own (no counterpart in the reference) ----------
+    def path_params(self, n_rays, first_iteration=0, n_iterations=1, first_index=0, index_stride=None):
+        """A ``PathParams``; ``index_stride`` None = ``n_rays``: consecutive iterations then draw from consecutive blocks of indices."""
+        return PathParams(C.sizeof(PathParams), first_iteration, n_iterations, first_index, n_rays if index_stride is None else index_stride)
+
+    def trace_paths(self, origins, directions, first_iteration=0, n_iterations=1, first_index=0, index_stride=None, out=None):
+        """The radiance that arrives along n rays of the caller's: each is traced as a full path of the integrator (every light,
+        every bounce up to ``ray_max_depth``) for iterations [first_iteration, first_iteration + n_iterations), the random
+        numbers of ray i in iteration it being those of index ``first_index + i + it * index_stride`` (None: n).  ``origins`` and
+        ``directions`` as for ``query_rays``.  Returns a ``structs.PATH_SUM`` array (``out``: fill this one, e.g. a page-locked
+        array): ``radiance`` is the SUM over the iterations - divide by ``n_iterations`` for the mean - next to the counts of
+        those paths.  One lane traces one ray for all its iterations: with few rays, repeat them with different ``first_index``
+        instead of raising ``n_iterations`` (at most ``MAX_PATH_ITERATIONS`` per call).  Touches nothing that has been rendered."""
+        rays = make_rays(origins, directions)
+        sums = np.zeros(len(rays), S.PATH_SUM) if out is None else out
+        if sums.dtype != S.PATH_SUM or len(sums) != len(rays) or not sums.flags.c_contiguous:
+            raise PtmiError(-1, "out must be a contiguous structs.PATH_SUM array with one record per ray")
+        p = self.path_params(len(rays), first_iteration, n_iterations, first_index, index_stride)
+        self._check(self._lib.ptmi_trace_paths(self._ctx, C.byref(p), rays.ctypes.data_as(C.c_void_p), len(rays),
+                                               sums.ctypes.data_as(C.c_void_p)))
+        return sums
+
+    def trace_paths_device(self, d_rays, n, d_sums, first_iteration=0, n_iterations=1, first_index=0, index_stride=None):
+        """The same for ``n`` 48-byte ``structs.RAY`` records at device address ``d_rays`` (e.g. ``tensor.data_ptr()``), 48-byte
+        ``structs.PATH_SUM`` records to ``d_sums``: asynchronous on the context's stream."""
+        p = self.path_params(n, first_iteration, n_iterations, first_index, index_stride)
+        self._check(self._lib.ptmi_trace_paths_device(self._ctx, C.byref(p), C.c_void_p(d_rays), n, C.c_void_p(d_sums)))
 
     # -- what the camera sees, per pixel (no counterpart in the reference) ------------------
     def guide_plane(self, name):

@@ -291,6 +291,7 @@ void ptmi_release(ptmi_ctx* ctx)
     free_scene_memory(ctx);
     if (!ctx->dev.empty()) (void)hipSetDevice(ctx->dev[0].device);
     ctx->query_buffers.release();
+    ctx->path_buffers.release();
     ctx->guide_buffers.release();
     ctx->denoise_buffers.release();
     if (ctx->d_denoise_features) (void)hipFree(ctx->d_denoise_features);

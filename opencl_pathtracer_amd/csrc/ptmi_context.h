@@ -1,5 +1,5 @@
 // ptmi_context.h - the state behind a ptmi_ctx, grouped by WHEN IT DIES, and what the host units of libptmi.so share
-// (ptmi_api.cpp, ptmi_scene_memory.cpp, ptmi_render.cpp, ptmi_readback.cpp, ptmi_query.cpp, ptmi_guides.cpp, ptmi_denoise.cpp).  Private: not ABI, never installed.
+// (ptmi_api.cpp, ptmi_scene_memory.cpp, ptmi_render.cpp, ptmi_readback.cpp, ptmi_query.cpp, ptmi_paths.cpp, ptmi_guides.cpp, ptmi_denoise.cpp).  Private: not ABI, never installed.
 //
 // Two lifetimes.  PER SCENE (DeviceScene, ContextScene): free_scene_memory() frees what the struct owns and assigns a
 // value-initialised one, so a new per-scene field needs no line anywhere else.  PER CONTEXT (the members DeviceState and ptmi_ctx
@@ -76,7 +76,7 @@ struct DeviceState : DeviceScene {
     DeviceScene& scene() { return *this; }
 };
 
-// ---- per context: a round trip through devices[0] for host arrays of the caller's (ptmi_query_rays, ptmi_render_guides) - a
+// ---- per context: a round trip through devices[0] for host arrays of the caller's (ptmi_query_rays, ptmi_trace_paths, ptmi_render_guides) - a
 // device buffer, and a pinned landing buffer of `cap` bytes, allocated only once a result's destination is not page-locked.
 // reserve() frees and regrows both when `landing_bytes` exceeds the capacity; ptmi_release frees them.
 struct RoundTrip {
@@ -126,9 +126,10 @@ struct ptmi_ctx : ptmi_internal::ContextScene {
     float* h_staging = nullptr;  // pinned, 5*W*H floats
     struct HostRange { char* p; size_t bytes; };
     std::vector<HostRange> pinned_host;  // caller buffers page-locked by ptmi_pin_host_buffer: readbacks DMA straight into them
-    // ptmi_query_rays: rays, and `cap` bytes of hits behind them, on the device; the hits land.  ptmi_render_guides: the planes
-    // of one call behind one another, in the same layout on the device and where they land
-    ptmi_internal::RoundTrip query_buffers, guide_buffers;
+    // ptmi_query_rays: rays, and `cap` bytes of hits behind them, on the device; the hits land.  ptmi_trace_paths: the same with
+    // sums for hits.  ptmi_render_guides: the planes of one call behind one another, in the same layout on the device and where
+    // they land
+    ptmi_internal::RoundTrip query_buffers, path_buffers, guide_buffers;
     // ptmi_denoise / ptmi_denoise_device (ptmi_denoise.cpp), on devices[0], allocated by the first call that needs them: the
     // feature planes between the filter's passes, 56 bytes per pixel, for either form; for the host form a round trip of 68 more
     // (the result, which lands, then the guide planes it renders); and the event that orders the host form of a multi-device

@@ -28,7 +28,7 @@ inline int launch_status(hipError_t e, const char* kernel, std::string* err)
 }
 
 // The grid of a kernel whose 256-lane workgroups keep one LDS traversal stack each and take their work in a grid-stride loop
-// (ray_query.hip, guide_buffers.hip): as many workgroups as the device holds at once - 8 of four waves by wave slots, fewer
+// (ray_query.hip, guide_buffers.hip, path_query.hip): as many workgroups as the device holds at once - 8 of four waves by wave slots, fewer
 // where 160 KB of LDS hold fewer stacks - four times over (rays differ in cost), and never more than `wanted`; the loop takes
 // the rest.  `stack_levels`: the depth of the uploaded tree; *lds_bytes = the dynamic LDS of a workgroup, one word per level
 // and lane.  `cap_env`: the environment switch of the tests that caps the grid, so that a small batch takes the loop too.
@@ -258,6 +258,16 @@ int launch_query_rays(const DScene& sc, bool any_hit, const void* d_rays, void* 
                       void* stream, std::string* err);
 int launch_query_rays_da(const DScene& sc, bool any_hit, const void* d_rays, void* d_hits, uint32_t n_rays, uint32_t stack_levels,
                          void* stream, std::string* err);
+
+// path_query.hip (compiled once per arithmetic mode): n_rays ptmi_ray records at d_rays -> as many ptmi_path_sum records at
+// d_sums, ray i traced as a full path for iterations [first_iteration, first_iteration + n_iterations) with the seed of index
+// first_index + i + it * index_stride.  stack_levels as for launch_query_rays.  Reads the scene's records only.
+int launch_trace_paths(const DScene& sc, const void* d_rays, void* d_sums, uint32_t n_rays, uint32_t first_iteration,
+                       uint32_t n_iterations, uint32_t first_index, uint32_t index_stride, uint32_t stack_levels, void* stream,
+                       std::string* err);
+int launch_trace_paths_da(const DScene& sc, const void* d_rays, void* d_sums, uint32_t n_rays, uint32_t first_iteration,
+                          uint32_t n_iterations, uint32_t first_index, uint32_t index_stride, uint32_t stack_levels, void* stream,
+                          std::string* err);
 
 // guide_buffers.hip (compiled once per arithmetic mode): the first-hit planes of ptmi_render_guides for iterations
 // [first_iteration, first_iteration + n_iterations), to DEVICE pointers; a plane that is NULL is not written.  stack_levels as

@@ -1,6 +1,7 @@
 // ptmi_literal_path.hpp - one path of the reference, its loops as they are written (Kernel_Main, FullKernel.cl:1180-1331):
-// the body of the one-path-per-lane kernel (kernels.hip), and what the wavefront kernel's launches fall back on for the rare
-// path whose closest-hit query accepts a NaN distance (kernel_wavefront.hip: redo_poisoned_kernel).
+// the body of the one-path-per-lane kernel (kernels.hip), what the wavefront kernel's launches fall back on for the rare
+// path whose closest-hit query accepts a NaN distance (kernel_wavefront.hip: redo_poisoned_kernel), and - from the bounce loop
+// on - the path of a ray the caller supplies (path_query.hip).
 #pragma once
 
 #include "ptmi_device.hpp"
@@ -149,14 +150,6 @@ __device__ __forceinline__ bool query(const DScene& sc, const Ray& r, float& lim
     if (MAY_ORDER && sc.boxes_ordered && ray_slabs_are_ordered(r) && !(limit < 0)) return walk<ANY_HIT, PRE, true>(sc, r, limit, hit, pc, stack);
     return walk<ANY_HIT, PRE, false>(sc, r, limit, hit, pc, stack);
 }
-// One query of a path: `query` with the ordered form switched off - which is what makes these loops the fallback for
-// everything the fast forms cannot express.
-template <bool ANY_HIT, bool PRE>
-__device__ __forceinline__ bool traverse(const DScene& sc, const Ray& r, float limit, Hit& hit, PathCounters& pc,
-                                         uint32_t* __restrict__ stack)
-{
-    return query<ANY_HIT, PRE, false>(sc, r, limit, hit, pc, stack);
-}
 
 // The camera ray of sample (gx, gy, iteration) as Kernel_Main makes it (FullKernel.cl:1208-1215); `seed` is left where the
 // path goes on.  (kernel_wavefront.hip, "start the next camera path", keeps a copy that reads the cold scene record.)
@@ -171,20 +164,15 @@ __device__ __forceinline__ Ray primary_ray(const DScene& sc, uint32_t gx, uint32
     return r;
 }
 
-// One path = one Kernel_Main work-item (FullKernel.cl:1180-1331) up to the
-// statistics; returns the radiance and the sample position.
-// `stop_criterion_draw`: SUPER_SAMPLING draws one random number for its stop criterion before the path starts (cl:1219-1222,
-// from iteration 6 on); a caller that re-traces a path of such a render passes true so that the path's numbers are the same.
-template <bool PRE>
-__device__ __forceinline__ V4 trace_path(const DScene& sc, uint32_t gx, uint32_t gy, uint32_t iteration,
-                                         uint32_t* __restrict__ stack, float& sample_x, float& sample_y,
-                                         uint32_t& depth, uint32_t& segments, uint32_t& shadows, PathCounters& pc,
-                                         bool stop_criterion_draw = false)
+// The bounce loop of Kernel_Main (FullKernel.cl:1224-1317) from a ray that has been made and a seed that stands where the path
+// goes on: the ONE definition for the render kernel, the wavefront kernel's retraces (both through trace_path) and the paths of
+// a caller's own rays (path_query.hip).  Returns the radiance; `depth` = the surface hits, `segments` and `shadows` are added to.
+// MAY_ORDER: the queries may take the 5-comparison box test where it applies (`query`); false, the ordered form switched off,
+// is what makes these loops the fallback for everything the fast forms cannot express.
+template <bool PRE, bool MAY_ORDER = false>
+__device__ __forceinline__ V4 trace_path_from(const DScene& sc, Ray r, int seed, uint32_t* __restrict__ stack, uint32_t& depth,
+                                              uint32_t& segments, uint32_t& shadows, PathCounters& pc)
 {
-    int seed;
-    Ray r = primary_ray(sc, gx, gy, iteration, seed, sample_x, sample_y);
-    if (stop_criterion_draw) (void)lcg_random(seed);
-
     V4 radiance = v4(0, 0, 0, 0), transfer = v4(1, 1, 1, 1);
     bool active = true, in_water = false;
     uint32_t reflection = 0;
@@ -194,7 +182,8 @@ __device__ __forceinline__ V4 trace_path(const DScene& sc, uint32_t gx, uint32_t
     while (active && reflection < sc.max_depth) {
         Hit hit = no_hit();
         segments++;
-        if (traverse<false, PRE>(sc, r, INFINITY, hit, pc, stack)) {
+        float unlimited = INFINITY;
+        if (query<false, PRE, MAY_ORDER>(sc, r, unlimited, hit, pc, stack)) {
             Surface sf;
             load_surface(sc, r, hit, sf);
 
@@ -207,11 +196,11 @@ __device__ __forceinline__ V4 trace_path(const DScene& sc, uint32_t gx, uint32_t
                 Ray lr;
                 lr.o = hit.point;
                 ray_set_direction(lr, full);
-                const float light_distance = directional ? INFINITY : length(full);  // linear, :938
+                float light_distance = directional ? INFINITY : length(full);  // linear, :938
                 const float brdf = material_brdf(sf.mat.type, -lr.d, sf.Ns, r.d);
                 Hit dummy;
                 shadows++;
-                if (!traverse<true, PRE>(sc, lr, light_distance, dummy, pc, stack))
+                if (!query<true, PRE, MAY_ORDER>(sc, lr, light_distance, dummy, pc, stack))
                     direct = mad(v4(1, 1, 1, 1) * (light_power_toward(light, hit.point, sf.Ns) * brdf), v4(light.color), direct);  // cl:945
             }
 
@@ -225,6 +214,22 @@ __device__ __forceinline__ V4 trace_path(const DScene& sc, uint32_t gx, uint32_t
     }
     depth = reflection;
     return radiance;
+}
+
+// One path = one Kernel_Main work-item (FullKernel.cl:1180-1331) up to the
+// statistics; returns the radiance and the sample position.
+// `stop_criterion_draw`: SUPER_SAMPLING draws one random number for its stop criterion before the path starts (cl:1219-1222,
+// from iteration 6 on); a caller that re-traces a path of such a render passes true so that the path's numbers are the same.
+template <bool PRE>
+__device__ __forceinline__ V4 trace_path(const DScene& sc, uint32_t gx, uint32_t gy, uint32_t iteration,
+                                         uint32_t* __restrict__ stack, float& sample_x, float& sample_y,
+                                         uint32_t& depth, uint32_t& segments, uint32_t& shadows, PathCounters& pc,
+                                         bool stop_criterion_draw = false)
+{
+    int seed;
+    const Ray r = primary_ray(sc, gx, gy, iteration, seed, sample_x, sample_y);
+    if (stop_criterion_draw) (void)lcg_random(seed);
+    return trace_path_from<PRE>(sc, r, seed, stack, depth, segments, shadows, pc);
 }
 
 }  // namespace PTMI_DEV_NS

@@ -82,6 +82,14 @@ RAY_HIT = np.dtype({
 })
 RAY_MISS = 0xFFFFFFFF  # RAY_HIT.triangle_id of a ray that hit nothing
 
+# include/ptmi.h: ptmi_path_sum, what Backend.trace_paths gets per ray
+PATH_SUM = np.dtype({
+    "names": ["radiance", "segments", "surface_hits", "shadow_rays", "reserved", "box_tests", "triangle_tests"],
+    "formats": [FLOAT4, np.uint32, np.uint32, np.uint32, np.uint32, np.uint64, np.uint64],
+    "offsets": [0, 16, 20, 24, 28, 32, 40],
+    "itemsize": 48,
+})
+
 # enums (PathTracer_Structs.h:24-30, 43-51, 66-71, 130-135)
 LIGHT_DIRECTIONNAL, LIGHT_POINT, LIGHT_SPOT, LIGHT_UNKNOWN = 0, 1, 2, 3
 MAT_STANDART, MAT_WATER, MAT_GLASS, MAT_VARNHISHED, MAT_METAL, MAT_UNKNOWN = 0, 1, 2, 3, 4, 5
@@ -95,4 +103,4 @@ MAX_LIGHT_SIZE = 30             # PathTracer_PreProc.h:20
 
 assert BoundingBox.itemsize == 64 and Light.itemsize == 64 and Material.itemsize == 48
 assert Node.itemsize == 160 and Texture.itemsize == 12 and Triangle.itemsize == 336 and Sky.itemsize == 92
-assert RAY.itemsize == 48 and RAY_HIT.itemsize == 48
+assert RAY.itemsize == 48 and RAY_HIT.itemsize == 48 and PATH_SUM.itemsize == 48

@@ -1,0 +1,161 @@
+"""ptmi_trace_paths without a GPU: the new ABI (symbols, struct layouts) held against the header, the yardstick of the GPU tests
+(path_query_cases.py) held against the oracle's own render of the built-in camera, and the conditions on the ray sets that make
+a pass of test_path_query_gpu.py mean something."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from opencl_pathtracer_amd import backend, structs as S
+import oracle_ffi as O
+import path_query_cases as P
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+# ---------------------------------------------------------------------------------------------- ABI and layout
+
+def test_library_exports_the_path_entry_points(built):
+    """Both calls exist and refuse a NULL context with PTMI_ERR_INVALID_ARGUMENT, before they look at anything else."""
+    out = subprocess.run(["nm", "-D", "--defined-only", backend.library_path()], capture_output=True, text=True, check=True).stdout
+    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
+    assert {"ptmi_trace_paths", "ptmi_trace_paths_device"} <= exported
+    assert {"ptmi_trace_paths", "ptmi_trace_paths_device"} <= set(backend.ABI_SYMBOLS)
+    lib = backend.load_library()
+    assert lib.ptmi_abi_version() == 4
+    p = backend.PathParams(C.sizeof(backend.PathParams), 0, 1, 0, 1)
+    assert lib.ptmi_trace_paths(None, C.byref(p), None, 0, None) == -1
+    assert lib.ptmi_trace_paths_device(None, C.byref(p), None, 0, None) == -1
+    assert lib.ptmi_trace_paths(None, None, None, 0, None) == -1
+
+
+LAYOUT_PROGRAM = r"""
+#include <stddef.h>
+#include <stdio.h>
+#include "ptmi.h"
+#define F(type, field) printf(#type "." #field " %zu\n", offsetof(type, field))
+int main(void)
+{
+    printf("ptmi_path_params %zu\n", sizeof(ptmi_path_params));
+    F(ptmi_path_params, struct_size); F(ptmi_path_params, first_iteration); F(ptmi_path_params, n_iterations);
+    F(ptmi_path_params, first_index); F(ptmi_path_params, index_stride); F(ptmi_path_params, reserved);
+    printf("ptmi_path_sum %zu\n", sizeof(ptmi_path_sum));
+    F(ptmi_path_sum, radiance); F(ptmi_path_sum, segments); F(ptmi_path_sum, surface_hits); F(ptmi_path_sum, shadow_rays);
+    F(ptmi_path_sum, reserved); F(ptmi_path_sum, box_tests); F(ptmi_path_sum, triangle_tests);
+    printf("cap %u\n", (unsigned)PTMI_MAX_PATH_ITERATIONS);
+    return 0;
+}
+"""
+
+
+def test_numpy_dtype_and_ctypes_struct_match_the_header(tmp_path):
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text(LAYOUT_PROGRAM)
+    subprocess.run(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    out = {k: int(v) for k, v in (line.rsplit(" ", 1) for line in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines())}
+    assert out.pop("cap") == 4096 == backend.MAX_PATH_ITERATIONS
+    want = {"ptmi_path_params": 32, "ptmi_path_sum": 48}
+    for field, _ in backend.PathParams._fields_:
+        want[f"ptmi_path_params.{field}"] = getattr(backend.PathParams, field).offset
+    for field in S.PATH_SUM.names:
+        want[f"ptmi_path_sum.{field}"] = S.PATH_SUM.fields[field][1]
+    assert out == want
+    assert C.sizeof(backend.PathParams) == 32 and S.PATH_SUM.itemsize == 48
+    assert [out[f"ptmi_path_sum.{f}"] for f in S.PATH_SUM.names] == [0, 16, 20, 24, 28, 32, 40]
+    assert [out[f"ptmi_path_params.{f}"] for f, _ in backend.PathParams._fields_] == [0, 4, 8, 12, 16, 20]
+
+
+# ---------------------------------------------------------------------------------------------- the yardstick against the image
+
+@pytest.mark.parametrize("default_arithmetic", [False, True], ids=["strict", "default"])
+@pytest.mark.parametrize("sampler", [S.JITTERED, S.UNIFORM], ids=["jittered", "uniform"])
+@pytest.mark.parametrize("name", ["cornell", "matmix"])
+def test_yardstick_reproduces_the_render_of_the_camera(scene_factory, name, sampler, default_arithmetic):
+    """The camera's own rays at 16 x 12 through the zero-basis construction, first_index = 0 and index_stride = W * H: the image
+    of oracle_render's one iteration word for word, and its totals - for iteration 0 and for a later one."""
+    w, h, depth = 16, 12, 4
+    sc = scene_factory(name, w, h)
+    y = P.Yardstick(sc, depth, sampler, default_arithmetic)
+    for it in (0, 7):
+        color, count, _, totals = O.oracle_render(sc, w, h, depth, 1, first_iteration=it, sampler=sampler, default_arithmetic=default_arithmetic)
+        assert (count == 1).all()  # (with these samplers a sample lands on its work-item's pixel)
+        rays = P.camera_rays(sc, w, h, it, sampler, default_arithmetic)
+        sums = y.sums(rays, first_iteration=it, n_iterations=1, first_index=0, index_stride=w * h)
+        assert np.array_equal(sums["radiance"].view(np.uint32), color.reshape(-1, 4).view(np.uint32))
+        assert {n: int(sums[n].sum()) for n in P.COUNTS} == {n: totals[n] for n in P.COUNTS} and totals["paths"] == w * h
+        assert (sums["reserved"] == 0).all()
+
+
+def test_sums_add_in_iteration_order_and_share_paths(built):
+    """Three iterations are the float32 sum of the three single ones in order, and a ray's result does not depend on the batch
+    it travels in while its index stays (what lets the GPU tests share one batch between sizes)."""
+    sc = P.scene("cornell")
+    rays = P.batch("cornell", sc, P.N_CORNELL)[:48]
+    y = P.Yardstick(sc)
+    three = y.sums(rays, 0, 3, index_stride=P.STRIDE)
+    singles = [y.sums(rays, it, 1, index_stride=P.STRIDE) for it in range(3)]
+    acc = np.zeros((48, 4), np.float32)
+    for s in singles:
+        acc = acc + s["radiance"]
+    assert np.array_equal(acc.view(np.uint32), three["radiance"].view(np.uint32))
+    assert np.array_equal(three["box_tests"], sum(s["box_tests"] for s in singles))
+    assert not P.describe_difference(P.Yardstick(sc).sums(rays[:7], 0, 3, index_stride=P.STRIDE), three[:7])
+    moved = P.Yardstick(sc).sums(rays[8:16], 0, 3, first_index=8, index_stride=P.STRIDE)
+    assert not P.describe_difference(moved, three[8:16])
+    assert P.describe_difference(P.Yardstick(sc).sums(rays[8:16], 0, 3, index_stride=P.STRIDE), three[8:16])  # (other indices: other paths)
+
+
+# ---------------------------------------------------------------------------------------------- what the GPU tests' rays reach
+
+def _coverage(sc, rays, **kw):
+    y = P.Yardstick(sc, **kw)
+    with np.errstate(all="ignore"):
+        sums = y.sums(rays, 0, 1, index_stride=P.STRIDE)
+    return y, sums, float((sums["surface_hits"] >= 2).mean()), float((y.sky_ends > 0).mean())
+
+
+@pytest.mark.parametrize("default_arithmetic", [False, True], ids=["strict", "default"])
+@pytest.mark.parametrize("sampler", [S.JITTERED, S.RANDOM, S.UNIFORM], ids=["jittered", "random", "uniform"])
+def test_the_cornell_batches_reach_deep_paths_and_the_sky(built, sampler, default_arithmetic):
+    """Every batch size test_path_query_gpu.py sends (prefixes of one batch), under every sampler and arithmetic it runs: at least
+    half the rays have two or more surface hits in ONE iteration, at least 10 % end on the sky.  (Sizes 1 and below 20 cannot
+    hold both kinds; they are prefixes of the sizes that do.)"""
+    sc = P.scene("cornell")
+    rays = P.batch("cornell", sc, P.N_CORNELL)
+    assert (rays["direction"][:, :3] != 0).all()
+    y, sums, _, _ = _coverage(sc, rays, sampler=sampler, default_arithmetic=default_arithmetic)
+    for n in (63, 64, 65, 257, 1000):
+        assert (sums["surface_hits"][:n] >= 2).mean() >= 0.5 and (y.sky_ends[:n] > 0).mean() >= 0.1, n
+    assert sums["segments"].mean() > 3  # (paths, not single segments)
+
+
+@pytest.mark.parametrize("name", P.SCENES)
+def test_the_scene_batches_reach_deep_paths_and_the_sky(built, name):
+    """The same two conditions for the batch of every scene, in both arithmetics.  `one_triangle` is the one set that cannot
+    meet the first: a path that has hit the only triangle of a scene leaves it into the hemisphere it came from and meets
+    nothing again.  There at least a quarter of the rays must hit the triangle, once, which is all the geometry can give."""
+    sc = P.scene(name)
+    rays = P.batch(name, sc, P.N_SCENE)
+    assert (rays["direction"][:, :3] != 0).all()
+    for da in (False, True):
+        y, sums, deep, sky = _coverage(sc, rays, default_arithmetic=da)
+        assert sky >= 0.1, (name, sky)
+        if name == "one_triangle":
+            assert (sums["surface_hits"] == 1).mean() >= 0.25 and (sums["surface_hits"] <= 1).all()
+        else:
+            assert deep >= 0.5, (name, deep)
+        if name == "matmix":
+            assert len(sc.lights) == 3 and (sums["shadow_rays"] == 3 * sums["surface_hits"]).all()
+        if name == "hostile":  # the rays at the zero-area triangles walk far more of the tree than any other ray
+            assert sums["triangle_tests"][-32:].max() > 4 * np.median(sums["triangle_tests"][:-32])
+
+
+@pytest.mark.parametrize("name", ["feat_glass", "feat_water"])
+def test_the_glass_and_water_batches_refract(built, name):
+    sc = P.scene(name)
+    rays = P.batch(name, sc, P.N_SCENE)
+    y = P.Yardstick(sc)
+    refracted = sum(1 for i, r in enumerate(rays) if y.refractions(sc, r["origin"], r["direction"], i, 0, P.STRIDE) > 0)
+    assert refracted >= 10, refracted
