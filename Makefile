@@ -20,7 +20,8 @@ LIB_OBJS   := $(OBJDIR)/kernels.o $(OBJDIR)/kernel_wavefront.o $(OBJDIR)/kernels
               $(OBJDIR)/ray_query.o $(OBJDIR)/ray_query_da.o $(OBJDIR)/ptmi_guides.o \
               $(OBJDIR)/path_query.o $(OBJDIR)/path_query_da.o $(OBJDIR)/ptmi_paths.o \
               $(OBJDIR)/guide_buffers.o $(OBJDIR)/guide_buffers_da.o \
-              $(OBJDIR)/denoise.o $(OBJDIR)/ptmi_denoise.o
+              $(OBJDIR)/denoise.o $(OBJDIR)/ptmi_denoise.o \
+              $(OBJDIR)/reproject.o $(OBJDIR)/ptmi_reproject.o
 
 .PHONY: all lib shim oracle ref clean resources
 all: lib shim oracle
@@ -59,4 +60,4 @@ clean:
 # register / LDS budget of both kernels (occupancy is VGPR-bound: read this after every kernel edit)
 resources:
 	@for f in kernels kernel_wavefront ray_query guide_buffers path_query; do for m in 0 1; do $(HIPCC) $(HIPFLAGS) -DPTMI_DEFAULT_ARITHMETIC=$$m --cuda-device-only -c $(CSRC)/$$f.hip -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs:|ScratchSize|Occupancy|LDS Size|Spill" | sed 's/.*remark: *//' | tr '\n' ' '; echo; done; done
-	@for f in denoise; do $(HIPCC) $(HIPFLAGS) --cuda-device-only -c $(CSRC)/$$f.hip -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs:|ScratchSize|Occupancy|LDS Size|Spill" | sed 's/.*remark: *//' | tr '\n' ' '; echo; done
+	@for f in denoise reproject; do $(HIPCC) $(HIPFLAGS) --cuda-device-only -c $(CSRC)/$$f.hip -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs:|ScratchSize|Occupancy|LDS Size|Spill" | sed 's/.*remark: *//' | tr '\n' ' '; echo; done

@@ -265,7 +265,7 @@ void ptmi_release(ptmi_ctx* ctx);
  * device write: after any error the context renders the scene it held before the call.
  * NEITHER TOUCHES what has been rendered: accumulators, histograms, counters, snapshots, bound accumulators and the caller's
  * stream stay as they are.  A caller who wants a fresh image of the new scene calls ptmi_clear; a caller who does not
- * accumulates over the motion - motion blur.
+ * accumulates over the motion - motion blur.  ptmi_set_camera_reprojected (below) is the third way: it takes the image along.
  *
  * ptmi_set_camera: a new camera (kernel arguments 1..4 of the reference), everything else stays.  A camera that is not finite or
  * beyond 2^21 would change the kernel instantiation chosen at upload (ptmi_literal_kernel_reason): PTMI_ERR_UNSUPPORTED, call
@@ -502,6 +502,96 @@ int ptmi_denoise(ptmi_ctx* ctx, const ptmi_denoise_params* params, float* image_
  * ptmi_device_accumulators).  d_image_out (float4[W*H]) MUST NOT ALIAS AN INPUT; the library cannot check that. */
 int ptmi_denoise_device(ptmi_ctx* ctx, const ptmi_denoise_params* params, const ptmi_guides* device_guides,
                         const void* d_image_color, const void* d_image_ray_nb, void* d_image_out);
+
+/* ---- carrying the image across a camera move ------------------------------ */
+
+/* Temporal reprojection: the accumulated image of the PREVIOUS camera, resampled to where the same surfaces lie under the camera
+ * of NOW, so that a viewer that orbits neither smears the old views into the new one (accumulating on) nor starts from one noisy
+ * sample per pixel (ptmi_clear).  The position plane of the guides holds the world-space point a pixel sees; projecting it into
+ * the previous camera finds the previous pixels that saw that point, and the previous position and normal planes say whether
+ * they really saw the same surface.  A pure function of planes and one camera: the camera of NOW is not an argument, the
+ * current position plane already holds world-space points.
+ *
+ * THE ARITHMETIC, the same in both arithmetic modes of a context.  Every operation is one IEEE binary32 operation in the
+ * written order: no contraction, correctly rounded division, denormals kept, no transcendental.
+ * dot3(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z;  min(a, b) = a < b ? a : b;  prev.* = the previous planes (position, normal,
+ * hit_count of previous_guides; color, ray_nb), cur.* = current_guides.
+ *   on the host, in DOUBLE, each result rounded to float once:  cross(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z,
+ *       a.x*b.y - a.y*b.x);  with the previous camera's dir, right, up (xyz): c = cross(right, up), det = dot3(dir, c),
+ *       r0 = c / det, r1 = cross(up, dir) / det, r2 = cross(dir, right) / det - the rows that solve
+ *       v = t * (dir + sx*right + sy*up) for any camera, orthogonal or not (the camera expression is cl:1213).
+ *   on the host, in float:  tp = position_tolerance * position_tolerance, tn = normal_tolerance * normal_tolerance,
+ *       Wf = (float)W, Hf = (float)H.
+ *   pixel p = (x, y) of the new frame:
+ *     1. h = cur.hit_count[p]; no history unless h > 0.
+ *     2. P = cur.position[p].xyz / h, N = cur.normal[p].xyz / h, v = P - previous_camera[0].xyz.
+ *     3. t = dot3(r0, v), a = dot3(r1, v), b = dot3(r2, v); no history unless t > 0.
+ *     4. u = (a / t + 0.5f) * Wf - 0.5f, w_ = (b / t + 0.5f) * Hf - 0.5f (the centre of previous pixel gx is u = gx); no history
+ *        unless u > -1 && u < Wf && w_ > -1 && w_ < Hf (a NaN fails).
+ *     5. x0 = floorf(u), fx = u - x0, y0 = floorf(w_), fy = w_ - y0, lim = tp * dot3(v, v).
+ *     6. the taps (x0,y0), (x0+1,y0), (x0,y0+1), (x0+1,y0+1), in this order, with weights w = (1-fx)*(1-fy), fx*(1-fy),
+ *        (1-fx)*fy, fx*fy.  A tap q is taken only when it lies inside the image, w > 0, hq = prev.hit_count[q] > 0,
+ *        nq = prev.ray_nb[q] > 0, dot3(Pq - P, Pq - P) <= lim with Pq = prev.position[q].xyz / hq,
+ *        dot3(Nq - N, Nq - N) <= tn with Nq = prev.normal[q].xyz / hq, and all four channels of mq = prev.color[q] / nq are
+ *        finite (mq_c - mq_c == 0).
+ *     7. a taken tap adds sw = sw + w, sm_c = sm_c + w * mq_c (all four channels), sn = sn + w * nq.
+ *     8. history exists when sw > 0 and n = floorf(min(sn / sw, max_history)) >= 1:
+ *        out_color[p]_c = (sm_c / sw) * n, out_ray_nb[p] = n; otherwise four +0 and a count of +0.
+ * WHAT FOLLOWS.  All four channels of the radiance are treated alike, as everywhere here.  Counts stay integral floats.  A MISS
+ * pixel (the sky) carries no history: it has no world point, and it converges in a few samples.  A pixel without history comes
+ * out exactly as ptmi_clear leaves it.  A bad previous pixel (a NaN or infinite channel, a count that is zero, negative or NaN)
+ * never reaches the output, so with finite counts no word of the output is a NaN.  position_tolerance is RELATIVE, a fraction of
+ * the point's distance from the previous camera (neighbouring pixels lie further apart the further away they are);
+ * normal_tolerance is a distance between mean shading normals, as the denoiser's sigma_normal.  (A position_tolerance of 0.64,
+ * the Python binding's measured default, lets every tap of an ordinary scene pass: the position test is then off.)  Geometry that
+ * ptmi_update_triangles has moved is tested at its new position: it mostly fails the position test and restarts (per-object
+ * motion vectors are not kept).
+ *
+ * PTMI_ERR_STATE before ptmi_initialize_memory; PTMI_ERR_INVALID_ARGUMENT for a NULL or wrongly sized struct (the params or
+ * either ptmi_guides), a non-zero flags or reserved, a tolerance that is not finite and > 0, max_history that is NaN or < 1,
+ * guide_iterations of 0 or >= 2^24 (host form), a missing plane, a pointer that is not 16-byte aligned, a previous camera whose
+ * position, direction, right or up (xyz) is not finite or whose det is 0 or not finite.  After any error the context renders,
+ * and holds, what it did before. */
+typedef struct ptmi_reproject_params {   /* 32 bytes */
+    uint32_t struct_size;            /* = sizeof(ptmi_reproject_params) */
+    uint32_t flags;                  /* 0: none defined yet */
+    uint32_t guide_first_iteration;  /* ptmi_set_camera_reprojected only */
+    uint32_t guide_iterations;       /* ptmi_set_camera_reprojected only: >= 1, < 2^24 */
+    float position_tolerance;        /* finite, > 0: RELATIVE - a fraction of the point's distance from the previous camera */
+    float normal_tolerance;          /* finite, > 0: a distance between mean shading normals, as the denoiser's sigma_normal */
+    float max_history;               /* >= 1, +INFINITY allowed, not NaN: cap of the sample count a pixel carries over */
+    uint32_t reserved;               /* 0 */
+} ptmi_reproject_params;
+
+/* Device form: every pointer is a device address, 16-byte aligned; asynchronous on the context's main stream (ptmi_set_stream's,
+ * where one was given), ordered like ptmi_denoise_device: the calls that rewrite scene records wait for it.  It TOUCHES NOTHING
+ * THAT HAS BEEN RENDERED (the list of the guide and denoise calls) and needs no scratch at all.  previous_camera = position,
+ * direction, right, up the previous planes were made with; previous_guides and current_guides carry normal, position and
+ * hit_count (albedo and ids are ignored), summed over any number of iterations; d_previous_color / d_previous_ray_nb are the
+ * float4[W*H] sums and float[W*H] counts of the previous image; d_out_color (float4[W*H]) and d_out_ray_nb (float[W*H]) MUST NOT
+ * ALIAS AN INPUT; the library cannot check that. */
+int ptmi_reproject_device(ptmi_ctx* ctx, const ptmi_reproject_params* params, const ptmi_float4 previous_camera[4],
+                          const ptmi_guides* previous_guides, const void* d_previous_color, const void* d_previous_ray_nb,
+                          const ptmi_guides* current_guides, void* d_out_color, void* d_out_ray_nb);
+
+/* Host form: ptmi_set_camera that takes the image along.  In this order, what a caller could do with the calls above:
+ *   1. guides (position, normal, hit count) for [guide_first_iteration, + guide_iterations) under the camera the context holds;
+ *   2. the image ptmi_read_image would return (on a multi-device context the shares are summed, as for ptmi_denoise);
+ *   3. everything ptmi_set_camera does (synchronise, drop launches rendered ahead, every device);
+ *   4. the same guides under the new camera;
+ *   5. the reprojection above, with the camera of step 1 as the previous one;
+ *   6. the result stored as ptmi_write_image would: devices[0] gets it, every other device restarts from zero - copied on the
+ *      device, nothing crosses the bus.
+ * Afterwards the context is in the state "ptmi_set_camera + ptmi_write_image(reprojected)": histograms, ptmi_counters,
+ * scheduler statistics and the caller's snapshot slots are unchanged, bound accumulators (ptmi_bind_accumulators) are written in
+ * place.  Scratch on devices[0], allocated by the first call and freed by ptmi_release: 92 bytes per pixel - two sets of the
+ * three guide planes at 36 bytes each, and the result at 20 (plus at most 45 bytes: every plane starts 16-byte aligned).  Every
+ * check and every allocation happens before the first write to the camera or the accumulators.
+ * PTMI_ERR_UNSUPPORTED for everything ptmi_set_camera refuses; on a context with the RANDOM sampler (no guides, as
+ * ptmi_denoise); and on a context with super_sampling, whose variance accumulator and per-pixel stop decisions cannot be
+ * carried over. */
+int ptmi_set_camera_reprojected(ptmi_ctx* ctx, const ptmi_float4* position, const ptmi_float4* direction, const ptmi_float4* right,
+                                const ptmi_float4* up, const ptmi_reproject_params* params);
 
 /* ---- measurement / plumbing -------------------------------------------- */
 

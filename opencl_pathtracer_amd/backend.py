@@ -103,6 +103,13 @@ class DenoiseParams(C.Structure):
                 ("sigma_position", C.c_float), ("reserved", C.c_uint32 * 2)]
 
 
+class ReprojectParams(C.Structure):
+    """ptmi_reproject_params: the tests of ptmi_reproject_device / ptmi_set_camera_reprojected (ptmi.h states its arithmetic)."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("guide_first_iteration", C.c_uint32),
+                ("guide_iterations", C.c_uint32), ("position_tolerance", C.c_float), ("normal_tolerance", C.c_float),
+                ("max_history", C.c_float), ("reserved", C.c_uint32)]
+
+
 class PathParams(C.Structure):
     """ptmi_path_params: which iterations ptmi_trace_paths traces for every ray, and the index its seeds come from."""
     _fields_ = [("struct_size", C.c_uint32), ("first_iteration", C.c_uint32), ("n_iterations", C.c_uint32),
@@ -116,6 +123,14 @@ DENOISE_DEMODULATE_ALBEDO, DENOISE_UNTILED = 1, 2  # ptmi.h: PTMI_DENOISE_*
 # profiles/denoise_quality_cornell.json (tests/test_denoise_gpu.py holds them to it).  sigma_position is in scene units.
 # That box is 555 units wide: scale sigma_position with the scene (about 3 % of its extent).
 DENOISE_DEFAULTS = dict(passes=5, sigma_color=8.0, sigma_normal=1.0, sigma_position=16.0)
+
+# The shipped defaults of the reprojection: the RMSE minimum against 1024 further iterations after a small orbit of the Cornell
+# camera, 16 iterations before the move and 4 after it, over the grid of profiles/reproject_quality_cornell.json
+# (tests/test_reproject_gpu.py holds them to it).  position_tolerance is relative to the distance from the previous camera.
+# From 0.64 on the position test rejects nothing in that box (RMSE is flat from 0.08 on), so THIS DEFAULT IN EFFECT SWITCHES THE
+# POSITION TEST OFF and the normal test and the image's frame do the work: tighten it to a few pixel spacings
+# (a pixel is 1 / W of the distance wide) where parallel surfaces lie at different depths.
+REPROJECT_DEFAULTS = dict(position_tolerance=0.64, normal_tolerance=1.0, max_history=16.0)
 
 
 BVH_FALLBACK_NONE, BVH_FALLBACK_STALE_AXIS, BVH_FALLBACK_HOST_ERROR, BVH_FALLBACK_RECORDS = 0, 1, 2, 3
@@ -157,7 +172,8 @@ ABI_SYMBOLS = ["ptmi_setup_context", "ptmi_initialize_memory", "ptmi_render", "p
                "ptmi_abi_version", "ptmi_device_count", "ptmi_device_share", "ptmi_bvh_create",
                "ptmi_bvh_create_device", "ptmi_set_camera", "ptmi_update_triangles", "ptmi_bvh_refit",
                "ptmi_query_rays", "ptmi_query_rays_device", "ptmi_render_guides", "ptmi_render_guides_device",
-               "ptmi_denoise", "ptmi_denoise_device", "ptmi_trace_paths", "ptmi_trace_paths_device"]
+               "ptmi_denoise", "ptmi_denoise_device", "ptmi_trace_paths", "ptmi_trace_paths_device",
+               "ptmi_reproject_device", "ptmi_set_camera_reprojected"]
 
 QUERY_CLOSEST, QUERY_ANY = 0, 1  # ptmi.h: PTMI_QUERY_*
 
@@ -220,6 +236,9 @@ def load_library():
     lib.ptmi_render_guides_device.argtypes = [vp, u32, u32, C.POINTER(Guides)]
     lib.ptmi_denoise.argtypes = [vp, C.POINTER(DenoiseParams), vp]
     lib.ptmi_denoise_device.argtypes = [vp, C.POINTER(DenoiseParams), C.POINTER(Guides), vp, vp, vp]
+    lib.ptmi_reproject_device.argtypes = [vp, C.POINTER(ReprojectParams), C.POINTER(Float4 * 4), C.POINTER(Guides), vp, vp, C.POINTER(Guides), vp, vp]
+    lib.ptmi_set_camera_reprojected.argtypes = [vp, C.POINTER(Float4), C.POINTER(Float4), C.POINTER(Float4), C.POINTER(Float4),
+                                                C.POINTER(ReprojectParams)]
     lib.ptmi_device_share.argtypes = [u32, u32, u32, u32, C.POINTER(u32), C.POINTER(u32)]
     lib.ptmi_device_share.restype = None
     _lib = lib
@@ -514,6 +533,43 @@ class Backend:
         p = self.denoise_params(**params)
         self._check(self._lib.ptmi_denoise_device(self._ctx, C.byref(p), C.byref(g), C.c_void_p(image_color), C.c_void_p(image_ray_nb),
                                                   C.c_void_p(out)))
+
+    # -- the image carried across a camera move (no counterpart in the reference) ---------------
+    @staticmethod
+    def reproject_params(position_tolerance=None, normal_tolerance=None, max_history=None, guide_first_iteration=0, guide_iterations=1):
+        """A ``ReprojectParams``; what is None takes its value from ``REPROJECT_DEFAULTS``."""
+        given = dict(position_tolerance=position_tolerance, normal_tolerance=normal_tolerance, max_history=max_history)
+        v = {k: REPROJECT_DEFAULTS[k] if x is None else x for k, x in given.items()}
+        return ReprojectParams(C.sizeof(ReprojectParams), 0, guide_first_iteration, guide_iterations, v["position_tolerance"],
+                               v["normal_tolerance"], v["max_history"], 0)
+
+    def set_camera_reprojected(self, position, direction, right, up, **params):
+        """``set_camera`` that takes the image along: every pixel whose surface the previous camera saw too keeps its mean and
+        (up to ``max_history``) its sample count, every other pixel restarts as after ``clear()``.  Keywords as for
+        ``reproject_params``: the guides of both cameras are rendered for [guide_first_iteration, + guide_iterations)."""
+        v = [_f4(x) for x in (position, direction, right, up)]
+        p = self.reproject_params(**params)
+        self._check(self._lib.ptmi_set_camera_reprojected(self._ctx, *[C.byref(x) for x in v], C.byref(p)))
+
+    def reproject_device(self, out_color, out_ray_nb, previous_camera, previous_guides, previous_color, previous_ray_nb, current_guides,
+                         **params):
+        """The reprojection alone, between device addresses (e.g. ``tensor.data_ptr()``), 16-byte aligned: ``previous_camera`` =
+        (position, direction, right, up) the previous planes were made with; both guides are dicts with the ``normal``,
+        ``position`` and ``hit_count`` planes of ``render_guides_device``; the previous image's sums float4[W*H] and counts
+        float[W*H]; the result's likewise.  Asynchronous on the context's stream; the result must not alias an input."""
+        cam = (Float4 * 4)(*[_f4(x) for x in previous_camera])
+        structs = []
+        for guides in (previous_guides, current_guides):
+            g = Guides(C.sizeof(Guides), 0)
+            for name, address in guides.items():
+                if name not in GUIDE_PLANES:
+                    raise PtmiError(-1, f"unknown guide plane {name!r}: one of {GUIDE_PLANES}")
+                setattr(g, name, address)
+            structs.append(g)
+        p = self.reproject_params(**params)
+        self._check(self._lib.ptmi_reproject_device(self._ctx, C.byref(p), C.byref(cam), C.byref(structs[0]), C.c_void_p(previous_color),
+                                                    C.c_void_p(previous_ray_nb), C.byref(structs[1]), C.c_void_p(out_color),
+                                                    C.c_void_p(out_ray_nb)))
 
     # -- one launch of the loop body of OpenCL_RunKernel, generalised to a range ----------
     def render(self, first_iteration, n_iterations):

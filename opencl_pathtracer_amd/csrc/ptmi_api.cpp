@@ -296,6 +296,8 @@ void ptmi_release(ptmi_ctx* ctx)
     ctx->denoise_buffers.release();
     if (ctx->d_denoise_features) (void)hipFree(ctx->d_denoise_features);
     if (ctx->denoise_ordered) (void)hipEventDestroy(ctx->denoise_ordered);
+    if (ctx->d_reproject_scratch) (void)hipFree(ctx->d_reproject_scratch);
+    if (ctx->reproject_gathered) (void)hipEventDestroy(ctx->reproject_gathered);
     destroy_rccl_communicators(ctx);
     for (auto& r : ctx->pinned_host) (void)hipHostUnregister(r.p);
     (void)hipGetLastError();

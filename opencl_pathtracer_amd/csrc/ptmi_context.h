@@ -1,5 +1,5 @@
 // ptmi_context.h - the state behind a ptmi_ctx, grouped by WHEN IT DIES, and what the host units of libptmi.so share
-// (ptmi_api.cpp, ptmi_scene_memory.cpp, ptmi_render.cpp, ptmi_readback.cpp, ptmi_query.cpp, ptmi_paths.cpp, ptmi_guides.cpp, ptmi_denoise.cpp).  Private: not ABI, never installed.
+// (ptmi_api.cpp, ptmi_scene_memory.cpp, ptmi_render.cpp, ptmi_readback.cpp, ptmi_query.cpp, ptmi_paths.cpp, ptmi_guides.cpp, ptmi_denoise.cpp, ptmi_reproject.cpp).  Private: not ABI, never installed.
 //
 // Two lifetimes.  PER SCENE (DeviceScene, ContextScene): free_scene_memory() frees what the struct owns and assigns a
 // value-initialised one, so a new per-scene field needs no line anywhere else.  PER CONTEXT (the members DeviceState and ptmi_ctx
@@ -137,6 +137,12 @@ struct ptmi_ctx : ptmi_internal::ContextScene {
     char* d_denoise_features = nullptr;
     ptmi_internal::RoundTrip denoise_buffers;
     hipEvent_t denoise_ordered = nullptr;
+    // ptmi_set_camera_reprojected (ptmi_reproject.cpp), on devices[0], allocated by the first call: 92 bytes per pixel - the
+    // normal and position planes of the previous and of the new camera and the result's sums (float4 each: 80), then the two hit
+    // counts and the result's counts (12), every plane starting 16-byte aligned; and the event behind a multi-device context's
+    // gathered image, which the main stream waits for
+    char* d_reproject_scratch = nullptr;
+    hipEvent_t reproject_gathered = nullptr;
 
     ptmi_internal::ContextScene& scene() { return *this; }
     uint32_t n_dev() const { return (uint32_t)dev.size(); }
@@ -257,6 +263,11 @@ int land(ptmi_ctx* ctx, const Landing (&items)[N], hipStream_t stream, char* lan
 bool one_path_per_lane(const ptmi_ctx* ctx);
 void free_scene_memory(ptmi_ctx* ctx);
 int quiesce(ptmi_ctx* ctx, DeviceState& d);
+// ptmi_set_camera in its two halves (ptmi_set_camera_reprojected does its own work between them): what can refuse - a missing
+// context, vector or scene, a camera that would change the kernel instantiation - and the write on every device, behind quiesce()
+int camera_check(ptmi_ctx* ctx, const char* who, const ptmi_float4* position, const ptmi_float4* direction, const ptmi_float4* right,
+                 const ptmi_float4* up);
+int camera_write(ptmi_ctx* ctx, const ptmi_float4& position, const ptmi_float4& direction, const ptmi_float4& right, const ptmi_float4& up);
 // ptmi_render.cpp
 int fold_events(ptmi_ctx* ctx, DeviceState& d);
 // ptmi_readback.cpp

@@ -303,6 +303,20 @@ struct DenoiseJob {
 };
 int launch_denoise(const DenoiseJob& job, void* stream, std::string* err);
 
+// reproject.hip (compiled once: one arithmetic for both modes): ptmi_reproject_device on DEVICE pointers, one kernel on
+// `stream`, no scratch.  The previous camera arrives as the contract's host-side values: its position, the three rows the host
+// computes in double and rounds once, and the squared tolerances.
+struct ReprojectJob {
+    const float *prev_normal, *prev_position, *prev_hit_count;  // float4[W*H], float4[W*H], float[W*H]
+    const float *prev_color, *prev_ray_nb;                      // float4[W*H] sums, float[W*H] counts
+    const float *cur_normal, *cur_position, *cur_hit_count;
+    float *out_color, *out_ray_nb;                              // float4[W*H], float[W*H]
+    uint32_t width, height;
+    float cam[3], r0[3], r1[3], r2[3];
+    float tp, tn, max_history;
+};
+int launch_reproject(const ReprojectJob& job, void* stream, std::string* err);
+
 // display.hip: out[i] = ((parts[0][i] + parts[1][i]) + parts[2][i]) + ...  in this fixed order (the accumulators of the devices
 // that shared a render, summed on the first one: ptmi_read_image / ptmi_read_snapshot); n_parts <= PTMI_MAX_DEVICES
 int launch_sum_images(float* out, const float* const* parts, uint32_t n_parts, size_t n_floats, void* stream, std::string* err);

@@ -197,6 +197,35 @@ int upload_scene(ptmi_ctx* ctx, DeviceState& d, const Relayout& lay, const ptmi_
 
 }  // namespace
 
+int ptmi_internal::camera_check(ptmi_ctx* ctx, const char* who, const ptmi_float4* position, const ptmi_float4* direction,
+                                const ptmi_float4* right, const ptmi_float4* up)
+{
+    if (!ctx) return PTMI_ERR_INVALID_ARGUMENT;
+    if (!position || !direction || !right || !up) return fail(ctx, PTMI_ERR_INVALID_ARGUMENT, std::string(who) + ": a camera vector is NULL");
+    if (int rc = need_scene(ctx, who)) return rc;
+    const std::string why = camera_needs_literal_kernel(*position, *direction, *right, *up);
+    if (!why.empty())
+        return fail(ctx, PTMI_ERR_UNSUPPORTED, std::string(who) + ": " + why + ": the kernel instantiation was chosen at upload, call "
+                                               "ptmi_initialize_memory with the new camera");
+    return PTMI_OK;
+}
+
+int ptmi_internal::camera_write(ptmi_ctx* ctx, const ptmi_float4& position, const ptmi_float4& direction, const ptmi_float4& right,
+                                const ptmi_float4& up)
+{
+    for (DeviceState& d : ctx->dev)
+        if (int rc = quiesce(ctx, d)) return rc;
+    for (DeviceState& d : ctx->dev) {
+        ON_DEVICE(ctx, d);
+        std::memcpy(d.ds.cam_pos, &position, 16);
+        std::memcpy(d.ds.cam_dir, &direction, 16);
+        std::memcpy(d.ds.cam_right, &right, 16);
+        std::memcpy(d.ds.cam_up, &up, 16);
+        if (int rc = upload_scene_records(ctx, d)) return rc;
+    }
+    return PTMI_OK;
+}
+
 extern "C" {
 
 int ptmi_initialize_memory(ptmi_ctx* ctx, const ptmi_scene* sc)
@@ -339,24 +368,8 @@ int ptmi_bind_accumulators(ptmi_ctx* ctx, void* d_color, void* d_count)
 
 int ptmi_set_camera(ptmi_ctx* ctx, const ptmi_float4* position, const ptmi_float4* direction, const ptmi_float4* right, const ptmi_float4* up)
 {
-    if (!ctx) return PTMI_ERR_INVALID_ARGUMENT;
-    if (!position || !direction || !right || !up) return fail(ctx, PTMI_ERR_INVALID_ARGUMENT, "ptmi_set_camera: a camera vector is NULL");
-    NEED_SCENE(ctx);
-    const std::string why = camera_needs_literal_kernel(*position, *direction, *right, *up);
-    if (!why.empty())
-        return fail(ctx, PTMI_ERR_UNSUPPORTED, "ptmi_set_camera: " + why + ": the kernel instantiation was chosen at upload, call "
-                                               "ptmi_initialize_memory with the new camera");
-    for (DeviceState& d : ctx->dev)
-        if (int rc = quiesce(ctx, d)) return rc;
-    for (DeviceState& d : ctx->dev) {
-        ON_DEVICE(ctx, d);
-        std::memcpy(d.ds.cam_pos, position, 16);
-        std::memcpy(d.ds.cam_dir, direction, 16);
-        std::memcpy(d.ds.cam_right, right, 16);
-        std::memcpy(d.ds.cam_up, up, 16);
-        if (int rc = upload_scene_records(ctx, d)) return rc;
-    }
-    return PTMI_OK;
+    if (int rc = camera_check(ctx, "ptmi_set_camera", position, direction, right, up)) return rc;
+    return camera_write(ctx, *position, *direction, *right, *up);
 }
 
 int ptmi_update_triangles(ptmi_ctx* ctx, const ptmi_triangle* triangulation, uint32_t triangulation_size, ptmi_update_info* info)

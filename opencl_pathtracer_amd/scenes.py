@@ -223,6 +223,20 @@ def camera(position, direction, right, up):
     return _f4(position, 1.0), _f4(direction, 0.0), _f4(right, 0.0), _f4(up, 0.0)
 
 
+def orbit_camera(cam, centre, degrees):
+    """The camera ``cam`` = (position, direction, right, up) turned by ``degrees`` about the axis through ``centre`` that is
+    parallel to its ``up``: what a viewer's orbit does.  Computed in float64 (Rodrigues) and rounded once."""
+    pos, direction, right, up = (np.asarray(v, np.float64) for v in cam)
+    centre = np.asarray(centre, np.float64)[:3]
+    axis = up[:3] / np.linalg.norm(up[:3])
+    c, s = np.cos(np.radians(degrees)), np.sin(np.radians(degrees))
+
+    def turn(v):
+        return v * c + np.cross(axis, v) * s + axis * np.dot(axis, v) * (1 - c)
+
+    return camera(turn(pos[:3] - centre) + centre, turn(direction[:3]), turn(right[:3]), turn(up[:3]))
+
+
 def camera_from_film(eye, view, up, right, focal_length_mm, aperture_x_inch, aperture_y_inch, maya_axes=False):
     """SetCam, MayaImporter.cpp:59-101: unit view / up / right directions and film data -> the four camera vectors the
     kernel takes.  Right and Up are scaled by aperture / focal length (apertures come in inches, the focal length in
