@@ -9,14 +9,9 @@ import numpy as np
 import pytest
 
 from opencl_pathtracer_amd import backend, structs as S
+from abi_cases import declared_symbols, exported_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "ptmi.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(ptmi_[a-z_]+)\s*\(", text)))
 
 
 def test_header_and_binding_list_agree():
@@ -27,9 +22,7 @@ def test_library_exports_every_declared_symbol(built):
     lib = backend.load_library()
     for name in declared_symbols():
         assert hasattr(lib, name), f"libptmi.so does not export {name}"
-    out = subprocess.run(["nm", "-D", "--defined-only", backend.library_path()], capture_output=True, text=True,
-                         check=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T " in l and "ptmi_" in l and "_Z" not in l}
+    exported = {name for name in exported_symbols() if "ptmi_" in name and "_Z" not in name}
     assert exported == set(declared_symbols()), exported ^ set(declared_symbols())
     assert lib.ptmi_abi_version() == 4
 

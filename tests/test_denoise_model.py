@@ -2,17 +2,14 @@
 of the GPU tests (denoise_cases.py) is held against a second, scalar restatement of the contract, and the properties that make
 the contract a denoiser are checked on the yardstick."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from opencl_pathtracer_amd import backend
+from abi_cases import declared_symbols, exported_symbols, header_values
 import denoise_cases as D
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = {"ptmi_denoise", "ptmi_denoise_device"}
 f32 = np.float32
 
@@ -20,39 +17,23 @@ f32 = np.float32
 # ---------------------------------------------------------------------------------------------- ABI
 
 def test_header_binding_list_and_library_agree(built):
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ptmi.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(ptmi_[a-z_]+)\s*\(", header))
+    declared = set(declared_symbols())
     assert NEW_SYMBOLS <= declared and declared == set(backend.ABI_SYMBOLS)
-    out = subprocess.run(["nm", "-D", "--defined-only", backend.library_path()], capture_output=True, text=True, check=True).stdout
-    assert NEW_SYMBOLS <= {l.split()[-1] for l in out.splitlines() if " T " in l}
+    assert NEW_SYMBOLS <= exported_symbols()
     assert backend.load_library().ptmi_abi_version() == 4
 
 
-LAYOUT_PROGRAM = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "ptmi.h"
-#define F(field) printf(#field " %zu\n", offsetof(ptmi_denoise_params, field))
-int main(void)
-{
-    printf("sizeof %zu\n", sizeof(ptmi_denoise_params));
-    F(struct_size); F(passes); F(flags); F(guide_first_iteration); F(guide_iterations); F(sigma_color); F(sigma_normal);
-    F(sigma_position); F(reserved);
-    printf("demodulate %u\n", PTMI_DENOISE_DEMODULATE_ALBEDO);
-    printf("untiled %u\n", PTMI_DENOISE_UNTILED);
-    return 0;
-}
-"""
+LAYOUT = ['VALUE("sizeof", sizeof(ptmi_denoise_params));', 'VALUE("demodulate", PTMI_DENOISE_DEMODULATE_ALBEDO);',
+          'VALUE("untiled", PTMI_DENOISE_UNTILED);'] + [
+    f'VALUE("{field}", offsetof(ptmi_denoise_params, {field}));' for field in
+    "struct_size passes flags guide_first_iteration guide_iterations sigma_color sigma_normal sigma_position reserved".split()]
 
 
-def test_ctypes_struct_matches_the_header(tmp_path):
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text(LAYOUT_PROGRAM)
-    subprocess.run(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = dict(line.rsplit(" ", 1) for line in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines())
+def test_ctypes_struct_matches_the_header():
+    out = header_values(LAYOUT)
     want = {"sizeof": C.sizeof(backend.DenoiseParams), "demodulate": backend.DENOISE_DEMODULATE_ALBEDO, "untiled": backend.DENOISE_UNTILED}
     want.update({name: getattr(backend.DenoiseParams, name).offset for name, _ in backend.DenoiseParams._fields_})
-    assert {k: int(v) for k, v in out.items()} == want
+    assert out == want
     assert C.sizeof(backend.DenoiseParams) == 40 and D.DEMODULATE == backend.DENOISE_DEMODULATE_ALBEDO
 
 

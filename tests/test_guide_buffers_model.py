@@ -2,54 +2,36 @@
 yardstick of the GPU tests (guide_cases.py) checks itself against the yardstick of the ray queries and against the conditions
 its scenes have to meet."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from opencl_pathtracer_amd import backend, structs as S
+from abi_cases import declared_symbols, exported_symbols, header_values
 import guide_cases as G
 import ray_query_cases as Q
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = {"ptmi_render_guides", "ptmi_render_guides_device"}
 
 
 # ---------------------------------------------------------------------------------------------- ABI
 
 def test_header_binding_list_and_library_agree(built):
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ptmi.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(ptmi_[a-z_]+)\s*\(", header))
+    declared = set(declared_symbols())
     assert NEW_SYMBOLS <= declared and declared == set(backend.ABI_SYMBOLS)
-    out = subprocess.run(["nm", "-D", "--defined-only", backend.library_path()], capture_output=True, text=True, check=True).stdout
-    assert NEW_SYMBOLS <= {l.split()[-1] for l in out.splitlines() if " T " in l}
+    assert NEW_SYMBOLS <= exported_symbols()
     assert backend.load_library().ptmi_abi_version() == 4
 
 
-LAYOUT_PROGRAM = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "ptmi.h"
-#define F(field) printf(#field " %zu\n", offsetof(ptmi_guides, field))
-int main(void)
-{
-    printf("sizeof %zu\n", sizeof(ptmi_guides));
-    F(struct_size); F(reserved); F(albedo); F(normal); F(position); F(hit_count); F(ids);
-    return 0;
-}
-"""
+LAYOUT = ['VALUE("sizeof", sizeof(ptmi_guides));'] + [
+    f'VALUE("{field}", offsetof(ptmi_guides, {field}));' for field in "struct_size reserved albedo normal position hit_count ids".split()]
 
 
-def test_ctypes_struct_matches_the_header(tmp_path):
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text(LAYOUT_PROGRAM)
-    subprocess.run(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = dict(line.rsplit(" ", 1) for line in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines())
+def test_ctypes_struct_matches_the_header():
+    out = header_values(LAYOUT)
     want = {"sizeof": C.sizeof(backend.Guides)}
     want.update({name: getattr(backend.Guides, name).offset for name, _ in backend.Guides._fields_})
-    assert {k: int(v) for k, v in out.items()} == want
+    assert out == want
     assert [name for name, _ in backend.Guides._fields_][2:] == list(backend.GUIDE_PLANES) == list(G.PLANES)
 
 

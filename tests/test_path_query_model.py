@@ -2,26 +2,21 @@
 (path_query_cases.py) held against the oracle's own render of the built-in camera, and the conditions on the ray sets that make
 a pass of test_path_query_gpu.py mean something."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from opencl_pathtracer_amd import backend, structs as S
+from abi_cases import exported_symbols, header_values
 import oracle_ffi as O
 import path_query_cases as P
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ---------------------------------------------------------------------------------------------- ABI and layout
 
 def test_library_exports_the_path_entry_points(built):
     """Both calls exist and refuse a NULL context with PTMI_ERR_INVALID_ARGUMENT, before they look at anything else."""
-    out = subprocess.run(["nm", "-D", "--defined-only", backend.library_path()], capture_output=True, text=True, check=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
-    assert {"ptmi_trace_paths", "ptmi_trace_paths_device"} <= exported
+    assert {"ptmi_trace_paths", "ptmi_trace_paths_device"} <= exported_symbols()
     assert {"ptmi_trace_paths", "ptmi_trace_paths_device"} <= set(backend.ABI_SYMBOLS)
     lib = backend.load_library()
     assert lib.ptmi_abi_version() == 4
@@ -31,30 +26,20 @@ def test_library_exports_the_path_entry_points(built):
     assert lib.ptmi_trace_paths(None, None, None, 0, None) == -1
 
 
-LAYOUT_PROGRAM = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "ptmi.h"
-#define F(type, field) printf(#type "." #field " %zu\n", offsetof(type, field))
-int main(void)
-{
-    printf("ptmi_path_params %zu\n", sizeof(ptmi_path_params));
-    F(ptmi_path_params, struct_size); F(ptmi_path_params, first_iteration); F(ptmi_path_params, n_iterations);
-    F(ptmi_path_params, first_index); F(ptmi_path_params, index_stride); F(ptmi_path_params, reserved);
-    printf("ptmi_path_sum %zu\n", sizeof(ptmi_path_sum));
-    F(ptmi_path_sum, radiance); F(ptmi_path_sum, segments); F(ptmi_path_sum, surface_hits); F(ptmi_path_sum, shadow_rays);
-    F(ptmi_path_sum, reserved); F(ptmi_path_sum, box_tests); F(ptmi_path_sum, triangle_tests);
-    printf("cap %u\n", (unsigned)PTMI_MAX_PATH_ITERATIONS);
-    return 0;
-}
-"""
+LAYOUT = """
+    SIZE(ptmi_path_params);
+    OFFSET(ptmi_path_params, struct_size); OFFSET(ptmi_path_params, first_iteration); OFFSET(ptmi_path_params, n_iterations);
+    OFFSET(ptmi_path_params, first_index); OFFSET(ptmi_path_params, index_stride); OFFSET(ptmi_path_params, reserved);
+    SIZE(ptmi_path_sum);
+    OFFSET(ptmi_path_sum, radiance); OFFSET(ptmi_path_sum, segments); OFFSET(ptmi_path_sum, surface_hits);
+    OFFSET(ptmi_path_sum, shadow_rays); OFFSET(ptmi_path_sum, reserved); OFFSET(ptmi_path_sum, box_tests);
+    OFFSET(ptmi_path_sum, triangle_tests);
+    VALUE("cap", PTMI_MAX_PATH_ITERATIONS);
+""".splitlines()
 
 
-def test_numpy_dtype_and_ctypes_struct_match_the_header(tmp_path):
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text(LAYOUT_PROGRAM)
-    subprocess.run(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = {k: int(v) for k, v in (line.rsplit(" ", 1) for line in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines())}
+def test_numpy_dtype_and_ctypes_struct_match_the_header():
+    out = header_values(LAYOUT)
     assert out.pop("cap") == 4096 == backend.MAX_PATH_ITERATIONS
     want = {"ptmi_path_params": 32, "ptmi_path_sum": 48}
     for field, _ in backend.PathParams._fields_:

@@ -1,15 +1,12 @@
 """ptmi_query_rays without a GPU: the yardstick of the GPU tests checks itself against a pass without a tree, and the new
 ABI (symbols, struct layouts) is held against the header."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from opencl_pathtracer_amd import backend, structs as S
+from abi_cases import exported_symbols, header_values
 import ray_query_cases as Q
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H = 64, 48
 
 
@@ -94,41 +91,30 @@ def test_the_generators_reach_the_thresholds(scene_factory):
 # ---------------------------------------------------------------------------------------------- ABI and layout
 
 def test_library_exports_the_query_entry_points(built):
-    out = subprocess.run(["nm", "-D", "--defined-only", backend.library_path()], capture_output=True, text=True, check=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
-    assert {"ptmi_query_rays", "ptmi_query_rays_device"} <= exported
+    assert {"ptmi_query_rays", "ptmi_query_rays_device"} <= exported_symbols()
     assert {"ptmi_query_rays", "ptmi_query_rays_device"} <= set(backend.ABI_SYMBOLS)
     assert backend.load_library().ptmi_abi_version() == 4
 
 
-LAYOUT_PROGRAM = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "ptmi.h"
-#define F(type, field) printf(#type "." #field " %zu\n", offsetof(type, field))
-int main(void)
-{
-    printf("ptmi_ray %zu\n", sizeof(ptmi_ray));
-    F(ptmi_ray, origin); F(ptmi_ray, direction); F(ptmi_ray, max_squared_distance); F(ptmi_ray, reserved);
-    printf("ptmi_ray_hit %zu\n", sizeof(ptmi_ray_hit));
-    F(ptmi_ray_hit, point); F(ptmi_ray_hit, squared_distance); F(ptmi_ray_hit, s); F(ptmi_ray_hit, t); F(ptmi_ray_hit, triangle_id);
-    F(ptmi_ray_hit, front); F(ptmi_ray_hit, box_tests); F(ptmi_ray_hit, triangle_tests); F(ptmi_ray_hit, reserved);
-    printf("kinds %d %d\n", (int)PTMI_QUERY_CLOSEST, (int)PTMI_QUERY_ANY);
-    return 0;
-}
-"""
+LAYOUT = """
+    SIZE(ptmi_ray);
+    OFFSET(ptmi_ray, origin); OFFSET(ptmi_ray, direction); OFFSET(ptmi_ray, max_squared_distance); OFFSET(ptmi_ray, reserved);
+    SIZE(ptmi_ray_hit);
+    OFFSET(ptmi_ray_hit, point); OFFSET(ptmi_ray_hit, squared_distance); OFFSET(ptmi_ray_hit, s); OFFSET(ptmi_ray_hit, t);
+    OFFSET(ptmi_ray_hit, triangle_id); OFFSET(ptmi_ray_hit, front); OFFSET(ptmi_ray_hit, box_tests);
+    OFFSET(ptmi_ray_hit, triangle_tests); OFFSET(ptmi_ray_hit, reserved);
+    VALUE("closest", PTMI_QUERY_CLOSEST); VALUE("any", PTMI_QUERY_ANY);
+""".splitlines()
 
 
-def test_numpy_dtypes_match_the_header(tmp_path):
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text(LAYOUT_PROGRAM)
-    subprocess.run(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = dict(line.rsplit(" ", 1) for line in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines() if not line.startswith("kinds"))
+def test_numpy_dtypes_match_the_header():
+    out = header_values(LAYOUT)
+    assert (out.pop("closest"), out.pop("any")) == (0, 1)
     want = {"ptmi_ray": S.RAY.itemsize, "ptmi_ray_hit": S.RAY_HIT.itemsize}
     for cname, dtype in (("ptmi_ray", S.RAY), ("ptmi_ray_hit", S.RAY_HIT)):
         for field in dtype.names:
             want[f"{cname}.{field}"] = dtype.fields[field][1]
-    assert {k: int(v) for k, v in out.items()} == want
+    assert out == want
     assert S.RAY.itemsize == 48 and S.RAY_HIT.itemsize == 48
     assert (backend.QUERY_CLOSEST, backend.QUERY_ANY) == (0, 1)
 

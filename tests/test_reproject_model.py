@@ -2,16 +2,14 @@
 the yardstick of the GPU tests (reproject_cases.py) held bit for bit against a second restatement of the contract - a scalar
 loop over pixels and taps - and the properties that make it a reprojection."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from opencl_pathtracer_amd import backend
+from abi_cases import exported_symbols, header_values
 import reproject_cases as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 NAMES = {"ptmi_reproject_device", "ptmi_set_camera_reprojected"}
 
@@ -20,9 +18,7 @@ NAMES = {"ptmi_reproject_device", "ptmi_set_camera_reprojected"}
 
 def test_library_exports_the_reproject_entry_points(built):
     """Both calls exist and refuse a NULL context with PTMI_ERR_INVALID_ARGUMENT, before they look at anything else."""
-    out = subprocess.run(["nm", "-D", "--defined-only", backend.library_path()], capture_output=True, text=True, check=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
-    assert NAMES <= exported
+    assert NAMES <= exported_symbols()
     assert NAMES <= set(backend.ABI_SYMBOLS)
     lib = backend.load_library()
     assert lib.ptmi_abi_version() == 4
@@ -32,27 +28,16 @@ def test_library_exports_the_reproject_entry_points(built):
     assert lib.ptmi_set_camera_reprojected(None, None, None, None, None, None) == -1
 
 
-LAYOUT_PROGRAM = r"""
-#include <stddef.h>
-#include <stdio.h>
-#include "ptmi.h"
-#define F(type, field) printf(#type "." #field " %zu\n", offsetof(type, field))
-int main(void)
-{
-    printf("ptmi_reproject_params %zu\n", sizeof(ptmi_reproject_params));
-    F(ptmi_reproject_params, struct_size); F(ptmi_reproject_params, flags); F(ptmi_reproject_params, guide_first_iteration);
-    F(ptmi_reproject_params, guide_iterations); F(ptmi_reproject_params, position_tolerance);
-    F(ptmi_reproject_params, normal_tolerance); F(ptmi_reproject_params, max_history); F(ptmi_reproject_params, reserved);
-    return 0;
-}
-"""
+LAYOUT = """
+    SIZE(ptmi_reproject_params);
+    OFFSET(ptmi_reproject_params, struct_size); OFFSET(ptmi_reproject_params, flags); OFFSET(ptmi_reproject_params, guide_first_iteration);
+    OFFSET(ptmi_reproject_params, guide_iterations); OFFSET(ptmi_reproject_params, position_tolerance);
+    OFFSET(ptmi_reproject_params, normal_tolerance); OFFSET(ptmi_reproject_params, max_history); OFFSET(ptmi_reproject_params, reserved);
+""".splitlines()
 
 
-def test_ctypes_struct_matches_the_header(tmp_path):
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text(LAYOUT_PROGRAM)
-    subprocess.run(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = {k: int(v) for k, v in (line.rsplit(" ", 1) for line in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines())}
+def test_ctypes_struct_matches_the_header():
+    out = header_values(LAYOUT)
     want = {"ptmi_reproject_params": 32}
     for field, _ in backend.ReprojectParams._fields_:
         want[f"ptmi_reproject_params.{field}"] = getattr(backend.ReprojectParams, field).offset
