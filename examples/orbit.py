@@ -9,6 +9,12 @@ One context calls ptmi_clear after every move, as a caller had to: each of its f
 moves with ptmi_set_camera_reprojected: every pixel whose surface the previous camera saw too keeps its mean and its sample count,
 only the revealed ones restart, and ptmi_denoise filters what is left of the noise.  One BMP per step and way, to be flipped
 through side by side.
+
+    python examples/orbit.py --tone filmic --transfer srgb --exposure auto
+
+With --tone, --transfer or --exposure the frames are displayed on the device (ptmi_read_display_tonemapped; guides, filter and
+ptmi_display_device between tensors for the carried image), `auto` choosing the exposure from the luminance histogram of each
+frame: 3 bytes per pixel cross the bus, no float plane.
 """
 import argparse
 import os
@@ -20,6 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import opencl_pathtracer_amd as pt  # noqa: E402
 from opencl_pathtracer_amd import output, structs as S  # noqa: E402
+import display_options  # noqa: E402
 
 
 def main():
@@ -36,7 +43,9 @@ def main():
     ap.add_argument("--max-history", type=float, default=d["max_history"])
     ap.add_argument("--out", default="orbit", help="prefix of the BMPs")
     ap.add_argument("--device", type=int, default=0)
+    display_options.add_arguments(ap)
     args = ap.parse_args()
+    display = display_options.chosen(args)
 
     w, h, n = args.width, args.height, max(args.spp, 1)
     scene = pt.bvh_create(pt.scenes.build(args.scene, w, h))
@@ -60,9 +69,18 @@ def main():
             clearing.clear()
             carrying.set_camera_reprojected(*camera, position_tolerance=args.position_tolerance, normal_tolerance=args.normal_tolerance,
                                             max_history=args.max_history, guide_first_iteration=first, guide_iterations=n)
-            kept.append(float((carrying.read_image()[1] > 0).mean()))
+            if display:  # (word 256: the pixels without a sample - no plane is read back)
+                kept.append(1.0 - float(carrying.luminance_histogram()[256]) / (w * h))
+            else:
+                kept.append(float((carrying.read_image()[1] > 0).mean()))
         for be in contexts:
             be.render(first, n)
+        if display:
+            output.save_bmp_rows(f"{args.out}_clear_{step:02d}.bmp", clearing.display(exposure=display_options.exposure_of(clearing, args), **display), w, h)
+            rows = display_options.denoised_rows(carrying, display_options.exposure_of(carrying, args), display, guide_first_iteration=first,
+                                                 guide_iterations=n)
+            output.save_bmp_rows(f"{args.out}_reprojected_{step:02d}.bmp", rows, w, h)
+            continue
         output.save_bmp(f"{args.out}_clear_{step:02d}.bmp", *clearing.read_image())
         output.save_bmp(f"{args.out}_reprojected_{step:02d}.bmp", carrying.denoise(guide_first_iteration=first, guide_iterations=n))
     for be in contexts:

@@ -10,7 +10,6 @@ The pixels are quantised on the device (ptmi_read_display): 3 bytes per pixel cr
 """
 import argparse
 import os
-import struct
 import sys
 import time
 
@@ -19,13 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 
 import opencl_pathtracer_amd as pt  # noqa: E402
-
-
-def save_bmp(path, rows, w, h):
-    with open(path, "wb") as f:  # SaveBMP, Alone/PathTracer_bitmap.cpp:146-205
-        f.write(struct.pack("<HIHHI", 0x4D42, 14 + 40 + rows.size, 0, 0, 0x36))
-        f.write(struct.pack("<IiiHHIIiiII", 40, w, h, 1, 24, 0, 0, 0x0EC4, 0x0EC4, 0, 0))
-        f.write(rows.tobytes())
+from opencl_pathtracer_amd.output import save_bmp_rows as save_bmp  # noqa: E402  (SaveBMP, Alone/PathTracer_bitmap.cpp:146-205)
 
 
 def orbit_camera(scene, angle):

@@ -593,6 +593,80 @@ int ptmi_reproject_device(ptmi_ctx* ctx, const ptmi_reproject_params* params, co
 int ptmi_set_camera_reprojected(ptmi_ctx* ctx, const ptmi_float4* position, const ptmi_float4* direction, const ptmi_float4* right,
                                 const ptmi_float4* up, const ptmi_reproject_params* params);
 
+/* ---- displaying an image ------------------------------------------------- */
+
+/* The last stage of a viewer's pipeline: any image plane -> 8-bit pixels, on the device, so that 3 (or 4) bytes per pixel cross
+ * the bus and no float plane does.  Exposure, a tone operator, a display transfer function, quantisation by rounding to the
+ * nearest encoded value; and a luminance histogram of the same image, from which a viewer chooses the exposure without reading
+ * the image back.  ptmi_read_display (above) stays what it is: the reference viewer's linear clamp, the parity path.
+ *
+ * THE IMAGE.  The host forms take the image ptmi_read_image would return at this moment (on a multi-device context the shares
+ * are summed first, as for ptmi_read_display and ptmi_denoise).  The device forms take
+ *   d_color and d_count    any float4[W*H] sum plane and float[W*H] count plane: a snapshot, ptmi_reproject_device's result;
+ *   d_color alone          a float4[W*H] MEAN plane whose fourth word is ignored: exactly what ptmi_denoise_device writes;
+ *   neither                the context's own accumulators (PTMI_ERR_UNSUPPORTED on a multi-device context, as for
+ *                          ptmi_denoise_device);
+ *   d_count alone          PTMI_ERR_INVALID_ARGUMENT.
+ *
+ * THE ARITHMETIC, the same in both arithmetic modes of a context.  Every operation is one IEEE binary32 operation in the
+ * written order: no contraction, correctly rounded division, denormals kept, no transcendental on the device.
+ * min(a, b) = a < b ? a : b.  Pixel p, channel c of r, g, b:
+ *   1. mean.      sum form: n = count[p]; m_c = n > 0 ? sum_c / n : 0 (a count that is zero, negative or NaN shows BLACK, not
+ *                 255);  mean form: m_c = plane_c.
+ *   2. exposure.  x = m_c * exposure;  if (!(x > 0)) x = 0  (NaN and negative values go to 0).
+ *   3. tone.      CLAMP: t = x.   REINHARD: w2 = white * white on the host in float; t = (x * (1.f + x / w2)) / (1.f + x).
+ *                 FILMIC (Narkowicz's fit of the ACES curve): t = (x * (2.51f * x + 0.03f)) / (x * (2.43f * x + 0.59f) + 0.14f).
+ *                 Then, for all three, t = min(t, 1.f): the NaN of inf / inf at a huge x becomes 1, white.
+ *   4. transfer and quantisation.  byte = the largest k in 0..255 with T[k] <= t, T = ptmi_display_table(transfer):
+ *                 T[0] = 0, T[k] = (float) EOTF((k - 0.5) / 255.0) with the EOTF evaluated in double - round to nearest AFTER
+ *                 encoding.  LINEAR: v.  SRGB: v <= 0.04045 ? v / 12.92 : pow((v + 0.055) / 1.055, 2.4).  GAMMA22: pow(v, 2.2).
+ *                 The three tables are constants of the source (csrc/display_tables.inc), strictly increasing.
+ *   5. output.    BGR24: B, G, R per pixel in scanlines of row_stride bytes, EVERY padding byte written 0 (ptmi_read_display's
+ *                 layout);  RGBA32: R, G, B, 255.  Image row 0 first.
+ * THE LUMINANCE HISTOGRAM works on the mean m of step 1, before exposure:  Y = (0.2126f * m.x + 0.7152f * m.y) + 0.0722f * m.z.
+ *   words 0..255   the pixels with Y > 0 and Y finite, in quarter-octave bins read off the float's own bits:
+ *                  bin = clamp((bits(Y) >> 21) - 380, 0, 255); bin b starts at (1 + (b & 3) / 4) * 2^((b >> 2) - 32), bin 128 at 1.0;
+ *   word 256       the pixels with !(Y > 0): black, negative, NaN, never sampled;
+ *   word 257       the pixels with Y == +inf;    words 258, 259: 0.
+ * The 260 words sum to W*H.  Counts are integers added with atomics: the result does not depend on an order.
+ *
+ * ORDER AND STATE.  The device forms are asynchronous on the context's main stream (ptmi_set_stream's, where one was given),
+ * ordered like ptmi_denoise_device; the host forms wait for their own stream before they return.  All four calls TOUCH NOTHING
+ * THAT HAS BEEN RENDERED (the list of the guide and denoise calls).  Scratch on devices[0]: none for the device forms; for the
+ * host forms the display buffer ptmi_read_display uses, grown on demand, and 1040 bytes for the histogram.
+ * PTMI_ERR_STATE before ptmi_initialize_memory; PTMI_ERR_INVALID_ARGUMENT for a NULL struct, a wrong struct_size, a non-zero
+ * flags or reserved word, an unknown tone, transfer or format, a row_stride outside its range, an exposure that is not finite
+ * and > 0, under REINHARD a white that is NaN or <= 0, a NULL output, a device pointer that is not 16-byte aligned.  After any
+ * error the context renders as before. */
+enum { PTMI_TONE_CLAMP = 0, PTMI_TONE_REINHARD = 1, PTMI_TONE_FILMIC = 2 };
+enum { PTMI_TRANSFER_LINEAR = 0, PTMI_TRANSFER_SRGB = 1, PTMI_TRANSFER_GAMMA22 = 2 };
+enum { PTMI_PIXELS_BGR24 = 0,   /* B,G,R scanlines of row_stride bytes, padding zero-filled: ptmi_read_display's layout */
+       PTMI_PIXELS_RGBA32 = 1 };/* R,G,B,255 - 4 bytes per pixel, row_stride = 4*W exactly */
+
+typedef struct ptmi_display_params {   /* 48 bytes */
+    uint32_t struct_size;   /* = sizeof(ptmi_display_params) */
+    uint32_t flags;         /* 0: none defined */
+    uint32_t tone, transfer, format;
+    uint32_t row_stride;    /* BGR24: 3*W .. 3*W+3;  RGBA32: 4*W */
+    float exposure;         /* finite, > 0 */
+    float white;            /* REINHARD only: > 0, +INFINITY allowed (= plain x/(1+x)), not NaN; ignored otherwise */
+    uint32_t reserved[4];   /* 0 */
+} ptmi_display_params;
+
+#define PTMI_LUMINANCE_WORDS 260u
+
+/* The 256 thresholds of a transfer function (step 4).  Host only: no device, no context.  PTMI_ERR_INVALID_ARGUMENT for an
+ * unknown transfer or a NULL table, with the message in ptmi_last_error(NULL). */
+int ptmi_display_table(uint32_t transfer, float table[256]);
+/* Host form: `pixels` holds H * row_stride bytes, filled when the call returns - directly where the caller has page-locked it
+ * (ptmi_pin_host_buffer). */
+int ptmi_read_display_tonemapped(ptmi_ctx* ctx, const ptmi_display_params* params, uint8_t* pixels);
+/* Device form: d_pixels holds H * row_stride bytes, 16-byte aligned like the planes, and MUST NOT ALIAS AN INPUT. */
+int ptmi_display_device(ptmi_ctx* ctx, const ptmi_display_params* params, const void* d_color, const void* d_count, void* d_pixels);
+int ptmi_luminance_histogram(ptmi_ctx* ctx, uint32_t histogram[PTMI_LUMINANCE_WORDS]);
+/* Device form: d_histogram holds PTMI_LUMINANCE_WORDS words, 16-byte aligned; the call zeroes it on the stream before it counts. */
+int ptmi_luminance_histogram_device(ptmi_ctx* ctx, const void* d_color, const void* d_count, void* d_histogram);
+
 /* ---- measurement / plumbing -------------------------------------------- */
 
 int ptmi_get_counters(ptmi_ctx* ctx, ptmi_counters* out);

@@ -110,6 +110,14 @@ class ReprojectParams(C.Structure):
                 ("max_history", C.c_float), ("reserved", C.c_uint32)]
 
 
+class DisplayParams(C.Structure):
+    """ptmi_display_params: exposure, tone operator, transfer function and pixel format of ptmi_read_display_tonemapped /
+    ptmi_display_device (ptmi.h states its arithmetic)."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("tone", C.c_uint32), ("transfer", C.c_uint32),
+                ("format", C.c_uint32), ("row_stride", C.c_uint32), ("exposure", C.c_float), ("white", C.c_float),
+                ("reserved", C.c_uint32 * 4)]
+
+
 class PathParams(C.Structure):
     """ptmi_path_params: which iterations ptmi_trace_paths traces for every ray, and the index its seeds come from."""
     _fields_ = [("struct_size", C.c_uint32), ("first_iteration", C.c_uint32), ("n_iterations", C.c_uint32),
@@ -131,6 +139,14 @@ DENOISE_DEFAULTS = dict(passes=5, sigma_color=8.0, sigma_normal=1.0, sigma_posit
 # POSITION TEST OFF and the normal test and the image's frame do the work: tighten it to a few pixel spacings
 # (a pixel is 1 / W of the distance wide) where parallel surfaces lie at different depths.
 REPROJECT_DEFAULTS = dict(position_tolerance=0.64, normal_tolerance=1.0, max_history=16.0)
+
+TONE_CLAMP, TONE_REINHARD, TONE_FILMIC = 0, 1, 2  # ptmi.h: PTMI_TONE_*
+TRANSFER_LINEAR, TRANSFER_SRGB, TRANSFER_GAMMA22 = 0, 1, 2  # ptmi.h: PTMI_TRANSFER_*
+PIXELS_BGR24, PIXELS_RGBA32 = 0, 1  # ptmi.h: PTMI_PIXELS_*
+LUMINANCE_WORDS = 260  # ptmi.h: PTMI_LUMINANCE_WORDS
+# What a viewer wants by default, and not what read_display gives (the reference viewer's linear clamp, kept for parity): a
+# filmic curve that rolls the highlights off instead of clipping them, and the sRGB encoding displays expect.
+DISPLAY_DEFAULTS = dict(tone=TONE_FILMIC, transfer=TRANSFER_SRGB, exposure=1.0, white=float("inf"))
 
 
 BVH_FALLBACK_NONE, BVH_FALLBACK_STALE_AXIS, BVH_FALLBACK_HOST_ERROR, BVH_FALLBACK_RECORDS = 0, 1, 2, 3
@@ -173,9 +189,35 @@ ABI_SYMBOLS = ["ptmi_setup_context", "ptmi_initialize_memory", "ptmi_render", "p
                "ptmi_bvh_create_device", "ptmi_set_camera", "ptmi_update_triangles", "ptmi_bvh_refit",
                "ptmi_query_rays", "ptmi_query_rays_device", "ptmi_render_guides", "ptmi_render_guides_device",
                "ptmi_denoise", "ptmi_denoise_device", "ptmi_trace_paths", "ptmi_trace_paths_device",
-               "ptmi_reproject_device", "ptmi_set_camera_reprojected"]
+               "ptmi_reproject_device", "ptmi_set_camera_reprojected",
+               "ptmi_display_table", "ptmi_read_display_tonemapped", "ptmi_display_device", "ptmi_luminance_histogram",
+               "ptmi_luminance_histogram_device"]
 
 QUERY_CLOSEST, QUERY_ANY = 0, 1  # ptmi.h: PTMI_QUERY_*
+
+
+def display_table(transfer):
+    """float32[256]: the thresholds of a ``TRANSFER_*`` function - byte k is shown from T[k] on (ptmi_display_table; no device)."""
+    lib = load_library()
+    out = np.empty(256, np.float32)
+    rc = lib.ptmi_display_table(transfer, out.ctypes.data_as(C.c_void_p))
+    if rc:
+        raise PtmiError(rc, lib.ptmi_last_error(None).decode())
+    return out
+
+
+def exposure_from_histogram(hist, key=0.18):
+    """The exposure that brings the image's log-average luminance to ``key`` (middle grey), from ``luminance_histogram``'s words:
+    bin b stands for log2 luminance L_b = (b >> 2) - 32 + log2(1 + ((b & 3) + 0.5) / 4), the middle of its quarter octave;
+    exposure = key / 2 ** (sum(hist[b] * L_b) / sum(hist[b])) over words 0..255.  1.0 where no pixel is positive.  Host only, in
+    Python double."""
+    import math
+    counts = [int(x) for x in hist[:256]]
+    total = sum(counts)
+    if total == 0:
+        return 1.0
+    mean = sum(n * ((b >> 2) - 32 + math.log2(1 + ((b & 3) + 0.5) / 4)) for b, n in enumerate(counts) if n) / total
+    return key / 2.0 ** mean
 
 
 def library_path():
@@ -239,6 +281,11 @@ def load_library():
     lib.ptmi_reproject_device.argtypes = [vp, C.POINTER(ReprojectParams), C.POINTER(Float4 * 4), C.POINTER(Guides), vp, vp, C.POINTER(Guides), vp, vp]
     lib.ptmi_set_camera_reprojected.argtypes = [vp, C.POINTER(Float4), C.POINTER(Float4), C.POINTER(Float4), C.POINTER(Float4),
                                                 C.POINTER(ReprojectParams)]
+    lib.ptmi_display_table.argtypes = [u32, vp]
+    lib.ptmi_read_display_tonemapped.argtypes = [vp, C.POINTER(DisplayParams), vp]
+    lib.ptmi_display_device.argtypes = [vp, C.POINTER(DisplayParams), vp, vp, vp]
+    lib.ptmi_luminance_histogram.argtypes = [vp, vp]
+    lib.ptmi_luminance_histogram_device.argtypes = [vp, vp, vp, vp]
     lib.ptmi_device_share.argtypes = [u32, u32, u32, u32, C.POINTER(u32), C.POINTER(u32)]
     lib.ptmi_device_share.restype = None
     _lib = lib
@@ -625,6 +672,50 @@ class Backend:
         out = np.empty((h, stride), np.uint8)
         self._check(self._lib.ptmi_read_display(self._ctx, _ptr(out), stride))
         return out
+
+    # -- the display stage: any image plane -> 8-bit pixels on the device (no counterpart in the reference) --
+    def display_params(self, tone=None, transfer=None, exposure=None, white=None, rgba=False, row_stride=None):
+        """A ``DisplayParams`` for this context's image; what is None takes its value from ``DISPLAY_DEFAULTS``, ``row_stride``
+        the BMP stride (3W rounded up to 4) or, with ``rgba``, 4W."""
+        given = dict(tone=tone, transfer=transfer, exposure=exposure, white=white)
+        v = {k: DISPLAY_DEFAULTS[k] if x is None else x for k, x in given.items()}
+        w = self.cfg.image_width
+        stride = (4 * w if rgba else (3 * w + 3) & ~3) if row_stride is None else row_stride
+        return DisplayParams(C.sizeof(DisplayParams), 0, v["tone"], v["transfer"], PIXELS_RGBA32 if rgba else PIXELS_BGR24, stride,
+                             v["exposure"], v["white"])
+
+    def display(self, tone=None, transfer=None, exposure=None, white=None, rgba=False, out=None):
+        """The image ``read_image`` would return, exposed, tone-mapped, encoded and quantised on the device: padded B,G,R
+        scanlines uint8[H, (3W+3)&~3] (``save_bmp_rows`` writes them as they are) or, with ``rgba``, uint8[H, W, 4] = R, G, B, 255.
+        ``out`` = an array to fill (e.g. a page-locked one).  Touches nothing that has been rendered."""
+        h, w = self.cfg.image_height, self.cfg.image_width
+        p = self.display_params(tone, transfer, exposure, white, rgba)
+        shape = (h, w, 4) if rgba else (h, p.row_stride)
+        pixels = np.empty(shape, np.uint8) if out is None else out
+        if pixels.dtype != np.uint8 or pixels.shape != shape or not pixels.flags.c_contiguous:
+            raise PtmiError(-1, f"out must be a contiguous uint8 array of shape {shape}")
+        self._check(self._lib.ptmi_read_display_tonemapped(self._ctx, C.byref(p), _ptr(pixels)))
+        return pixels
+
+    def display_device(self, out, image_color=None, image_ray_nb=None, **params):
+        """The same between device addresses (e.g. ``tensor.data_ptr()``), 16-byte aligned: ``out`` holds H * row_stride bytes;
+        both planes = float4 sums and float counts, ``image_color`` alone = a mean plane (what ``denoise_device`` writes), neither =
+        the context's own accumulators.  Keywords as for ``display_params``.  Asynchronous on the context's stream."""
+        p = self.display_params(**params)
+        self._check(self._lib.ptmi_display_device(self._ctx, C.byref(p), C.c_void_p(image_color), C.c_void_p(image_ray_nb), C.c_void_p(out)))
+
+    def luminance_histogram(self):
+        """uint32[260] of the image ``read_image`` would return: words 0..255 count the pixels of positive finite mean luminance in
+        quarter-octave bins (bin 128 starts at 1.0), word 256 the pixels that are not positive, word 257 the infinite ones
+        (ptmi.h).  ``exposure_from_histogram`` turns it into an exposure."""
+        out = np.empty(LUMINANCE_WORDS, np.uint32)
+        self._check(self._lib.ptmi_luminance_histogram(self._ctx, _ptr(out)))
+        return out
+
+    def luminance_histogram_device(self, out, image_color=None, image_ray_nb=None):
+        """The same between device addresses, the planes as for ``display_device``; ``out`` holds 260 words, which the call zeroes
+        on the stream before it counts.  Asynchronous on the context's stream."""
+        self._check(self._lib.ptmi_luminance_histogram_device(self._ctx, C.c_void_p(image_color), C.c_void_p(image_ray_nb), C.c_void_p(out)))
 
     def read_statistics(self):
         """(rayDepths[D+1], rayIntersectedBBx[5000], rayIntersectedTri[5000]), OpenCL.cpp:110-112."""

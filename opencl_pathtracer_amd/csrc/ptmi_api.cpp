@@ -298,6 +298,7 @@ void ptmi_release(ptmi_ctx* ctx)
     if (ctx->denoise_ordered) (void)hipEventDestroy(ctx->denoise_ordered);
     if (ctx->d_reproject_scratch) (void)hipFree(ctx->d_reproject_scratch);
     if (ctx->reproject_gathered) (void)hipEventDestroy(ctx->reproject_gathered);
+    if (ctx->d_luminance) (void)hipFree(ctx->d_luminance);
     destroy_rccl_communicators(ctx);
     for (auto& r : ctx->pinned_host) (void)hipHostUnregister(r.p);
     (void)hipGetLastError();

@@ -1,5 +1,5 @@
 // ptmi_context.h - the state behind a ptmi_ctx, grouped by WHEN IT DIES, and what the host units of libptmi.so share
-// (ptmi_api.cpp, ptmi_scene_memory.cpp, ptmi_render.cpp, ptmi_readback.cpp, ptmi_query.cpp, ptmi_paths.cpp, ptmi_guides.cpp, ptmi_denoise.cpp, ptmi_reproject.cpp).  Private: not ABI, never installed.
+// (ptmi_api.cpp, ptmi_scene_memory.cpp, ptmi_render.cpp, ptmi_readback.cpp, ptmi_query.cpp, ptmi_paths.cpp, ptmi_guides.cpp, ptmi_denoise.cpp, ptmi_reproject.cpp, ptmi_display.cpp).  Private: not ABI, never installed.
 //
 // Two lifetimes.  PER SCENE (DeviceScene, ContextScene): free_scene_memory() frees what the struct owns and assigns a
 // value-initialised one, so a new per-scene field needs no line anywhere else.  PER CONTEXT (the members DeviceState and ptmi_ctx
@@ -106,7 +106,7 @@ struct ContextScene {
     bool have_refit = false;
     // on devices[0], owned
     float* d_reduced = nullptr;    // sum of the devices' snapshots (n_devices > 1)
-    uint8_t* d_display = nullptr;  // B,G,R scanlines of ptmi_read_display
+    uint8_t* d_display = nullptr;  // the pixels of ptmi_read_display and of ptmi_read_display_tonemapped
     size_t display_bytes = 0;
 };
 
@@ -143,6 +143,9 @@ struct ptmi_ctx : ptmi_internal::ContextScene {
     // gathered image, which the main stream waits for
     char* d_reproject_scratch = nullptr;
     hipEvent_t reproject_gathered = nullptr;
+    // ptmi_luminance_histogram (ptmi_display.cpp), on devices[0], allocated by the first call: the 260 words of the host form.
+    // (ptmi_read_display_tonemapped shares ContextScene::d_display with ptmi_read_display; the device forms need no scratch.)
+    uint32_t* d_luminance = nullptr;
 
     ptmi_internal::ContextScene& scene() { return *this; }
     uint32_t n_dev() const { return (uint32_t)dev.size(); }

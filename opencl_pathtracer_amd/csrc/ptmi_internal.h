@@ -288,6 +288,20 @@ int launch_guides_da(const DScene& sc, const DGuides& planes, uint32_t first_ite
 int launch_display_bgr(const float* image_color, const float* image_ray_nb, uint8_t* out, uint32_t width, uint32_t height,
                        uint32_t row_stride, void* stream, std::string* err);
 
+// display.hip (compiled once: one arithmetic for both modes): ptmi_display_device and ptmi_luminance_histogram_device on DEVICE
+// pointers, on `stream`, no scratch.  ray_nb = nullptr: `color` is a mean plane.  w2 = white * white, computed by the host in
+// float.  launch_luminance_histogram zeroes the 260 words on the stream, then counts.
+struct DisplayJob {
+    const float *color, *ray_nb;  // float4[W*H] sums and float[W*H] counts, or float4[W*H] means and nullptr
+    uint8_t* out;                 // height * row_stride bytes
+    uint32_t width, height, row_stride;
+    uint32_t tone, transfer, format;  // PTMI_TONE_*, PTMI_TRANSFER_*, PTMI_PIXELS_*
+    float exposure, w2;
+};
+int launch_display_tonemapped(const DisplayJob& job, void* stream, std::string* err);
+int launch_luminance_histogram(const float* color, const float* ray_nb, uint32_t* histogram, size_t n_pixels, void* stream, std::string* err);
+const float* display_table(uint32_t transfer);  // the 256 thresholds of PTMI_TRANSFER_* `transfer` (< 3), host memory
+
 // denoise.hip (compiled once: the filter's arithmetic is the same in both modes): the prepass and `passes` a-trous passes of
 // ptmi_denoise on DEVICE pointers, all on `stream`.  `features` = 56 bytes per pixel of scratch (two e planes, g1, g2); the
 // sigmas arrive as the reciprocals the contract has the host compute in float.  tiled: steps 1 and 2 stage their tile in LDS.

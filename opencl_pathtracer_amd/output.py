@@ -46,3 +46,12 @@ def save_bmp(path, image_color, image_ray_nb=None):
         f.write(struct.pack("<HIHHI", 0x4D42, 14 + 40 + len(data), 0, 0, 0x36))
         f.write(struct.pack("<IiiHHIIiiII", 40, w, h, 1, 24, 0, 0, 0x0EC4, 0x0EC4, 0, 0))
         f.write(data)
+
+
+def save_bmp_rows(path, rows, width, height):
+    """SaveBMP of scanlines that are B,G,R and padded already: what ``Backend.read_display`` and ``Backend.display`` return,
+    quantised on the device."""
+    with open(path, "wb") as f:
+        f.write(struct.pack("<HIHHI", 0x4D42, 14 + 40 + rows.size, 0, 0, 0x36))
+        f.write(struct.pack("<IiiHHIIiiII", 40, width, height, 1, 24, 0, 0, 0x0EC4, 0x0EC4, 0, 0))
+        f.write(rows.tobytes())
