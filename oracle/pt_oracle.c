@@ -513,6 +513,13 @@ static f4 triangle_color_at(const pto_scene* sc, const ptmi_triangle* tri, int p
     return texture_pixel(&sc->textures[mat->texture_id], sc->textures_data, u, v);
 }
 
+/* The reciprocal determinant of Triangle_Intersects, cl:556: `1 / (uv * uv - uu * vv)` in this build's arithmetic (one
+ * expression of the reference: contracted and divided as its build does).  uv, uu, vv: cl:550, 553, 554. */
+static inline float triangle_inverse_determinant(float uv, float uu, float vv)
+{
+    return fdiv(1, mad(uv, uv, -(uu * vv))); /* cl:556 */
+}
+
 /* Triangle_Intersects, cl:519-589.  `shade` = fetch the colour as the
  * reference does on every accepted hit (cl:568-570); the shadow traversal
  * never reads it so it passes 0 there. */
@@ -539,7 +546,7 @@ static int triangle_intersects(const pto_scene* sc, const ptmi_triangle* tri, ra
 
         w = sub4(q, S1);
         uv = dot4(u, v); wv = dot4(w, v); wu = dot4(w, u); uu = dot4(u, u); vv = dot4(v, v);
-        denom = fdiv(1, mad(uv, uv, -(uu * vv))); /* cl:556 */
+        denom = triangle_inverse_determinant(uv, uu, vv); /* cl:556 */
         s = mad(uv, wv, -(vv * wu)) * denom;      /* cl:558 */
         t = mad(uv, wu, -(uu * wv)) * denom;      /* cl:559 */
         if (s < 0 || t < 0 || s + t > 1) return 0;
@@ -1153,6 +1160,15 @@ int pto_triangle_intersects(const ptmi_triangle* tri, const float origin[4], con
     return pto_triangle_intersects_side(tri, origin, direction, squared_distance, s, t, point, NULL);
 }
 
+/* cl:556 on its own, from the triangle alone (cl:528-529 the edges, cl:550, 553, 554 the three dot products): what every test
+ * of this triangle computes whatever the ray - the value a record that precomputes it must hold (tests/test_scene_records_gpu.py). */
+float pto_triangle_inverse_determinant(const ptmi_triangle* tri)
+{
+    const f4 S1 = ld4(&tri->s1), S2 = ld4(&tri->s2), S3 = ld4(&tri->s3);
+    const f4 u = sub4(S2, S1), v = sub4(S3, S1);
+    return triangle_inverse_determinant(dot4(u, v), dot4(u, u), dot4(v, v));
+}
+
 /* The rejection of Triangle_Intersects that fires FIRST in the reference's order (cl:533, 542, 543, 561, 566), 0 = accepted:
  * for the coverage counts of tests/test_unit_probe_model.py. */
 int pto_triangle_first_rejection(const ptmi_triangle* tri, const float origin[4], const float direction[4], float squared_distance)
@@ -1173,7 +1189,7 @@ int pto_triangle_first_rejection(const ptmi_triangle* tri, const float origin[4]
     if (nsd < 0.00001f) return 3;
     w = sub4(q, S1);
     uv = dot4(u, v); wv = dot4(w, v); wu = dot4(w, u); uu = dot4(u, u); vv = dot4(v, v);
-    denom = fdiv(1, mad(uv, uv, -(uu * vv)));
+    denom = triangle_inverse_determinant(uv, uu, vv);
     s = mad(uv, wv, -(vv * wu)) * denom;
     t = mad(uv, wu, -(uu * wv)) * denom;
     if (s < 0) return 4;

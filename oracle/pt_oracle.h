@@ -117,6 +117,8 @@ int pto_triangle_intersects(const ptmi_triangle* tri, const float origin[4], con
 /* the same, and *positive_normal = the side that was hit (cl:568), written on a hit */
 int pto_triangle_intersects_side(const ptmi_triangle* tri, const float origin[4], const float direction[4],
                                  float* squared_distance, float* s, float* t, float point[4], int* positive_normal);
+/* cl:556 alone: 1 / (uv * uv - uu * vv) of the triangle's edge vectors, in this build's arithmetic */
+float pto_triangle_inverse_determinant(const ptmi_triangle* tri);
 /* which test decided, in the reference's order (coverage counts of tests/test_unit_probe_model.py; the lists are in pt_oracle.c) */
 int pto_triangle_first_rejection(const ptmi_triangle* tri, const float origin[4], const float direction[4], float squared_distance);
 int pto_bounding_box_decider(const ptmi_bounding_box* bb, const float origin[4], const float direction[4], float squared_distance);

@@ -49,15 +49,20 @@ extern "C" {
 const char* model_error() { return g_error.c_str(); }
 
 // build_layout's result for `scene` (what ptmi_initialize_memory uploads), or NULL with *status and model_error() set
-void* model_layout(const ptmi_config* cfg, const ptmi_scene* scene, int* status)
+// (a scene that the one-path-per-lane kernel renders, literal_kernel_reason, cannot be updated in place: refused here, where the
+// layouts are made for model_update)
+static void* layout_of(const ptmi_config* cfg, const ptmi_scene* scene, int* status, bool for_update)
 {
     Layout* l = new Layout();
     *status = build_layout(*cfg, scene, l->lay, g_error);
-    if (*status == PTMI_OK && !l->lay.literal_kernel_reason.empty()) { *status = PTMI_ERR_UNSUPPORTED; g_error = l->lay.literal_kernel_reason; }
+    if (for_update && *status == PTMI_OK && !l->lay.literal_kernel_reason.empty()) { *status = PTMI_ERR_UNSUPPORTED; g_error = l->lay.literal_kernel_reason; }
     if (*status != PTMI_OK) { delete l; return nullptr; }
     l->n_triangles = scene->triangulation_size;
     return l;
 }
+void* model_layout(const ptmi_config* cfg, const ptmi_scene* scene, int* status) { return layout_of(cfg, scene, status, true); }
+// ... and for any scene ptmi_initialize_memory accepts: what it uploads, to be read and never updated
+void* model_layout_uploaded(const ptmi_config* cfg, const ptmi_scene* scene, int* status) { return layout_of(cfg, scene, status, false); }
 void model_layout_free(void* h) { delete static_cast<Layout*>(h); }
 
 // info: n_records, n_triangles, n_big_leaves, root_ref, tris_precomputed, max_depth

@@ -26,6 +26,13 @@ def displaced(tris, seed, amplitude=0.02):
         v = t[name].copy()
         v[:, :3] += rs.uniform(-amplitude, amplitude, (n, 3)).astype(f32)
         t[name] = v
+    follow_vertices(t)
+    return t
+
+
+def follow_vertices(t):
+    """The derived fields of triangles whose vertices were moved in place: N is the unit normal of the new plane on the side it
+    was on, AABB is recompute_aabb's."""
     s1, s2, s3 = t["S1"][:, :3], t["S2"][:, :3], t["S3"][:, :3]
     c = scenes._cross3(s2 - s1, s3 - s1)
     nrm = (c / np.sqrt(scenes._dot3(c, c)).astype(f32)[:, None]).astype(f32)
@@ -35,7 +42,22 @@ def displaced(tris, seed, amplitude=0.02):
     N[:, :3] = nrm
     t["N"] = N
     recompute_aabb(t)
-    return t
+
+
+def moved_triangles(sc, name, seed=7):
+    """The motion of the GPU update tests for scene `name`: every vertex displaced (0.01 on tris20k, else 0.02), and on
+    feat_textured all twelve texture coordinates and the three shading normals as well."""
+    tris = displaced(sc.triangulation, seed, amplitude=0.01 if name == "tris20k" else 0.02)
+    if name == "feat_textured":
+        rs = np.random.default_rng(seed)
+        for field in ("UVP1", "UVP2", "UVP3", "UVN1", "UVN2", "UVN3"):
+            tris[field] = (tris[field] + rs.uniform(-0.3, 0.3, tris[field].shape)).astype(np.float32)
+        for field in ("N1", "N2", "N3"):
+            v = tris[field].copy()
+            v[:, :3] += rs.uniform(-0.2, 0.2, (len(v), 3)).astype(np.float32)
+            v[:, :3] /= np.linalg.norm(v[:, :3], axis=1, keepdims=True).astype(np.float32)
+            tris[field] = v
+    return tris
 
 
 def recompute_aabb(t):

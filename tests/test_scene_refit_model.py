@@ -4,44 +4,25 @@ ptmi_bvh_refit (csrc/scene_refit_host.cpp) recomputes a tree's boxes from its tr
 ptmi_bvh_create's tree byte for byte, with moved ones it must equal a refit written here in numpy.  tests/scene_refit_model.cpp
 runs the device side of ptmi_update_triangles serially, from the same __host__ __device__ header as csrc/scene_refit.hip and on
 the records build_layout makes: its record array must equal, byte for byte, build_layout's for (new triangles, host-refit tree),
-whatever the order in which the lanes of a launch are taken.
+whatever the order in which the lanes of a launch are taken.  The model is built by `make -C oracle probe`
+(oracle/build/libscene_refit_model.so); its wrapper and the scenes are scene_record_cases.py's, shared with the GPU readback.
 """
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
-from opencl_pathtracer_amd import backend, scenes, bvh_create, structs as S
-import bvh_stress_cases as stress
+from opencl_pathtracer_amd import backend
+import scene_record_cases as R
 import scene_update_cases as U
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "opencl_pathtracer_amd", "csrc")
-MODEL_SRCS = [os.path.join(ROOT, "tests", "scene_refit_model.cpp"), os.path.join(CSRC, "scene_refit_host.cpp"),
-              os.path.join(CSRC, "scene_layout.cpp")]
-INCLUDES = ["-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
-FP_FLAGS = ["-ffp-contract=off", "-fno-fast-math"]  # the records' arithmetic is fused only where fmaf says so
-W, H = 64, 48
+W, H = R.W, R.H
 OK, INVALID_ARGUMENT, BAD_SCENE, UNSUPPORTED = 0, -1, -5, -7
 
-SCENES = ["cornell", "tris20k", "fuzz3_l1", "fuzz7_l1", "fuzz12_l1", "big_leaf", "signed_zero-s0", "signed_zero-s1"]
-_cache = {}
-
-
-def scene(name):
-    if name not in _cache:
-        if name == "big_leaf":
-            sc = U.big_leaf_scene(W, H)
-        elif name.startswith("signed_zero"):
-            sc = scenes.cornell_box(W, H)
-            sc.triangulation = stress.make("signed_zero_lattice", int(name[-1]), 16 ** 3)
-        else:
-            sc = scenes.build(name, W, H)
-        _cache[name] = bvh_create(sc)
-    return _cache[name]
+SCENES = R.MODEL_SCENES
+scene = R.scene
 
 
 def node_bytes(bvh):
@@ -142,61 +123,14 @@ def test_refit_refuses_a_broken_tree_and_leaves_it_untouched(lib, fault):
 
 # ---------------------------------------------------------------------------------------------- the device schedule, serially
 
-class Model:
-    def __init__(self, so):
-        m = C.CDLL(so)
-        m.model_layout.restype = C.c_void_p
-        m.model_layout.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-        m.model_layout_free.argtypes = [C.c_void_p]
-        m.model_layout_info.argtypes = [C.c_void_p, C.c_void_p]
-        m.model_layout_copy.argtypes = [C.c_void_p] * 5
-        m.model_update.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
-        m.model_error.restype = C.c_char_p
-        self.m = m
-
-    def layout(self, sc):
-        cfg = backend.Config(C.sizeof(backend.Config), 0, W, H, 4, sc.lightsSize, S.JITTERED, 0, 0)
-        d, keep = backend.scene_desc(sc)
-        rc = C.c_int(0)
-        h = self.m.model_layout(C.addressof(cfg), C.addressof(d), C.byref(rc))
-        assert rc.value == OK and h, self.m.model_error()
-        return h
-
-    def arrays(self, h):
-        info = np.zeros(6, np.uint32)
-        self.m.model_layout_info(h, info.ctypes.data_as(C.c_void_p))
-        n_rec, n_tri, n_big = int(info[0]), int(info[1]), int(info[2])
-        recs, ids = np.zeros((n_rec, 16), np.uint32), np.zeros(n_rec, np.uint32)
-        shade, big = np.zeros((n_tri, 28), np.uint32), np.zeros((max(n_big, 1), 2), np.uint32)
-        self.m.model_layout_copy(h, *[a.ctypes.data_as(C.c_void_p) for a in (recs, ids, shade, big)])
-        return dict(recs=recs, tri_ids=ids, shade=shade, big_leaves=big[:n_big], info=info)
-
-    def update(self, h, tris, order_seed):
-        levels = C.c_uint32(0)
-        tris = np.ascontiguousarray(tris)
-        rc = self.m.model_update(h, tris.ctypes.data_as(C.c_void_p), len(tris), order_seed, C.byref(levels))
-        return rc, self.m.model_error().decode(), levels.value
-
-    def free(self, h):
-        self.m.model_layout_free(h)
-
-
 @pytest.fixture(scope="module")
-def model(tmp_path_factory, built):
-    gxx = shutil.which("g++")
-    if not gxx:
-        pytest.skip("g++ not installed")
-    so = str(tmp_path_factory.mktemp("refit_model") / "libscene_refit_model.so")
-    r = subprocess.run([gxx, "-std=c++17", "-O2", "-fPIC", "-shared", "-Wall", *FP_FLAGS, *INCLUDES, *MODEL_SRCS, "-o", so],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return Model(so)
-
-
-def textured_scene():
-    if "textured" not in _cache:
-        _cache["textured"] = bvh_create(scenes.feature_scene("textured", W, H))
-    return _cache["textured"]
+def model(built):
+    if R.model() is None and not os.path.exists(R.MODEL_LIB):  # (a tree that was never built: as `built` does for the library)
+        subprocess.run(["make", "-s", "-C", os.path.join(R.ROOT, "oracle"), "build/libscene_refit_model.so"], check=True)
+        R._model.clear()
+    if R.model() is None:
+        pytest.fail("oracle/build/libscene_refit_model.so not built (make -C oracle probe)", pytrace=False)
+    return R.model()
 
 
 @pytest.mark.parametrize("generic", [False, True], ids=["precomputed", "generic"])
@@ -204,7 +138,7 @@ def textured_scene():
 def test_model_of_the_device_update_equals_a_fresh_layout(model, lib, monkeypatch, name, generic):
     if generic:
         monkeypatch.setenv("PTMI_GENERIC_TRIANGLES", "1")
-    sc = textured_scene() if name == "textured" else U.with_empty_leaves(scene("cornell")) if name == "empty_leaves" else scene(name)
+    sc = scene(name)
     tris = U.displaced(sc.triangulation, seed=23)
     if name == "textured":
         rs = np.random.default_rng(4)

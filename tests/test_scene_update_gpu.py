@@ -85,17 +85,7 @@ def test_set_camera_with_the_other_kernel_and_with_adaptive_sampling(kw):
 
 def moved_triangles(name, seed=7):
     sc = scene(name)
-    tris = U.displaced(sc.triangulation, seed, amplitude=0.01 if name == "tris20k" else 0.02)
-    if name == "feat_textured":
-        rs = np.random.default_rng(seed)
-        for field in ("UVP1", "UVP2", "UVP3", "UVN1", "UVN2", "UVN3"):
-            tris[field] = (tris[field] + rs.uniform(-0.3, 0.3, tris[field].shape)).astype(np.float32)
-        for field in ("N1", "N2", "N3"):
-            v = tris[field].copy()
-            v[:, :3] += rs.uniform(-0.2, 0.2, (len(v), 3)).astype(np.float32)
-            v[:, :3] /= np.linalg.norm(v[:, :3], axis=1, keepdims=True).astype(np.float32)
-            tris[field] = v
-    return sc, tris
+    return sc, U.moved_triangles(sc, name, seed)
 
 
 UPDATE_CASES = {
