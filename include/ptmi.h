@@ -289,13 +289,28 @@ int ptmi_set_camera(ptmi_ctx* ctx, const ptmi_float4* position, const ptmi_float
 typedef struct ptmi_update_info {
     uint32_t struct_size; /* set by the library: sizeof(ptmi_update_info) */
     uint32_t levels;      /* level passes of the refit (the depth of the inner nodes) */
-    double upload_ms;     /* host -> device copies of the new triangles, all devices */
+    double upload_ms;     /* host -> device copies of the new triangles, all devices (device form: the copies to the other devices) */
     double device_ms;     /* device work behind them (HIP events), all devices */
     double total_ms;      /* the whole call */
-    double validate_ms;   /* the host's checks of the new triangles (and, in the first update, the schedule) */
+    double validate_ms;   /* the checks of the new triangles, on the host or (device form) by the screen kernel with its readback (and, in the first update, the schedule) */
 } ptmi_update_info;
 
 int ptmi_update_triangles(ptmi_ctx* ctx, const ptmi_triangle* triangulation, uint32_t triangulation_size, ptmi_update_info* info);
+
+/* ptmi_update_triangles_device: the same update from triangles that are on the device already - d_triangulation is the address,
+ * on devices[0], of triangulation_size records of ptmi_triangle, 16-byte aligned (a torch tensor's data_ptr(): a mesh skinned,
+ * simulated or deformed on the GPU).  No record crosses the bus.  The checks ptmi_update_triangles makes on the host run as one
+ * kernel on the context's main stream (ptmi_set_stream's, where one was given), one verdict per triangle, and one 32-bit word
+ * comes back: the call's only device-to-host traffic.  Statuses and messages are those of ptmi_update_triangles for the same
+ * records, the index of the refused triangle included, and as there nothing is written after a refusal.
+ * PTMI_ERR_INVALID_ARGUMENT before any device work: d_triangulation NULL or not 16-byte aligned, a count other than the
+ * uploaded one.  The kernels read the caller's buffer in place on devices[0] (a context of one device that uses only this
+ * form never allocates the scratch copy); every other listed device gets a device-to-device copy into its own scratch.
+ * SYNCHRONOUS like the host form: when it returns the work is done on every device and the buffer is no longer read.  The
+ * library reads the buffer on the main stream - the caller orders its own writes before the call - and never writes it.
+ * info: validate_ms is the host checks plus the screen kernel and its readback, upload_ms the device-to-device copies to the
+ * other devices (0 on one device), device_ms and levels as above.  Both forms may be mixed freely on one context. */
+int ptmi_update_triangles_device(ptmi_ctx* ctx, const void* d_triangulation, uint32_t triangulation_size, ptmi_update_info* info);
 
 /* ---- single rays against the loaded scene --------------------------------- */
 

@@ -186,7 +186,7 @@ ABI_SYMBOLS = ["ptmi_setup_context", "ptmi_initialize_memory", "ptmi_render", "p
                "ptmi_set_stream", "ptmi_device_accumulators", "ptmi_bind_accumulators", "ptmi_read_variance",
                "ptmi_device_variance", "ptmi_last_error",
                "ptmi_abi_version", "ptmi_device_count", "ptmi_device_share", "ptmi_bvh_create",
-               "ptmi_bvh_create_device", "ptmi_set_camera", "ptmi_update_triangles", "ptmi_bvh_refit",
+               "ptmi_bvh_create_device", "ptmi_set_camera", "ptmi_update_triangles", "ptmi_update_triangles_device", "ptmi_bvh_refit",
                "ptmi_query_rays", "ptmi_query_rays_device", "ptmi_render_guides", "ptmi_render_guides_device",
                "ptmi_denoise", "ptmi_denoise_device", "ptmi_trace_paths", "ptmi_trace_paths_device",
                "ptmi_reproject_device", "ptmi_set_camera_reprojected",
@@ -269,6 +269,7 @@ def load_library():
     lib.ptmi_bvh_create_device.argtypes = [C.c_int32, vp, u32, vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(BvhBuildInfo)]
     lib.ptmi_set_camera.argtypes = [vp, C.POINTER(Float4), C.POINTER(Float4), C.POINTER(Float4), C.POINTER(Float4)]
     lib.ptmi_update_triangles.argtypes = [vp, vp, u32, C.POINTER(UpdateInfo)]
+    lib.ptmi_update_triangles_device.argtypes = [vp, vp, u32, C.POINTER(UpdateInfo)]
     lib.ptmi_bvh_refit.argtypes = [vp, u32, vp, u32]
     lib.ptmi_query_rays.argtypes = [vp, u32, vp, u32, vp]
     lib.ptmi_query_rays_device.argtypes = [vp, u32, vp, u32, vp]
@@ -455,6 +456,14 @@ class Backend:
             raise PtmiError(-1, "triangulation must have the 336-byte structs.Triangle dtype")
         info = UpdateInfo()
         self._check(self._lib.ptmi_update_triangles(self._ctx, tris.ctypes.data_as(C.c_void_p), len(tris), C.byref(info)))
+        return info.as_dict()
+
+    def update_triangles_device(self, d_triangulation, n_triangles):
+        """The same from ``n_triangles`` 336-byte ``structs.Triangle`` records at device address ``d_triangulation`` on the
+        context's first device (e.g. ``tensor.data_ptr()`` of a float32 (n, 84) tensor, 16-byte aligned): the records are checked
+        and read where they are, none crosses the bus.  Synchronous; the buffer is not written.  Returns the UpdateInfo as a dict."""
+        info = UpdateInfo()
+        self._check(self._lib.ptmi_update_triangles_device(self._ctx, C.c_void_p(d_triangulation), n_triangles, C.byref(info)))
         return info.as_dict()
 
     # -- rays of the caller's own against the loaded scene (no counterpart in the reference) --

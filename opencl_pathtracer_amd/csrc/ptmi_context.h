@@ -38,6 +38,11 @@ struct DeviceScene {
     DScene* d_scene_set[kStageSets] = {};                 // ds with .counters = the set's block
     // ptmi_update_triangles, allocated by the first update of a scene: the caller's new triangles, and the inner records by
     // level (ContextScene::refit)
+    // ptmi_update_triangles_device, devices[0] only, allocated by its first call: what the screen kernel reads of the materials
+    // (UpdateFacts::material_is_simple_color) and the word it answers with.  That form reads the caller's buffer in place on
+    // devices[0], which then needs no d_update_tris
+    uint8_t* d_material_is_simple_color = nullptr;
+    uint32_t* d_screen_verdict = nullptr;
     ptmi_triangle* d_update_tris = nullptr;
     uint32_t* d_refit_nodes = nullptr;
     // Staged radiances [iteration][pixel] float4 (+ one statistics word per path) of the launches in flight: the stage sets of

@@ -11,6 +11,7 @@
 #include "kernel_choice.h"
 #include "ptmi_context.h"
 #include "scene_layout.h"
+#include "scene_refit_common.h"
 
 using namespace ptmi_internal;
 using ptmi_switches::Moment;
@@ -226,6 +227,161 @@ int ptmi_internal::camera_write(ptmi_ctx* ctx, const ptmi_float4& position, cons
     return PTMI_OK;
 }
 
+namespace {
+
+// The screen of the device form: the checks of screen_update as one kernel over the caller's buffer on devices[0]'s main stream,
+// and its one word back.  Nothing of the scene is written.
+int screen_update_on_device(ptmi_ctx* ctx, const ptmi_triangle* d_tris, uint32_t n, uint32_t* word)
+{
+    DeviceState& lead = ctx->dev[0];
+    ON_DEVICE(ctx, lead);
+    const std::vector<uint8_t>& simple = ctx->update.material_is_simple_color;
+    if (!lead.d_material_is_simple_color) {
+        uint8_t* p = nullptr;
+        if (int rc = scene_alloc(ctx, lead, std::max<size_t>(simple.size(), 16), p)) return rc;
+        if (!simple.empty()) HIP_TRY(ctx, hipMemcpy(p, simple.data(), simple.size(), hipMemcpyHostToDevice));
+        lead.d_material_is_simple_color = p;
+    }
+    if (!lead.d_screen_verdict)
+        if (int rc = scene_alloc(ctx, lead, 16, lead.d_screen_verdict)) return rc;
+    std::string err;
+    HIP_TRY(ctx, hipMemsetAsync(lead.d_screen_verdict, 0xFF, 4, lead.stream));  // ptmi_refit::kScreenAccepted
+    if (int rc = launch_screen_update(d_tris, n, lead.d_material_is_simple_color, (uint32_t)simple.size(), ctx->update.tris_precomputed,
+                                      lead.d_screen_verdict, lead.stream, &err))
+        return fail(ctx, rc, err);
+    HIP_TRY(ctx, hipMemcpyAsync(word, lead.d_screen_verdict, 4, hipMemcpyDeviceToHost, lead.stream));
+    HIP_TRY(ctx, hipStreamSynchronize(lead.stream));
+    return PTMI_OK;
+}
+
+// ptmi_update_triangles and ptmi_update_triangles_device: `tris` is host memory, or (device_form) memory of devices[0] that the
+// kernels read in place there.  The two differ in who applies the screen and in how the triangles reach a device; the schedule,
+// the scratch, quiesce and the launches are one.
+int update_triangles(ptmi_ctx* ctx, const char* who_is_calling, bool device_form, const ptmi_triangle* tris, uint32_t triangulation_size,
+                     ptmi_update_info* info)
+{
+    using clock = std::chrono::steady_clock;
+    auto ms_since = [](clock::time_point t) { return std::chrono::duration<double, std::milli>(clock::now() - t).count(); };
+    const clock::time_point t_call = clock::now();
+    const std::string who = who_is_calling, prefix = who + ": ";
+    if (info) {
+        *info = ptmi_update_info{};
+        info->struct_size = sizeof(ptmi_update_info);
+    }
+    if (!ctx) return PTMI_ERR_INVALID_ARGUMENT;
+    if (!tris) return fail(ctx, PTMI_ERR_INVALID_ARGUMENT, prefix + (device_form ? "d_triangulation is NULL" : "triangulation is NULL"));
+    if (device_form && (reinterpret_cast<uintptr_t>(tris) & 15u))
+        return fail(ctx, PTMI_ERR_INVALID_ARGUMENT, prefix + "d_triangulation is not 16-byte aligned");
+    if (int rc = need_scene(ctx, who)) return rc;
+    if (triangulation_size != ctx->update.triangulation_size)
+        return fail(ctx, PTMI_ERR_INVALID_ARGUMENT, prefix + std::to_string(triangulation_size) + " triangles, the context holds " +
+                                                    std::to_string(ctx->update.triangulation_size) + " (the topology cannot change)");
+    if (!ctx->literal_kernel_reason.empty())
+        return fail(ctx, PTMI_ERR_UNSUPPORTED, prefix + "the uploaded scene has records that can yield NaN distances (" +
+                                               ctx->literal_kernel_reason + "): call ptmi_initialize_memory with the new scene");
+    // ---- everything that can refuse, before the first device write
+    {
+        uint32_t word = ptmi_refit::kScreenAccepted;
+        if (device_form) {
+            if (int rc = screen_update_on_device(ctx, tris, triangulation_size, &word)) return rc;
+        } else {
+            word = screen_update_word(ctx->update, tris, triangulation_size);
+        }
+        std::string err;
+        if (int rc = screen_verdict(word, err)) return fail(ctx, rc, prefix + err);
+    }
+    DeviceState& lead = ctx->dev[0];
+    if (!ctx->have_refit) {
+        // the schedule of the refit, from the records as they were uploaded (every device holds the same)
+        ON_DEVICE(ctx, lead);
+        std::vector<DNode> records(lead.ds.n_records);
+        std::vector<uint32_t> tri_ids(lead.ds.n_records);
+        std::vector<DBigLeaf> big_leaves(ctx->update.n_big_leaves);
+        HIP_TRY(ctx, hipStreamSynchronize(lead.stream));
+        if (!records.empty()) {
+            HIP_TRY(ctx, hipMemcpy(records.data(), lead.ds.nodes, records.size() * sizeof(DNode), hipMemcpyDeviceToHost));
+            HIP_TRY(ctx, hipMemcpy(tri_ids.data(), lead.ds.tri_ids, tri_ids.size() * 4, hipMemcpyDeviceToHost));
+        }
+        if (!big_leaves.empty())
+            HIP_TRY(ctx, hipMemcpy(big_leaves.data(), lead.ds.big_leaves, big_leaves.size() * sizeof(DBigLeaf), hipMemcpyDeviceToHost));
+        std::string err;
+        if (int rc = build_refit_schedule(records.data(), tri_ids.data(), lead.ds.n_records, big_leaves.data(), ctx->update.n_big_leaves,
+                                          lead.ds.root_ref, triangulation_size, ctx->refit, err)) {
+            ctx->refit = RefitSchedule();
+            return fail(ctx, rc, prefix + err);
+        }
+        ctx->have_refit = true;
+    }
+    const size_t tri_bytes = (size_t)triangulation_size * sizeof(ptmi_triangle);
+    for (DeviceState& d : ctx->dev) {  // (allocations can refuse too)
+        ON_DEVICE(ctx, d);
+        const bool in_place = device_form && &d == &lead;  // devices[0] reads the caller's buffer where it is
+        if (!d.d_update_tris && !in_place)
+            if (int rc = scene_alloc(ctx, d, std::max<size_t>(tri_bytes, 16), d.d_update_tris)) return rc;
+        if (!d.d_refit_nodes) {
+            uint32_t* p = nullptr;
+            if (int rc = scene_alloc(ctx, d, std::max<size_t>(ctx->refit.nodes.size() * 4, 16), p)) return rc;
+            if (!ctx->refit.nodes.empty())
+                HIP_TRY(ctx, hipMemcpy(p, ctx->refit.nodes.data(), ctx->refit.nodes.size() * 4, hipMemcpyHostToDevice));
+            d.d_refit_nodes = p;
+        }
+    }
+    const double validate_ms = ms_since(t_call);
+    for (DeviceState& d : ctx->dev)
+        if (int rc = quiesce(ctx, d)) return rc;
+    // ---- the update: new triangles to the device, then the records, the shading records and the boxes, level by level from the deepest
+    double upload_ms = 0, device_ms = 0;
+    for (DeviceState& d : ctx->dev) {
+        ON_DEVICE(ctx, d);
+        const ptmi_triangle* d_tris = d.d_update_tris;
+        if (device_form && &d == &lead) {
+            d_tris = tris;
+        } else if (tri_bytes) {
+            // (blocking copies.  The device form's source was last written before the main stream of devices[0] was waited for, in quiesce)
+            const clock::time_point t_upload = clock::now();
+            if (!device_form) HIP_TRY(ctx, hipMemcpy(d.d_update_tris, tris, tri_bytes, hipMemcpyHostToDevice));
+            else if (d.device == lead.device) HIP_TRY(ctx, hipMemcpy(d.d_update_tris, tris, tri_bytes, hipMemcpyDeviceToDevice));
+            else HIP_TRY(ctx, hipMemcpyPeer(d.d_update_tris, d.device, tris, lead.device, tri_bytes));
+            upload_ms += ms_since(t_upload);
+        }
+        hipEvent_t begin = nullptr, end = nullptr;
+        HIP_TRY(ctx, hipEventCreate(&begin));
+        if (hipEventCreate(&end) != hipSuccess) {
+            (void)hipEventDestroy(begin);
+            return fail(ctx, PTMI_ERR_HIP, prefix + "hipEventCreate failed");
+        }
+        std::string err;
+        int rc = hipEventRecord(begin, d.stream) == hipSuccess ? (int)PTMI_OK : (int)PTMI_ERR_HIP;
+        DTri* const records = const_cast<DTri*>(d.ds.tris);
+        if (!rc) rc = launch_update_tri_records(records, d.ds.tri_ids, d.ds.n_records, d_tris, triangulation_size, d.ds.tris_precomputed != 0, d.stream, &err);
+        if (!rc && default_arithmetic(ctx) && d.ds.tris_precomputed)  // the reciprocal determinants of that arithmetic, as at upload
+            rc = launch_precompute_denominators_da(records, d.ds.tri_ids, d.ds.n_records, d.stream, &err);
+        if (!rc) rc = launch_update_shade_records(const_cast<DShade*>(d.ds.shade), d_tris, triangulation_size, d.stream, &err);
+        for (uint32_t level = ctx->refit.levels(); !rc && level-- > 0;)
+            rc = launch_refit_level(const_cast<DNode*>(d.ds.nodes), d.d_refit_nodes + ctx->refit.first[level],
+                                    ctx->refit.first[level + 1] - ctx->refit.first[level], d.ds.big_leaves, d.ds.tri_ids, d_tris, d.stream, &err);
+        hipError_t e = hipEventRecord(end, d.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
+        float ms = 0;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, begin, end);
+        (void)hipEventDestroy(begin);
+        (void)hipEventDestroy(end);
+        if (rc) return fail(ctx, rc, prefix + err);
+        if (e != hipSuccess) return fail(ctx, PTMI_ERR_HIP, prefix + hipGetErrorString(e));
+        device_ms += ms;
+    }
+    if (info) {
+        info->levels = ctx->refit.levels();
+        info->upload_ms = upload_ms;
+        info->device_ms = device_ms;
+        info->validate_ms = validate_ms;
+        info->total_ms = ms_since(t_call);
+    }
+    return PTMI_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int ptmi_initialize_memory(ptmi_ctx* ctx, const ptmi_scene* sc)
@@ -374,105 +530,12 @@ int ptmi_set_camera(ptmi_ctx* ctx, const ptmi_float4* position, const ptmi_float
 
 int ptmi_update_triangles(ptmi_ctx* ctx, const ptmi_triangle* triangulation, uint32_t triangulation_size, ptmi_update_info* info)
 {
-    using clock = std::chrono::steady_clock;
-    auto ms_since = [](clock::time_point t) { return std::chrono::duration<double, std::milli>(clock::now() - t).count(); };
-    const clock::time_point t_call = clock::now();
-    if (info) {
-        *info = ptmi_update_info{};
-        info->struct_size = sizeof(ptmi_update_info);
-    }
-    if (!ctx) return PTMI_ERR_INVALID_ARGUMENT;
-    if (!triangulation) return fail(ctx, PTMI_ERR_INVALID_ARGUMENT, "ptmi_update_triangles: triangulation is NULL");
-    NEED_SCENE(ctx);
-    if (triangulation_size != ctx->update.triangulation_size)
-        return fail(ctx, PTMI_ERR_INVALID_ARGUMENT, "ptmi_update_triangles: " + std::to_string(triangulation_size) + " triangles, the context holds " +
-                                                    std::to_string(ctx->update.triangulation_size) + " (the topology cannot change)");
-    if (!ctx->literal_kernel_reason.empty())
-        return fail(ctx, PTMI_ERR_UNSUPPORTED, "ptmi_update_triangles: the uploaded scene has records that can yield NaN distances (" +
-                                               ctx->literal_kernel_reason + "): call ptmi_initialize_memory with the new scene");
-    // ---- everything that can refuse, before the first device write
-    {
-        std::string err;
-        if (int rc = screen_update(ctx->update, triangulation, triangulation_size, err)) return fail(ctx, rc, "ptmi_update_triangles: " + err);
-    }
-    DeviceState& lead = ctx->dev[0];
-    if (!ctx->have_refit) {
-        // the schedule of the refit, from the records as they were uploaded (every device holds the same)
-        ON_DEVICE(ctx, lead);
-        std::vector<DNode> records(lead.ds.n_records);
-        std::vector<uint32_t> tri_ids(lead.ds.n_records);
-        std::vector<DBigLeaf> big_leaves(ctx->update.n_big_leaves);
-        HIP_TRY(ctx, hipStreamSynchronize(lead.stream));
-        if (!records.empty()) {
-            HIP_TRY(ctx, hipMemcpy(records.data(), lead.ds.nodes, records.size() * sizeof(DNode), hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, hipMemcpy(tri_ids.data(), lead.ds.tri_ids, tri_ids.size() * 4, hipMemcpyDeviceToHost));
-        }
-        if (!big_leaves.empty())
-            HIP_TRY(ctx, hipMemcpy(big_leaves.data(), lead.ds.big_leaves, big_leaves.size() * sizeof(DBigLeaf), hipMemcpyDeviceToHost));
-        std::string err;
-        if (int rc = build_refit_schedule(records.data(), tri_ids.data(), lead.ds.n_records, big_leaves.data(), ctx->update.n_big_leaves,
-                                          lead.ds.root_ref, triangulation_size, ctx->refit, err)) {
-            ctx->refit = RefitSchedule();
-            return fail(ctx, rc, "ptmi_update_triangles: " + err);
-        }
-        ctx->have_refit = true;
-    }
-    for (DeviceState& d : ctx->dev) {  // (allocations can refuse too)
-        ON_DEVICE(ctx, d);
-        if (!d.d_update_tris)
-            if (int rc = scene_alloc(ctx, d, std::max<size_t>((size_t)triangulation_size * sizeof(ptmi_triangle), 16), d.d_update_tris)) return rc;
-        if (!d.d_refit_nodes) {
-            uint32_t* p = nullptr;
-            if (int rc = scene_alloc(ctx, d, std::max<size_t>(ctx->refit.nodes.size() * 4, 16), p)) return rc;
-            if (!ctx->refit.nodes.empty())
-                HIP_TRY(ctx, hipMemcpy(p, ctx->refit.nodes.data(), ctx->refit.nodes.size() * 4, hipMemcpyHostToDevice));
-            d.d_refit_nodes = p;
-        }
-    }
-    const double validate_ms = ms_since(t_call);
-    for (DeviceState& d : ctx->dev)
-        if (int rc = quiesce(ctx, d)) return rc;
-    // ---- the update: new triangles up, then the records, the shading records and the boxes, level by level from the deepest
-    double upload_ms = 0, device_ms = 0;
-    for (DeviceState& d : ctx->dev) {
-        ON_DEVICE(ctx, d);
-        const clock::time_point t_upload = clock::now();
-        HIP_TRY(ctx, hipMemcpy(d.d_update_tris, triangulation, (size_t)triangulation_size * sizeof(ptmi_triangle), hipMemcpyHostToDevice));
-        upload_ms += ms_since(t_upload);
-        hipEvent_t begin = nullptr, end = nullptr;
-        HIP_TRY(ctx, hipEventCreate(&begin));
-        if (hipEventCreate(&end) != hipSuccess) {
-            (void)hipEventDestroy(begin);
-            return fail(ctx, PTMI_ERR_HIP, "ptmi_update_triangles: hipEventCreate failed");
-        }
-        std::string err;
-        int rc = hipEventRecord(begin, d.stream) == hipSuccess ? (int)PTMI_OK : (int)PTMI_ERR_HIP;
-        DTri* const records = const_cast<DTri*>(d.ds.tris);
-        if (!rc) rc = launch_update_tri_records(records, d.ds.tri_ids, d.ds.n_records, d.d_update_tris, triangulation_size, d.ds.tris_precomputed != 0, d.stream, &err);
-        if (!rc && default_arithmetic(ctx) && d.ds.tris_precomputed)  // the reciprocal determinants of that arithmetic, as at upload
-            rc = launch_precompute_denominators_da(records, d.ds.tri_ids, d.ds.n_records, d.stream, &err);
-        if (!rc) rc = launch_update_shade_records(const_cast<DShade*>(d.ds.shade), d.d_update_tris, triangulation_size, d.stream, &err);
-        for (uint32_t level = ctx->refit.levels(); !rc && level-- > 0;)
-            rc = launch_refit_level(const_cast<DNode*>(d.ds.nodes), d.d_refit_nodes + ctx->refit.first[level],
-                                    ctx->refit.first[level + 1] - ctx->refit.first[level], d.ds.big_leaves, d.ds.tri_ids, d.d_update_tris, d.stream, &err);
-        hipError_t e = hipEventRecord(end, d.stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
-        float ms = 0;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, begin, end);
-        (void)hipEventDestroy(begin);
-        (void)hipEventDestroy(end);
-        if (rc) return fail(ctx, rc, "ptmi_update_triangles: " + err);
-        if (e != hipSuccess) return fail(ctx, PTMI_ERR_HIP, std::string("ptmi_update_triangles: ") + hipGetErrorString(e));
-        device_ms += ms;
-    }
-    if (info) {
-        info->levels = ctx->refit.levels();
-        info->upload_ms = upload_ms;
-        info->device_ms = device_ms;
-        info->validate_ms = validate_ms;
-        info->total_ms = ms_since(t_call);
-    }
-    return PTMI_OK;
+    return update_triangles(ctx, "ptmi_update_triangles", false, triangulation, triangulation_size, info);
+}
+
+int ptmi_update_triangles_device(ptmi_ctx* ctx, const void* d_triangulation, uint32_t triangulation_size, ptmi_update_info* info)
+{
+    return update_triangles(ctx, "ptmi_update_triangles_device", true, static_cast<const ptmi_triangle*>(d_triangulation), triangulation_size, info);
 }
 
 }  // extern "C"

@@ -53,11 +53,8 @@ bool texture_ok(const ptmi_texture& t, uint32_t data_size)
 // Returns the reason, or an empty string.
 // The camera's and the lights' part is below; the triangle's part is triangle_needs_literal_kernel (also what an in-place update
 // of the triangles asks, scene_refit_host.cpp).
-constexpr float kCoord = 2097152.0f, kNormal = 16.0f;
-bool within(const ptmi_float4& v, float bound)
-{
-    return std::fabs(v.x) <= bound && std::fabs(v.y) <= bound && std::fabs(v.z) <= bound && std::fabs(v.w) <= bound;  // (false for NaN)
-}
+constexpr float kCoord = ptmi_refit::kScreenCoord;
+bool within(const ptmi_float4& v, float bound) { return ptmi_refit::within4(v, bound); }
 
 std::string scene_needs_literal_kernel(const ptmi_scene* sc)
 {
@@ -82,35 +79,37 @@ std::string camera_needs_literal_kernel(const ptmi_float4& position, const ptmi_
     return std::string();
 }
 
+int screen_refusal(uint32_t code, uint32_t i, std::string& err)
+{
+    if (code == ptmi_refit::kScreenOk) return PTMI_OK;  // (every triangle of every upload passes here: no string is built)
+    const std::string who = "triangle " + std::to_string(i);
+    switch (code) {
+    case ptmi_refit::kScreenMaterial: return fail(err, PTMI_ERR_BAD_SCENE, who + " references a material out of range");
+    case ptmi_refit::kScreenTexCoord: return fail(err, PTMI_ERR_BAD_SCENE, who + " has texture coordinates that are not finite (or beyond 2^30)");
+    case ptmi_refit::kScreenVertex: return fail(err, PTMI_ERR_UNSUPPORTED, who + " has a vertex that is not finite (or beyond 2^21)");
+    case ptmi_refit::kScreenNormal:
+        return fail(err, PTMI_ERR_UNSUPPORTED, who + " has a normal that is not finite (a zero-area triangle of the importer: N = 0/0)");
+    case ptmi_refit::kScreenNoArea:
+        return fail(err, PTMI_ERR_UNSUPPORTED, who + " has no area (its barycentric determinant is zero or not finite)");
+    case ptmi_refit::kScreenUnequalW:
+        return fail(err, PTMI_ERR_UNSUPPORTED, who + " has vertices of unequal w and the uploaded records are of the precomputed form");
+    case ptmi_refit::kScreenEmptyBox: return fail(err, PTMI_ERR_UNSUPPORTED, who + " has a bounding box that is marked empty");
+    case ptmi_refit::kScreenBadBox:
+        return fail(err, PTMI_ERR_UNSUPPORTED, who + " has a bounding box that is not finite with pMin <= pMax");
+    }
+    return fail(err, PTMI_ERR_INTERNAL, who + ": unknown screen code " + std::to_string(code));
+}
+
 std::string triangle_needs_literal_kernel(const ptmi_triangle& t, uint32_t i)
 {
-    if (!within(t.s1, kCoord) || !within(t.s2, kCoord) || !within(t.s3, kCoord))
-        return "triangle " + std::to_string(i) + " has a vertex that is not finite (or beyond 2^21)";
-    if (!within(t.n, kNormal) || !within(t.n1, kNormal) || !within(t.n2, kNormal) || !within(t.n3, kNormal))
-        return "triangle " + std::to_string(i) + " has a normal that is not finite (a zero-area triangle of the importer: N = 0/0)";
-    float u[4], v[4];
-    ptmi_refit::triangle_edges(t, u, v);
-    const float uv = ptmi_refit::dot4(u, v), uu = ptmi_refit::dot4(u, u), vv = ptmi_refit::dot4(v, v);
-    const float det[2] = {uv * uv - uu * vv, std::fmaf(uv, uv, -(uu * vv))};  // cl:556, strict and default arithmetic
-    for (float d : det)
-        if (!(d != 0.0f) || !std::isfinite(d) || !std::isfinite(1.0f / d))
-            return "triangle " + std::to_string(i) + " has no area (its barycentric determinant is zero or not finite)";
-    return std::string();
+    std::string why;
+    (void)screen_refusal(ptmi_refit::screen_literal(t), i, why);
+    return why;
 }
 
 int check_triangle_materials(const ptmi_triangle& t, uint32_t i, const uint8_t* material_is_simple_color, uint32_t materiaux_size, std::string& err)
 {
-    if (t.mat_pos >= materiaux_size || t.mat_neg >= materiaux_size)
-        return fail(err, PTMI_ERR_BAD_SCENE, "triangle " + std::to_string(i) + " references a material out of range");
-    if (!material_is_simple_color[t.mat_pos] || !material_is_simple_color[t.mat_neg]) {
-        // texture coordinates index texels (header.cl:430-459: u - (int)u, then (uint)(u * (width - 1))): beyond the int range the
-        // wrap does nothing and the index leaves the texture - in the reference as well, which reads whatever is there
-        const float* uv = reinterpret_cast<const float*>(&t.uvp1);
-        for (int k = 0; k < 12; k++)
-            if (!(std::fabs(uv[k]) <= 0x1p+30f))
-                return fail(err, PTMI_ERR_BAD_SCENE, "triangle " + std::to_string(i) + " has texture coordinates that are not finite (or beyond 2^30)");
-    }
-    return PTMI_OK;
+    return screen_refusal(ptmi_refit::screen_materials(t, material_is_simple_color, materiaux_size), i, err);
 }
 
 int build_layout(const ptmi_config& cfg, const ptmi_scene* sc, Relayout& out, std::string& err)

@@ -37,6 +37,10 @@ struct Relayout {
 // The per-record parts of the validation, which an in-place update applies to new cameras and triangles (scene_refit_host.cpp):
 // why the camera / triangle `i` can make a triangle test compute a NaN distance (empty: it cannot; scene_layout.cpp:
 // scene_needs_literal_kernel), and whether the triangle's materials exist and its texture coordinates can index texels.
+// The triangle's two are callers of the one classification the device shares (scene_refit_common.h: ScreenCode), and
+// screen_refusal is its formatter: the status and the words for code `code` on triangle `i` (PTMI_OK and `err` untouched for
+// kScreenOk).
+int screen_refusal(uint32_t code, uint32_t i, std::string& err);
 std::string camera_needs_literal_kernel(const ptmi_float4& position, const ptmi_float4& direction, const ptmi_float4& right, const ptmi_float4& up);
 std::string triangle_needs_literal_kernel(const ptmi_triangle& t, uint32_t i);
 int check_triangle_materials(const ptmi_triangle& t, uint32_t i, const uint8_t* material_is_simple_color, uint32_t materiaux_size, std::string& err);

@@ -24,6 +24,11 @@ struct UpdateFacts {
 // that could yield NaN distances (the kernel instantiation was chosen at upload), unequal w where the records are DTriPre, an
 // aabb that is marked empty, not finite or not ordered (the references' empty flags and boxes_ordered are upload-time facts).
 int screen_update(const UpdateFacts& facts, const ptmi_triangle* triangulation, uint32_t triangulation_size, std::string& err);
+// ... in its two halves, which the device form shares (scene_refit_common.h: ScreenCode, one classification for host and device):
+// the verdict on the whole array as one word - (index << 4) | code of the first refused triangle, or kScreenAccepted - and the
+// status and message of such a word, whoever computed it (the loop here, or the screen kernel below).
+uint32_t screen_update_word(const UpdateFacts& facts, const ptmi_triangle* triangulation, uint32_t triangulation_size);
+int screen_verdict(uint32_t word, std::string& err);
 
 // The inner records of the one record array by depth (root = level 0): level k is nodes[first[k] .. first[k + 1]).  A level pass
 // of the refit reads the records of the level below and writes its own, so the passes run from the last level to level 0.
@@ -41,6 +46,11 @@ int build_refit_schedule(const DNode* records, const uint32_t* tri_ids, uint32_t
                          uint32_t n_big_leaves, uint32_t root_ref, uint32_t triangulation_size, RefitSchedule& out, std::string& err);
 
 // ---- scene_refit.hip: every launch is asynchronous on `stream`; the caller's bounds are the schedule's ---------------------
+// The screen on the device (ptmi_update_triangles_device): *verdict = min(*verdict, the word of every refused triangle of
+// triangulation[0 .. triangulation_size)), so a word the caller has set to kScreenAccepted ends as screen_update_word's.
+// material_is_simple_color: one byte per material, on the device.  Reads the triangles, writes the one word.
+int launch_screen_update(const ptmi_triangle* triangulation, uint32_t triangulation_size, const uint8_t* material_is_simple_color,
+                         uint32_t materiaux_size, bool tris_precomputed, uint32_t* verdict, void* stream, std::string* err);
 // records[r] = the DTri (or DTriPre, strict reciprocal) record of triangulation[tri_ids[r]] where tri_ids[r] < triangulation_size
 // (a node record's is 0xFFFFFFFF)
 int launch_update_tri_records(DTri* records, const uint32_t* tri_ids, uint32_t n_records, const ptmi_triangle* triangulation,

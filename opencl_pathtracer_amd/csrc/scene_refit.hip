@@ -3,6 +3,8 @@
 // value comes from scene_refit_common.h, the header the host's upload path and the serial model (tests/scene_refit_model.cpp)
 // compute it from.  No atomics, nothing shared between lanes: a lane reads the caller's triangles and, in a level pass, records
 // of the level below (written by an earlier launch), and writes the one record that is its own, as whole 16-byte words.
+// In front of them, for ptmi_update_triangles_device alone, the screen kernel: the host's checks of the new triangles, one lane
+// per triangle, answered in one word (at most one atomicMin per wave that refuses, none in a good update).
 #include <hip/hip_runtime.h>
 
 #include "scene_refit.h"
@@ -63,9 +65,37 @@ __global__ void __launch_bounds__(kBlock) refit_level_kernel(DNode* records, con
     store_words<4>(mine, &d);
 }
 
+// The screen of ptmi_update_triangles_device: one lane per triangle, one verdict each (scene_refit_common.h: screen_triangle, the
+// host loop's own function), and of all refusals the smallest word (index << 4) | code into *verdict, which the host set to
+// kScreenAccepted.  A lane's word grows with its lane number, so a wave's smallest is its first refusing lane's: that lane issues
+// the wave's one atomic, and a wave without a refusal - every wave of a good update - issues none.  Lanes past n take part in the
+// ballot with no refusal and read nothing.
+__global__ void __launch_bounds__(kBlock) screen_update_kernel(const ptmi_triangle* __restrict__ tris, const uint32_t n_tris,
+                                                               const uint8_t* __restrict__ material_is_simple_color,
+                                                               const uint32_t materiaux_size, const uint32_t tris_precomputed,
+                                                               uint32_t* __restrict__ verdict)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    uint32_t code = ptmi_refit::kScreenOk;
+    if (i < n_tris) code = ptmi_refit::screen_triangle(tris[i], material_is_simple_color, materiaux_size, tris_precomputed != 0);
+    const unsigned long long refusing = __ballot(code != ptmi_refit::kScreenOk);
+    if (refusing == 0) return;
+    const uint32_t lane = __lane_id();
+    if (lane == (uint32_t)__ffsll(refusing) - 1u) atomicMin(verdict, ptmi_refit::screen_word(i, code));
+}
+
 dim3 grid_for(uint32_t n) { return dim3((n + kBlock - 1) / kBlock); }
 
 }  // namespace
+
+int launch_screen_update(const ptmi_triangle* triangulation, uint32_t triangulation_size, const uint8_t* material_is_simple_color,
+                         uint32_t materiaux_size, bool tris_precomputed, uint32_t* verdict, void* stream, std::string* err)
+{
+    if (triangulation_size == 0) return PTMI_OK;
+    hipLaunchKernelGGL(screen_update_kernel, grid_for(triangulation_size), dim3(kBlock), 0, (hipStream_t)stream, triangulation,
+                       triangulation_size, material_is_simple_color, materiaux_size, tris_precomputed ? 1u : 0u, verdict);
+    return launch_status(hipGetLastError(), "screen_update_kernel", err);
+}
 
 int launch_update_tri_records(DTri* records, const uint32_t* tri_ids, uint32_t n_records, const ptmi_triangle* triangulation,
                               uint32_t triangulation_size, bool tris_precomputed, void* stream, std::string* err)

@@ -1,7 +1,9 @@
 // scene_refit_common.h - the arithmetic of an in-place scene update, shared by the host (scene_layout.cpp, scene_refit_host.cpp),
 // the device (scene_refit.hip) and the serial model of the device schedule (tests/scene_refit_model.cpp).
 //
-// Two things live here, once:
+// Three things live here, once:
+//   * the screen of a new triangle - why build_layout or an in-place update refuses it, as a small code (ScreenCode) - for the
+//     host loops and for the screen kernel of ptmi_update_triangles_device (tests/update_screen_model.cpp runs it on its own);
 //   * a triangle's device records (DTri / DTriPre / DShade) as build_layout writes them at upload, so that a record rewritten on
 //     the device holds the bytes a fresh upload of the same triangle would;
 //   * the refit of a box from the boxes below it: a leaf's box is the fold of its triangles' `aabb` in ascending index order
@@ -85,6 +87,83 @@ PTMI_HD void make_shade_record(const ptmi_triangle& t, DShade* s)
     s->mat_pos = t.mat_pos;
     s->mat_neg = t.mat_neg;
     s->pad[0] = s->pad[1] = 0;
+}
+
+// ---- the screen ------------------------------------------------------------------------------------------------------------
+
+// Why one triangle is refused, as a small code: what build_layout asks of every triangle (scene_layout.cpp: its materials and
+// texture coordinates, and whether its record can make a triangle test compute a NaN distance) and what an in-place update
+// asks on top (scene_refit.h: screen_update).  One copy for the host loops and for the screen kernel of
+// ptmi_update_triangles_device (scene_refit.hip), so that both give one verdict for one record.  The codes are in the order of
+// the checks: of a triangle with several defects the smallest one is reported.  Words come from scene_layout.cpp:
+// screen_message.
+enum ScreenCode : uint32_t {
+    kScreenOk = 0,
+    kScreenMaterial = 1,   // a material index out of range                                  (PTMI_ERR_BAD_SCENE)
+    kScreenTexCoord = 2,   // a textured material, and a texture coordinate not finite or beyond 2^30          (PTMI_ERR_BAD_SCENE)
+    kScreenVertex = 3,     // a vertex not finite or beyond 2^21                       (PTMI_ERR_UNSUPPORTED, and all that follow)
+    kScreenNormal = 4,     // n, n1, n2 or n3 not finite or beyond 16
+    kScreenNoArea = 5,     // a barycentric determinant (cl:556, either arithmetic) zero, not finite, or without a finite reciprocal
+    kScreenUnequalW = 6,   // unequal w where the uploaded records are DTriPre
+    kScreenEmptyBox = 7,   // aabb marked empty
+    kScreenBadBox = 8,     // aabb not finite with pMin <= pMax (the centroid included)
+};
+// The verdict on a whole array in one word: (index << 4) | code of the first refused triangle (an index is below 2^27), or
+// kScreenAccepted.  The smallest word of all refused triangles is the first one's.
+constexpr uint32_t kScreenAccepted = 0xFFFFFFFFu;
+PTMI_HD uint32_t screen_word(uint32_t index, uint32_t code) { return (index << 4) | code; }
+
+constexpr float kScreenCoord = 2097152.0f, kScreenNormalBound = 16.0f, kScreenTexCoordBound = 1073741824.0f;
+
+PTMI_HD bool within4(const ptmi_float4& v, float bound)
+{
+    return std::fabs(v.x) <= bound && std::fabs(v.y) <= bound && std::fabs(v.z) <= bound && std::fabs(v.w) <= bound;  // (false for NaN)
+}
+PTMI_HD bool within2(const ptmi_float2& v, float bound) { return std::fabs(v.x) <= bound && std::fabs(v.y) <= bound; }
+
+// Texture coordinates index texels (header.cl:430-459: u - (int)u, then (uint)(u * (width - 1))): beyond the int range the wrap
+// does nothing and the index leaves the texture - in the reference as well, which reads whatever is there.
+PTMI_HD uint32_t screen_materials(const ptmi_triangle& t, const uint8_t* material_is_simple_color, uint32_t materiaux_size)
+{
+    if (t.mat_pos >= materiaux_size || t.mat_neg >= materiaux_size) return kScreenMaterial;
+    if (!material_is_simple_color[t.mat_pos] || !material_is_simple_color[t.mat_neg])
+        if (!(within2(t.uvp1, kScreenTexCoordBound) && within2(t.uvp2, kScreenTexCoordBound) && within2(t.uvp3, kScreenTexCoordBound) &&
+              within2(t.uvn1, kScreenTexCoordBound) && within2(t.uvn2, kScreenTexCoordBound) && within2(t.uvn3, kScreenTexCoordBound)))
+            return kScreenTexCoord;
+    return kScreenOk;
+}
+
+PTMI_HD bool determinant_is_usable(float d) { return d != 0.0f && std::isfinite(d) && std::isfinite(1.0f / d); }
+
+// Can this triangle's record make a triangle test compute a NaN distance (scene_layout.cpp: scene_needs_literal_kernel)?
+PTMI_HD uint32_t screen_literal(const ptmi_triangle& t)
+{
+    if (!within4(t.s1, kScreenCoord) || !within4(t.s2, kScreenCoord) || !within4(t.s3, kScreenCoord)) return kScreenVertex;
+    if (!within4(t.n, kScreenNormalBound) || !within4(t.n1, kScreenNormalBound) || !within4(t.n2, kScreenNormalBound) ||
+        !within4(t.n3, kScreenNormalBound))
+        return kScreenNormal;
+    float u[4], v[4];
+    triangle_edges(t, u, v);
+    const float uv = dot4(u, v), uu = dot4(u, u), vv = dot4(v, v);
+    // cl:556, strict and default arithmetic
+    if (!determinant_is_usable(uv * uv - uu * vv) || !determinant_is_usable(fmaf(uv, uv, -(uu * vv)))) return kScreenNoArea;
+    return kScreenOk;
+}
+
+PTMI_HD bool box_axis_ok(float lo, float hi, float c) { return std::isfinite(lo) && std::isfinite(hi) && std::isfinite(c) && lo <= hi; }
+
+// The whole screen of one triangle of an update: the first failing check, in the order of the codes.
+PTMI_HD uint32_t screen_triangle(const ptmi_triangle& t, const uint8_t* material_is_simple_color, uint32_t materiaux_size, bool tris_precomputed)
+{
+    if (const uint32_t code = screen_materials(t, material_is_simple_color, materiaux_size)) return code;
+    if (const uint32_t code = screen_literal(t)) return code;
+    if (tris_precomputed && !triangle_keeps_equal_w(t)) return kScreenUnequalW;
+    const ptmi_bounding_box& a = t.aabb;
+    if (a.is_empty) return kScreenEmptyBox;
+    if (!(box_axis_ok(a.p_min.x, a.p_max.x, a.centroid.x) && box_axis_ok(a.p_min.y, a.p_max.y, a.centroid.y) &&
+          box_axis_ok(a.p_min.z, a.p_max.z, a.centroid.z)))
+        return kScreenBadBox;
+    return kScreenOk;
 }
 
 // ---- refit --------------------------------------------------------------------------------------------------------------

@@ -22,27 +22,26 @@ const char* const kReinitialise = ": an update cannot express that, call ptmi_in
 
 }  // namespace
 
+int screen_verdict(uint32_t word, std::string& err)
+{
+    if (word == ptmi_refit::kScreenAccepted) return PTMI_OK;
+    const int rc = screen_refusal(word & 15u, word >> 4, err);
+    if (rc == PTMI_ERR_UNSUPPORTED) err += kReinitialise;
+    return rc;
+}
+
+uint32_t screen_update_word(const UpdateFacts& facts, const ptmi_triangle* triangulation, uint32_t triangulation_size)
+{
+    for (uint32_t i = 0; i < triangulation_size; i++)
+        if (const uint32_t code = ptmi_refit::screen_triangle(triangulation[i], facts.material_is_simple_color.data(),
+                                                              (uint32_t)facts.material_is_simple_color.size(), facts.tris_precomputed))
+            return ptmi_refit::screen_word(i, code);
+    return ptmi_refit::kScreenAccepted;
+}
+
 int screen_update(const UpdateFacts& facts, const ptmi_triangle* triangulation, uint32_t triangulation_size, std::string& err)
 {
-    for (uint32_t i = 0; i < triangulation_size; i++) {
-        const ptmi_triangle& t = triangulation[i];
-        if (int rc = check_triangle_materials(t, i, facts.material_is_simple_color.data(), (uint32_t)facts.material_is_simple_color.size(), err))
-            return rc;
-        const std::string why = triangle_needs_literal_kernel(t, i);
-        if (!why.empty()) return fail(err, PTMI_ERR_UNSUPPORTED, why + kReinitialise);
-        if (facts.tris_precomputed && !ptmi_refit::triangle_keeps_equal_w(t))
-            return fail(err, PTMI_ERR_UNSUPPORTED, "triangle " + std::to_string(i) + " has vertices of unequal w and the uploaded records are of the "
-                                                   "precomputed form" + kReinitialise);
-        const ptmi_bounding_box& a = t.aabb;
-        if (a.is_empty)
-            return fail(err, PTMI_ERR_UNSUPPORTED, "triangle " + std::to_string(i) + " has a bounding box that is marked empty" + kReinitialise);
-        const float lo[3] = {a.p_min.x, a.p_min.y, a.p_min.z}, hi[3] = {a.p_max.x, a.p_max.y, a.p_max.z};
-        const float c[3] = {a.centroid.x, a.centroid.y, a.centroid.z};
-        for (int k = 0; k < 3; k++)
-            if (!(std::isfinite(lo[k]) && std::isfinite(hi[k]) && std::isfinite(c[k]) && lo[k] <= hi[k]))
-                return fail(err, PTMI_ERR_UNSUPPORTED, "triangle " + std::to_string(i) + " has a bounding box that is not finite with pMin <= pMax" + kReinitialise);
-    }
-    return PTMI_OK;
+    return screen_verdict(screen_update_word(facts, triangulation, triangulation_size), err);
 }
 
 int build_refit_schedule(const DNode* records, const uint32_t* tri_ids, uint32_t n_records, const DBigLeaf* big_leaves,

@@ -3,6 +3,9 @@
 Every vertex is displaced by a small seeded offset (normals and boxes recomputed); then, each as the median of --reps warm calls:
 
   update_ms            ptmi_update_triangles (with its ptmi_update_info: checks, upload, device work)
+  update_device_ms     ptmi_update_triangles_device from a torch tensor that holds the same displaced records (with its info:
+                       there validate_ms is the host checks, the screen kernel and its one word back, upload_ms is 0 on one
+                       device); the two forms alternate inside one loop, so that both see the same machine
   host_refit_ms        ptmi_bvh_refit of the caller's tree
   init_refit_tree_ms   ptmi_initialize_memory of (new triangles, that tree) - what the update replaces
   rebuild_ms           ptmi_bvh_create_device + ptmi_initialize_memory - a new tree for the new triangles
@@ -68,6 +71,26 @@ def median_of(reps, fn):
     return round(runs[k][0], 3), [round(r[0], 3) for r in runs], runs[k][1]
 
 
+def alternating(reps, fns):
+    """Per function (median wall ms, all wall ms, the median call's result): one warm-up call each, then `reps` rounds in which
+    the functions take turns."""
+    for fn in fns:
+        fn()
+    runs = [[] for _ in fns]
+    for _ in range(reps):
+        for k, fn in enumerate(fns):
+            runs[k].append(timed(fn))
+    out = []
+    for r in runs:
+        k = int(np.argsort([x[0] for x in r])[len(r) // 2])
+        out.append((round(r[k][0], 3), [round(x[0], 3) for x in r], r[k][1]))
+    return out
+
+
+def rounded(info):
+    return {k: (round(v, 3) if isinstance(v, float) else v) for k, v in info.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", default="tris20k,tris1m,mayalike")
@@ -75,6 +98,8 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    import torch
+    torch.cuda.init()  # (before the library's first device call: torch's runtime does not find the device after it)
     records = []
     for name in a.scenes.split(","):
         sc = bvh_create(scenes.build(name, W, H), device=a.device)
@@ -90,9 +115,20 @@ def main():
             try:
                 rec["first_update_ms"], first = timed(lambda: be.update_triangles(tris))
                 rec["first_update_ms"] = round(rec["first_update_ms"], 3)
-                rec["first_update_info"] = {k: (round(v, 3) if isinstance(v, float) else v) for k, v in first.items()}
-                rec["update_ms"], rec["update_ms_all"], info = median_of(a.reps, lambda: be.update_triangles(tris))
-                rec["update_info"] = {k: (round(v, 3) if isinstance(v, float) else v) for k, v in info.items()}
+                rec["first_update_info"] = rounded(first)
+                d_tris = torch.from_numpy(np.ascontiguousarray(tris).view(np.uint8).reshape(len(tris), 336).view(np.float32)).to(f"cuda:{a.device}")
+                torch.cuda.synchronize()
+                rec["first_update_device_ms"], first = timed(lambda: be.update_triangles_device(d_tris.data_ptr(), len(tris)))
+                rec["first_update_device_ms"] = round(rec["first_update_device_ms"], 3)
+                rec["first_update_device_info"] = rounded(first)
+                host, dev = alternating(a.reps, [lambda: be.update_triangles(tris), lambda: be.update_triangles_device(d_tris.data_ptr(), len(tris))])
+                rec["update_ms"], rec["update_ms_all"], rec["update_info"] = host[0], host[1], rounded(host[2])
+                rec["update_device_ms"], rec["update_device_ms_all"], rec["update_device_info"] = dev[0], dev[1], rounded(dev[2])
+                rec["update_vs_update_device"] = round(rec["update_ms"] / rec["update_device_ms"], 2)
+                # the bytes the screen must read, at the 6.3 TB/s a float4 copy reaches (profiles/): the floor of its validate_ms
+                rec["screen_floor_ms"] = round(336 * len(tris) / 6.3e12 * 1e3, 5)
+                rec["screen_vs_floor"] = round(rec["update_device_info"]["validate_ms"] / rec["screen_floor_ms"], 1)
+                del d_tris
                 be.clear()
                 be.render(0, 2)
                 updated = be.read_image()[0].view(np.uint32).copy()
@@ -127,10 +163,10 @@ def main():
             be.release()
         print(json.dumps(rec), flush=True)
         records.append(rec)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(records, f, indent=1)
+        if a.out:  # (after every scene: a long run that is cut short keeps what it has measured)
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(records, f, indent=1)
 
 
 if __name__ == "__main__":
