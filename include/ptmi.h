@@ -312,6 +312,44 @@ int ptmi_update_triangles(ptmi_ctx* ctx, const ptmi_triangle* triangulation, uin
  * other devices (0 on one device), device_ms and levels as above.  Both forms may be mixed freely on one context. */
 int ptmi_update_triangles_device(ptmi_ctx* ctx, const void* d_triangulation, uint32_t triangulation_size, ptmi_update_info* info);
 
+/* Materials, lights and sky of the loaded scene, edited in place: what a look-development session changes between renders.
+ * The three calls below follow the contract of ptmi_set_camera and ptmi_update_triangles above, word for word: an initialised
+ * context (PTMI_ERR_STATE otherwise), every check before the first device write (after any error the context renders the scene
+ * it held), launches rendered ahead dropped and the streams waited for, every listed device updated, nothing that has been
+ * rendered touched.  Afterwards the context holds what ptmi_initialize_memory would upload for the edited scene: a render after
+ * ptmi_clear is bit-equal to a fresh context's.  The numbers of materials, lights and textures and the texels stay the
+ * uploaded ones.
+ *
+ * ptmi_update_materials: materiaux[k] replaces material first + k, k < n.  first + n beyond the uploaded count, or NULL with
+ * n > 0: PTMI_ERR_INVALID_ARGUMENT; n == 0 does nothing.  The checks are ptmi_initialize_memory's, in its order and with its
+ * words (status and message are ptmi_validate_scene's for the edited scene): a textured material whose texture_id is outside
+ * the uploaded textures, then - only where a material of the range is textured now and was a plain colour before - the
+ * texture coordinates of the triangles that use a textured material, which must be finite and at most 2^30: PTMI_ERR_BAD_SCENE.
+ * That second check reads the shading records the context holds on devices[0], one kernel on the main stream and one word
+ * back; no triangle crosses the bus.  The kernel instantiation follows the edit: a scene whose materials are all plain-colour
+ * PTMI_MAT_STANDART and whose lights are all PTMI_LIGHT_POINT renders with the plain one, any other with the general one
+ * (plain_before, plain_after).  `info` may be NULL. */
+typedef struct ptmi_material_update_info {
+    uint32_t struct_size;        /* set by the library: sizeof(ptmi_material_update_info) */
+    uint32_t screened_triangles; /* triangles the device screen looked at: 0 where it did not run */
+    uint32_t plain_before, plain_after; /* 1: every material a plain-colour MAT_STANDART, every light a point light - around the call */
+    double validate_ms; /* the checks, the screen kernel and its readback included */
+    double total_ms;    /* the whole call */
+} ptmi_material_update_info;
+
+int ptmi_update_materials(ptmi_ctx* ctx, uint32_t first, const ptmi_material* materiaux, uint32_t n, ptmi_material_update_info* info);
+
+/* ptmi_update_lights: the whole light array anew.  lights_size must be config.lights_size (LIGHTS_SIZE is baked at setup):
+ * PTMI_ERR_INVALID_ARGUMENT otherwise.  PTMI_ERR_UNSUPPORTED, scene untouched, where a light's position or direction is not
+ * finite or beyond 2^21 (it would give the scene a ptmi_literal_kernel_reason, as a camera would: ptmi_set_camera) and where
+ * the scene has such a reason already (it may be a light's).  A spot or directional light leaves the plain instantiation; a
+ * scene whose lights are all point lights again goes back to it. */
+int ptmi_update_lights(ptmi_ctx* ctx, const ptmi_light* lights, uint32_t lights_size);
+
+/* ptmi_set_sky: the sky record anew - rotation, ground scale, exposure factors and the six face descriptors, each of which
+ * must lie inside the uploaded textures_data (PTMI_ERR_BAD_SCENE otherwise, as at upload). */
+int ptmi_set_sky(ptmi_ctx* ctx, const ptmi_sky* sky);
+
 /* ---- single rays against the loaded scene --------------------------------- */
 
 /* Rays of the caller's own, traced against the geometry the context holds NOW (after any ptmi_update_triangles): viewport

@@ -87,6 +87,15 @@ class UpdateInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class MaterialUpdateInfo(C.Structure):
+    """ptmi_material_update_info: what ptmi_update_materials did (whether its device screen ran, and the plain-shading flip)."""
+    _fields_ = [("struct_size", C.c_uint32), ("screened_triangles", C.c_uint32), ("plain_before", C.c_uint32),
+                ("plain_after", C.c_uint32), ("validate_ms", C.c_double), ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class Guides(C.Structure):
     """ptmi_guides: the planes ptmi_render_guides fills (host or device addresses; None = not written)."""
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("albedo", C.c_void_p), ("normal", C.c_void_p),
@@ -187,6 +196,7 @@ ABI_SYMBOLS = ["ptmi_setup_context", "ptmi_initialize_memory", "ptmi_render", "p
                "ptmi_device_variance", "ptmi_last_error",
                "ptmi_abi_version", "ptmi_device_count", "ptmi_device_share", "ptmi_bvh_create",
                "ptmi_bvh_create_device", "ptmi_set_camera", "ptmi_update_triangles", "ptmi_update_triangles_device", "ptmi_bvh_refit",
+               "ptmi_update_materials", "ptmi_update_lights", "ptmi_set_sky",
                "ptmi_query_rays", "ptmi_query_rays_device", "ptmi_render_guides", "ptmi_render_guides_device",
                "ptmi_denoise", "ptmi_denoise_device", "ptmi_trace_paths", "ptmi_trace_paths_device",
                "ptmi_reproject_device", "ptmi_set_camera_reprojected",
@@ -270,6 +280,9 @@ def load_library():
     lib.ptmi_set_camera.argtypes = [vp, C.POINTER(Float4), C.POINTER(Float4), C.POINTER(Float4), C.POINTER(Float4)]
     lib.ptmi_update_triangles.argtypes = [vp, vp, u32, C.POINTER(UpdateInfo)]
     lib.ptmi_update_triangles_device.argtypes = [vp, vp, u32, C.POINTER(UpdateInfo)]
+    lib.ptmi_update_materials.argtypes = [vp, u32, vp, u32, C.POINTER(MaterialUpdateInfo)]
+    lib.ptmi_update_lights.argtypes = [vp, vp, u32]
+    lib.ptmi_set_sky.argtypes = [vp, vp]
     lib.ptmi_bvh_refit.argtypes = [vp, u32, vp, u32]
     lib.ptmi_query_rays.argtypes = [vp, u32, vp, u32, vp]
     lib.ptmi_query_rays_device.argtypes = [vp, u32, vp, u32, vp]
@@ -465,6 +478,33 @@ class Backend:
         info = UpdateInfo()
         self._check(self._lib.ptmi_update_triangles_device(self._ctx, C.c_void_p(d_triangulation), n_triangles, C.byref(info)))
         return info.as_dict()
+
+    def update_materials(self, first, materiaux):
+        """``materiaux`` (a ``structs.Material`` array) replace the materials from index ``first`` on; their number stays.  The
+        checks are initialize_memory's; a material that turns textured has its triangles' texture coordinates checked on the
+        device.  Returns the MaterialUpdateInfo as a dict.  What has been rendered stays: call clear() for a fresh image."""
+        mats = np.ascontiguousarray(materiaux).reshape(-1)
+        if mats.dtype != S.Material:
+            raise PtmiError(-1, "materiaux must have the 48-byte structs.Material dtype")
+        info = MaterialUpdateInfo()
+        self._check(self._lib.ptmi_update_materials(self._ctx, first, mats.ctypes.data_as(C.c_void_p), len(mats), C.byref(info)))
+        return info.as_dict()
+
+    def update_lights(self, lights):
+        """The whole light array anew (a ``structs.Light`` array of the ``lights_size`` the context was set up with).  What has
+        been rendered stays: call clear() for a fresh image."""
+        lights = np.ascontiguousarray(lights).reshape(-1)
+        if lights.dtype != S.Light:
+            raise PtmiError(-1, "lights must have the 64-byte structs.Light dtype")
+        self._check(self._lib.ptmi_update_lights(self._ctx, lights.ctypes.data_as(C.c_void_p), len(lights)))
+
+    def set_sky(self, sky):
+        """A new sky record (``structs.Sky``): rotation, scales and the six faces, which must lie inside the uploaded texels.
+        What has been rendered stays: call clear() for a fresh image."""
+        sky = np.ascontiguousarray(sky).reshape(-1)
+        if sky.dtype != S.Sky or len(sky) != 1:
+            raise PtmiError(-1, "sky must be one record of the 92-byte structs.Sky dtype")
+        self._check(self._lib.ptmi_set_sky(self._ctx, sky.ctypes.data_as(C.c_void_p)))
 
     # -- rays of the caller's own against the loaded scene (no counterpart in the reference) --
     def query_rays(self, origins, directions, max_squared_distance=None, any_hit=False, out=None):

@@ -42,6 +42,21 @@ struct ContextTraits {
 inline bool tris_precomputed_after_switch(bool scene_allows, const Switches& upload) { return scene_allows && !upload.generic_triangles; }
 inline bool plain_shading_after_switch(bool scene_allows, const Switches& upload) { return scene_allows && !upload.generic_shading; }
 
+// DScene::plain_shading of a scene: every material a plain-colour PTMI_MAT_STANDART and every light a PTMI_LIGHT_POINT, unless
+// switched off.  One per entry of the arrays: a material's type and whether it is a plain colour, a light's type - what
+// build_layout reads off the caller's records (scene_layout.cpp) and what a context keeps of them, so that an edit of the
+// materials or the lights (ptmi_update_materials, ptmi_update_lights) asks the upload's own rule again.
+inline bool scene_plain_shading(const int32_t* material_type, const uint8_t* material_is_simple_color, size_t n_materials,
+                                const int32_t* light_type, size_t n_lights, const Switches& upload)
+{
+    bool plain = plain_shading_after_switch(true, upload);
+    for (size_t i = 0; i < n_materials && plain; i++)
+        if (material_type[i] != PTMI_MAT_STANDART || !material_is_simple_color[i]) plain = false;
+    for (size_t i = 0; i < n_lights && plain; i++)
+        if (light_type[i] != PTMI_LIGHT_POINT) plain = false;
+    return plain;
+}
+
 // PTMI_LEAF_CULL as the context keeps it: 0, 1, 2 or 3 (anything else reads as 1, as it always did); -1 = unset
 inline int leaf_cull_setting(const Switches& setup)
 {

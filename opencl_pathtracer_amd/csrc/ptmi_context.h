@@ -43,6 +43,9 @@ struct DeviceScene {
     // devices[0], which then needs no d_update_tris
     uint8_t* d_material_is_simple_color = nullptr;
     uint32_t* d_screen_verdict = nullptr;
+    // ptmi_update_materials, devices[0] only, allocated by the first call that screens: the table of plain-colour materials AS
+    // THE EDIT WOULD LEAVE IT, which its screen kernel reads (the one above stays the table in force until the edit is accepted)
+    uint8_t* d_edited_is_simple_color = nullptr;
     ptmi_triangle* d_update_tris = nullptr;
     uint32_t* d_refit_nodes = nullptr;
     // Staged radiances [iteration][pixel] float4 (+ one statistics word per path) of the launches in flight: the stage sets of

@@ -1,5 +1,6 @@
 // ptmi_scene_memory.cpp - a scene's life on the devices: upload (ptmi_initialize_memory), the calls that rewrite what was uploaded
-// (ptmi_clear, ptmi_bind_accumulators, ptmi_set_camera, ptmi_update_triangles, the image and variance writes) and the one place
+// (ptmi_clear, ptmi_bind_accumulators, ptmi_set_camera, ptmi_update_triangles, ptmi_update_materials, ptmi_update_lights,
+// ptmi_set_sky, the image and variance writes) and the one place
 // where it all dies (free_scene_memory).
 // Owns the per-scene state of ptmi_context.h: writes DeviceScene / ContextScene at upload and resets them whole; the other units
 // only fill the lazily allocated parts (stage sets, snapshot buffers, d_reduced, d_display).
@@ -380,9 +381,170 @@ int update_triangles(ptmi_ctx* ctx, const char* who_is_calling, bool device_form
     return PTMI_OK;
 }
 
+// DScene::plain_shading as an upload of the scene these facts describe would choose it now (the switch is the upload's)
+uint32_t plain_shading_of(const UpdateFacts& facts)
+{
+    return ptmi_choice::scene_plain_shading(facts.material_type.data(), facts.material_is_simple_color.data(), facts.material_type.size(),
+                                            facts.light_type.data(), facts.light_type.size(), read_switches(Moment::kUpload))
+               ? 1u
+               : 0u;
+}
+
+// The screen of ptmi_update_materials: the texture coordinates of the triangles whose materials are textured under `simple`, the
+// table as the edit would leave it, read from the DShade records of devices[0] by one kernel on its main stream, and its one
+// word back.  Nothing of the scene is written.
+int screen_shade_on_device(ptmi_ctx* ctx, const std::vector<uint8_t>& simple, uint32_t* word)
+{
+    DeviceState& lead = ctx->dev[0];
+    ON_DEVICE(ctx, lead);
+    if (!lead.d_edited_is_simple_color)
+        if (int rc = scene_alloc(ctx, lead, std::max<size_t>(simple.size(), 16), lead.d_edited_is_simple_color)) return rc;
+    if (!lead.d_screen_verdict)
+        if (int rc = scene_alloc(ctx, lead, 16, lead.d_screen_verdict)) return rc;
+    // (in stream order, behind whatever still reads the table; `simple` outlives the wait below)
+    HIP_TRY(ctx, hipMemcpyAsync(lead.d_edited_is_simple_color, simple.data(), simple.size(), hipMemcpyHostToDevice, lead.stream));
+    std::string err;
+    HIP_TRY(ctx, hipMemsetAsync(lead.d_screen_verdict, 0xFF, 4, lead.stream));  // ptmi_refit::kScreenAccepted
+    const int rc = launch_screen_shade(lead.ds.shade, ctx->update.triangulation_size, lead.d_edited_is_simple_color, (uint32_t)simple.size(),
+                                       lead.d_screen_verdict, lead.stream, &err);
+    const hipError_t back = rc ? hipSuccess : hipMemcpyAsync(word, lead.d_screen_verdict, 4, hipMemcpyDeviceToHost, lead.stream);
+    HIP_TRY(ctx, hipStreamSynchronize(lead.stream));  // (whatever happened: the copies above read and write the caller's memory)
+    if (rc) return fail(ctx, rc, err);
+    if (back != hipSuccess) return fail(ctx, PTMI_ERR_HIP, std::string("the screen's word back: ") + hipGetErrorString(back));
+    return PTMI_OK;
+}
+
+int update_materials(ptmi_ctx* ctx, uint32_t first, const ptmi_material* materiaux, uint32_t n, ptmi_material_update_info* info)
+{
+    using clock = std::chrono::steady_clock;
+    auto ms_since = [](clock::time_point t) { return std::chrono::duration<double, std::milli>(clock::now() - t).count(); };
+    const clock::time_point t_call = clock::now();
+    const std::string who = "ptmi_update_materials", prefix = who + ": ";
+    if (info) {
+        *info = ptmi_material_update_info{};
+        info->struct_size = sizeof(ptmi_material_update_info);
+    }
+    if (!ctx) return PTMI_ERR_INVALID_ARGUMENT;
+    if (int rc = need_scene(ctx, who)) return rc;
+    UpdateFacts& facts = ctx->update;
+    const size_t count = facts.material_is_simple_color.size();
+    const uint32_t plain_before = ctx->dev[0].ds.plain_shading;
+    if (info) info->plain_before = info->plain_after = plain_before;
+    if ((uint64_t)first + n > count)
+        return fail(ctx, PTMI_ERR_INVALID_ARGUMENT, prefix + "materials " + std::to_string(first) + " to " + std::to_string((uint64_t)first + n) +
+                                                    ", the context holds " + std::to_string(count) + " (their number cannot change)");
+    if (n == 0) return PTMI_OK;
+    if (!materiaux) return fail(ctx, PTMI_ERR_INVALID_ARGUMENT, prefix + "materiaux is NULL");
+    // ---- everything that can refuse, before the first device write: build_layout's checks, in its order
+    std::string err;
+    for (uint32_t k = 0; k < n; k++)
+        if (int rc = check_material_texture(materiaux[k], first + k, facts.textures_size, err)) return fail(ctx, rc, prefix + err);
+    std::vector<uint8_t> simple = facts.material_is_simple_color;
+    bool newly_textured = false;
+    for (uint32_t k = 0; k < n; k++) {
+        const uint8_t now = materiaux[k].is_simple_color ? 1 : 0;
+        if (!now && simple[first + k]) newly_textured = true;
+        simple[first + k] = now;
+    }
+    // Only a material that was a plain colour and is textured now puts coordinates to a test they have not passed: every other
+    // triangle's were checked at upload or by the last triangle update, under a table at least as demanding.
+    uint32_t screened = 0;
+    if (newly_textured && facts.triangulation_size) {
+        uint32_t word = ptmi_refit::kScreenAccepted;
+        if (int rc = screen_shade_on_device(ctx, simple, &word)) return rc;
+        if (int rc = screen_verdict(word, err)) return fail(ctx, rc, prefix + err);
+        screened = facts.triangulation_size;
+    }
+    std::vector<DMat> records(n);
+    for (uint32_t k = 0; k < n; k++) ptmi_refit::make_mat_record(materiaux[k], &records[k]);
+    const double validate_ms = ms_since(t_call);
+    for (DeviceState& d : ctx->dev)
+        if (int rc = quiesce(ctx, d)) return rc;
+    // ---- the update (the context's facts follow once every device holds it)
+    UpdateFacts edited = facts;
+    edited.material_is_simple_color = simple;
+    for (uint32_t k = 0; k < n; k++) edited.material_type[first + k] = materiaux[k].type;
+    const uint32_t plain_after = plain_shading_of(edited);
+    for (DeviceState& d : ctx->dev) {
+        ON_DEVICE(ctx, d);
+        HIP_TRY(ctx, hipMemcpy(const_cast<DMat*>(d.ds.mats) + first, records.data(), n * sizeof(DMat), hipMemcpyHostToDevice));
+        d.ds.plain_shading = plain_after;
+        if (int rc = upload_scene_records(ctx, d)) return rc;
+    }
+    // the table ptmi_update_triangles_device screens under follows the edit
+    DeviceState& lead = ctx->dev[0];
+    if (lead.d_material_is_simple_color) {
+        ON_DEVICE(ctx, lead);
+        HIP_TRY(ctx, hipMemcpy(lead.d_material_is_simple_color, simple.data(), simple.size(), hipMemcpyHostToDevice));
+    }
+    facts = std::move(edited);
+    if (info) {
+        info->screened_triangles = screened;
+        info->plain_after = plain_after;
+        info->validate_ms = validate_ms;
+        info->total_ms = ms_since(t_call);
+    }
+    return PTMI_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int ptmi_update_materials(ptmi_ctx* ctx, uint32_t first, const ptmi_material* materiaux, uint32_t n, ptmi_material_update_info* info)
+{
+    return update_materials(ctx, first, materiaux, n, info);
+}
+
+int ptmi_update_lights(ptmi_ctx* ctx, const ptmi_light* lights, uint32_t lights_size)
+{
+    const std::string who = "ptmi_update_lights", prefix = who + ": ";
+    if (!ctx) return PTMI_ERR_INVALID_ARGUMENT;
+    if (int rc = need_scene(ctx, who)) return rc;
+    if (lights_size != ctx->cfg.lights_size)
+        return fail(ctx, PTMI_ERR_INVALID_ARGUMENT, prefix + std::to_string(lights_size) + " lights, config.lights_size is " +
+                                                    std::to_string(ctx->cfg.lights_size) + " (LIGHTS_SIZE is baked at setup)");
+    if (lights_size && !lights) return fail(ctx, PTMI_ERR_INVALID_ARGUMENT, prefix + "lights is NULL");
+    if (!ctx->literal_kernel_reason.empty())
+        return fail(ctx, PTMI_ERR_UNSUPPORTED, prefix + "the uploaded scene has records that can yield NaN distances (" +
+                                               ctx->literal_kernel_reason + "): call ptmi_initialize_memory with the new scene");
+    const std::string why = lights_need_literal_kernel(lights, lights_size);
+    if (!why.empty())
+        return fail(ctx, PTMI_ERR_UNSUPPORTED, prefix + why + ": the kernel instantiation was chosen at upload, call "
+                                               "ptmi_initialize_memory with the new lights");
+    for (DeviceState& d : ctx->dev)
+        if (int rc = quiesce(ctx, d)) return rc;
+    UpdateFacts edited = ctx->update;
+    for (uint32_t i = 0; i < lights_size; i++) edited.light_type[i] = lights[i].type;
+    const uint32_t plain = plain_shading_of(edited);
+    for (DeviceState& d : ctx->dev) {
+        ON_DEVICE(ctx, d);
+        if (lights_size)
+            HIP_TRY(ctx, hipMemcpy(const_cast<ptmi_light*>(d.ds.lights), lights, (size_t)lights_size * sizeof(ptmi_light), hipMemcpyHostToDevice));
+        d.ds.plain_shading = plain;
+        if (int rc = upload_scene_records(ctx, d)) return rc;
+    }
+    ctx->update = std::move(edited);
+    return PTMI_OK;
+}
+
+int ptmi_set_sky(ptmi_ctx* ctx, const ptmi_sky* sky)
+{
+    const std::string who = "ptmi_set_sky", prefix = who + ": ";
+    if (!ctx) return PTMI_ERR_INVALID_ARGUMENT;
+    if (!sky) return fail(ctx, PTMI_ERR_INVALID_ARGUMENT, prefix + "sky is NULL");
+    if (int rc = need_scene(ctx, who)) return rc;
+    std::string err;
+    if (int rc = check_sky_textures(*sky, ctx->update.textures_data_size, err)) return fail(ctx, rc, prefix + err);
+    for (DeviceState& d : ctx->dev)
+        if (int rc = quiesce(ctx, d)) return rc;
+    for (DeviceState& d : ctx->dev) {
+        ON_DEVICE(ctx, d);
+        d.ds.sky = *sky;
+        if (int rc = upload_scene_records(ctx, d)) return rc;
+    }
+    return PTMI_OK;
+}
 
 int ptmi_initialize_memory(ptmi_ctx* ctx, const ptmi_scene* sc)
 {
@@ -405,6 +567,10 @@ int ptmi_initialize_memory(ptmi_ctx* ctx, const ptmi_scene* sc)
     ctx->update.n_big_leaves = (uint32_t)lay.big_leaves.size();
     ctx->update.tris_precomputed = lay.tris_precomputed;
     ctx->update.material_is_simple_color = lay.material_is_simple_color;
+    ctx->update.material_type = lay.material_type;
+    ctx->update.light_type = lay.light_type;
+    ctx->update.textures_size = sc->textures_size;
+    ctx->update.textures_data_size = sc->textures_data_size;
     for (DeviceState& d : ctx->dev)
         if (int rc = upload_scene(ctx, d, lay, sc)) {
             const std::string msg = ctx->err;

@@ -60,9 +60,8 @@ std::string scene_needs_literal_kernel(const ptmi_scene* sc)
 {
     const std::string camera = camera_needs_literal_kernel(sc->camera_position, sc->camera_direction, sc->camera_right, sc->camera_up);
     if (!camera.empty()) return camera;
-    for (uint32_t i = 0; i < sc->lights_size; i++)
-        if (!within(sc->lights[i].position, kCoord) || !within(sc->lights[i].direction, kCoord))
-            return "light " + std::to_string(i) + " is not finite (or beyond 2^21)";
+    const std::string lights = lights_need_literal_kernel(sc->lights, sc->lights_size);
+    if (!lights.empty()) return lights;
     for (uint32_t i = 0; i < sc->triangulation_size; i++) {
         const std::string why = triangle_needs_literal_kernel(sc->triangulation[i], i);
         if (!why.empty()) return why;
@@ -77,6 +76,29 @@ std::string camera_needs_literal_kernel(const ptmi_float4& position, const ptmi_
     if (!within(position, kCoord) || !within(direction, kCoord) || !within(right, kCoord) || !within(up, kCoord))
         return "the camera is not finite (or beyond 2^21)";
     return std::string();
+}
+
+std::string lights_need_literal_kernel(const ptmi_light* lights, uint32_t lights_size)
+{
+    for (uint32_t i = 0; i < lights_size; i++)
+        if (!within(lights[i].position, kCoord) || !within(lights[i].direction, kCoord))
+            return "light " + std::to_string(i) + " is not finite (or beyond 2^21)";
+    return std::string();
+}
+
+int check_material_texture(const ptmi_material& m, uint32_t i, uint32_t textures_size, std::string& err)
+{
+    if (!m.is_simple_color && (m.texture_id < 0 || (uint32_t)m.texture_id >= textures_size))
+        return fail(err, PTMI_ERR_BAD_SCENE, "material " + std::to_string(i) + " has an invalid textureId");
+    return PTMI_OK;
+}
+
+int check_sky_textures(const ptmi_sky& sky, uint32_t textures_data_size, std::string& err)
+{
+    for (int f = 0; f < 6; f++)
+        if (!texture_ok(sky.sky_textures[f], textures_data_size))
+            return fail(err, PTMI_ERR_BAD_SCENE, "sky texture " + std::to_string(f) + " outside textures_data");
+    return PTMI_OK;
 }
 
 int screen_refusal(uint32_t code, uint32_t i, std::string& err)
@@ -126,38 +148,32 @@ int build_layout(const ptmi_config& cfg, const ptmi_scene* sc, Relayout& out, st
     if (sc->lights_size != cfg.lights_size)
         return fail(err, PTMI_ERR_INVALID_ARGUMENT, "scene.lights_size differs from config.lights_size (LIGHTS_SIZE is baked at setup)");
 
-    for (int f = 0; f < 6; f++)
-        if (!texture_ok(sc->sky->sky_textures[f], sc->textures_data_size))
-            return fail(err, PTMI_ERR_BAD_SCENE, "sky texture " + std::to_string(f) + " outside textures_data");
+    if (int rc = check_sky_textures(*sc->sky, sc->textures_data_size, err)) return rc;
     for (uint32_t i = 0; i < sc->textures_size; i++)
         if (!texture_ok(sc->textures[i], sc->textures_data_size))
             return fail(err, PTMI_ERR_BAD_SCENE, "texture " + std::to_string(i) + " outside textures_data");
 
     out.mats.resize(sc->materiaux_size);
     for (uint32_t i = 0; i < sc->materiaux_size; i++) {
-        const ptmi_material& m = sc->materiaux[i];
-        if (!m.is_simple_color && (m.texture_id < 0 || (uint32_t)m.texture_id >= sc->textures_size))
-            return fail(err, PTMI_ERR_BAD_SCENE, "material " + std::to_string(i) + " has an invalid textureId");
-        DMat& d = out.mats[i];
-        std::memcpy(d.color, &m.simple_color, 16);
-        d.opacity = m.opacity;
-        d.texture_id = m.texture_id;
-        d.type = m.type;
-        d.is_simple_color = m.is_simple_color ? 1u : 0u;
+        if (int rc = check_material_texture(sc->materiaux[i], i, sc->textures_size, err)) return rc;
+        ptmi_refit::make_mat_record(sc->materiaux[i], &out.mats[i]);
     }
     // The common untextured Lambert scene (BASELINE's Cornell box and 1M-triangle scene): the wavefront kernel has a
     // specialisation whose path logic holds neither the other four material types nor textures nor the other light types.
     const ptmi_switches::Switches upload = ptmi_switches::read_switches(ptmi_switches::Moment::kUpload);
-    out.plain_shading = ptmi_choice::plain_shading_after_switch(true, upload);
-    for (uint32_t i = 0; i < sc->materiaux_size && out.plain_shading; i++)
-        if (sc->materiaux[i].type != PTMI_MAT_STANDART || !sc->materiaux[i].is_simple_color) out.plain_shading = false;
-    for (uint32_t i = 0; i < sc->lights_size && out.plain_shading; i++)
-        if (sc->lights[i].type != PTMI_LIGHT_POINT) out.plain_shading = false;
+    out.material_is_simple_color.resize(sc->materiaux_size);
+    out.material_type.resize(sc->materiaux_size);
+    out.light_type.resize(sc->lights_size);
+    for (uint32_t i = 0; i < sc->materiaux_size; i++) {
+        out.material_is_simple_color[i] = sc->materiaux[i].is_simple_color ? 1 : 0;
+        out.material_type[i] = sc->materiaux[i].type;
+    }
+    for (uint32_t i = 0; i < sc->lights_size; i++) out.light_type[i] = sc->lights[i].type;
+    out.plain_shading = ptmi_choice::scene_plain_shading(out.material_type.data(), out.material_is_simple_color.data(), sc->materiaux_size,
+                                                         out.light_type.data(), sc->lights_size, upload);
 
     out.tris.resize(nt);
     out.shade.resize(nt);
-    out.material_is_simple_color.resize(sc->materiaux_size);
-    for (uint32_t i = 0; i < sc->materiaux_size; i++) out.material_is_simple_color[i] = sc->materiaux[i].is_simple_color ? 1 : 0;
     for (uint32_t i = 0; i < nt; i++) {
         const ptmi_triangle& t = sc->triangulation[i];
         if (int rc = check_triangle_materials(t, i, out.material_is_simple_color.data(), sc->materiaux_size, err)) return rc;

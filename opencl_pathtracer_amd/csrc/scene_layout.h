@@ -19,6 +19,7 @@ struct Relayout {
     std::vector<DShade> shade;
     std::vector<DMat> mats;
     std::vector<uint8_t> material_is_simple_color;  // per material: what check_triangle_materials asks
+    std::vector<int32_t> material_type, light_type;  // per material / light: with the line above, what plain_shading was decided from
     std::vector<DBigLeaf> big_leaves;
     bool tris_precomputed = false;
     bool plain_shading = false; // every material a plain-colour MAT_STANDART, every light a LIGHT_POINT
@@ -44,6 +45,14 @@ int screen_refusal(uint32_t code, uint32_t i, std::string& err);
 std::string camera_needs_literal_kernel(const ptmi_float4& position, const ptmi_float4& direction, const ptmi_float4& right, const ptmi_float4& up);
 std::string triangle_needs_literal_kernel(const ptmi_triangle& t, uint32_t i);
 int check_triangle_materials(const ptmi_triangle& t, uint32_t i, const uint8_t* material_is_simple_color, uint32_t materiaux_size, std::string& err);
+
+// What build_layout asks of a material, of the lights and of the sky, one call each, for the in-place edits of a loaded scene
+// (ptmi_update_materials, ptmi_update_lights, ptmi_set_sky), which ask the same with the same words: material `i`'s texture among
+// `textures_size` textures (PTMI_ERR_BAD_SCENE); why the lights can make a triangle test compute a NaN distance (empty: they
+// cannot); the six faces of the sky inside `textures_data_size` texels (PTMI_ERR_BAD_SCENE).
+int check_material_texture(const ptmi_material& m, uint32_t i, uint32_t textures_size, std::string& err);
+std::string lights_need_literal_kernel(const ptmi_light* lights, uint32_t lights_size);
+int check_sky_textures(const ptmi_sky& sky, uint32_t textures_data_size, std::string& err);
 
 // Returns PTMI_OK or an error code with its message in `err`.  cfg: lights_size and sampler are read.
 int build_layout(const ptmi_config& cfg, const ptmi_scene* sc, Relayout& out, std::string& err);

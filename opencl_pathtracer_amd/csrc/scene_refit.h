@@ -17,6 +17,11 @@ struct UpdateFacts {
     uint32_t n_big_leaves = 0;
     bool tris_precomputed = false;
     std::vector<uint8_t> material_is_simple_color;
+    // ptmi_update_materials, ptmi_update_lights, ptmi_set_sky: the rest of what DScene::plain_shading was decided from (a
+    // material's type, a light's type: kernel_choice.h: scene_plain_shading), and the extents a texture id and a sky face are
+    // checked against.  The three calls keep these, and the line above, in step with what the devices hold.
+    std::vector<int32_t> material_type, light_type;
+    uint32_t textures_size = 0, textures_data_size = 0;
 };
 
 // The screen of ptmi_update_triangles, applied before the first device write: build_layout's checks on triangles (materials,
@@ -51,6 +56,11 @@ int build_refit_schedule(const DNode* records, const uint32_t* tri_ids, uint32_t
 // material_is_simple_color: one byte per material, on the device.  Reads the triangles, writes the one word.
 int launch_screen_update(const ptmi_triangle* triangulation, uint32_t triangulation_size, const uint8_t* material_is_simple_color,
                          uint32_t materiaux_size, bool tris_precomputed, uint32_t* verdict, void* stream, std::string* err);
+// The screen of ptmi_update_materials: the same protocol over the DShade records a device holds, shade[0 .. triangulation_size):
+// the word ends as that of the first triangle whose materials are out of range or, one of them textured under
+// material_is_simple_color, whose texture coordinates are not finite or beyond 2^30.  Reads the records, writes the one word.
+int launch_screen_shade(const DShade* shade, uint32_t triangulation_size, const uint8_t* material_is_simple_color, uint32_t materiaux_size,
+                        uint32_t* verdict, void* stream, std::string* err);
 // records[r] = the DTri (or DTriPre, strict reciprocal) record of triangulation[tri_ids[r]] where tri_ids[r] < triangulation_size
 // (a node record's is 0xFFFFFFFF)
 int launch_update_tri_records(DTri* records, const uint32_t* tri_ids, uint32_t n_records, const ptmi_triangle* triangulation,

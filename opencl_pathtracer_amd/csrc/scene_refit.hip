@@ -4,7 +4,8 @@
 // compute it from.  No atomics, nothing shared between lanes: a lane reads the caller's triangles and, in a level pass, records
 // of the level below (written by an earlier launch), and writes the one record that is its own, as whole 16-byte words.
 // In front of them, for ptmi_update_triangles_device alone, the screen kernel: the host's checks of the new triangles, one lane
-// per triangle, answered in one word (at most one atomicMin per wave that refuses, none in a good update).
+// per triangle, answered in one word (at most one atomicMin per wave that refuses, none in a good update).  And, for
+// ptmi_update_materials, the same protocol over the DShade records the device holds: screen_shade_kernel.
 #include <hip/hip_runtime.h>
 
 #include "scene_refit.h"
@@ -84,9 +85,44 @@ __global__ void __launch_bounds__(kBlock) screen_update_kernel(const ptmi_triang
     if (lane == (uint32_t)__ffsll(refusing) - 1u) atomicMin(verdict, ptmi_refit::screen_word(i, code));
 }
 
+// The screen of ptmi_update_materials: one lane per DShade record the context holds (its index is the caller's triangle index),
+// the verdict of scene_refit_common.h: screen_shade_materials under the NEW table of plain-colour materials, answered as above.
+// A lane fetches the quad with its two material indices and, only where one of them is textured, the three quads of texture
+// coordinates: four 16-byte loads at most, 16 of a record's 112 bytes where its materials are plain.  Nothing is written but
+// the one word.
+__global__ void __launch_bounds__(kBlock) screen_shade_kernel(const DShade* __restrict__ shade, const uint32_t n_tris,
+                                                              const uint8_t* __restrict__ material_is_simple_color,
+                                                              const uint32_t materiaux_size, uint32_t* __restrict__ verdict)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    uint32_t code = ptmi_refit::kScreenOk;
+    if (i < n_tris) {
+        const uint4* const quads = reinterpret_cast<const uint4*>(shade + i);  // (records of 7 x 16 bytes in a hipMalloc'ed array)
+        code = ptmi_refit::screen_shade_materials(
+            [quads](uint32_t k) {
+                const uint4 q = quads[k];
+                return ptmi_refit::ShadeQuad{{q.x, q.y, q.z, q.w}};
+            },
+            material_is_simple_color, materiaux_size);
+    }
+    const unsigned long long refusing = __ballot(code != ptmi_refit::kScreenOk);
+    if (refusing == 0) return;
+    const uint32_t lane = __lane_id();
+    if (lane == (uint32_t)__ffsll(refusing) - 1u) atomicMin(verdict, ptmi_refit::screen_word(i, code));
+}
+
 dim3 grid_for(uint32_t n) { return dim3((n + kBlock - 1) / kBlock); }
 
 }  // namespace
+
+int launch_screen_shade(const DShade* shade, uint32_t triangulation_size, const uint8_t* material_is_simple_color, uint32_t materiaux_size,
+                        uint32_t* verdict, void* stream, std::string* err)
+{
+    if (triangulation_size == 0) return PTMI_OK;
+    hipLaunchKernelGGL(screen_shade_kernel, grid_for(triangulation_size), dim3(kBlock), 0, (hipStream_t)stream, shade, triangulation_size,
+                       material_is_simple_color, materiaux_size, verdict);
+    return launch_status(hipGetLastError(), "screen_shade_kernel", err);
+}
 
 int launch_screen_update(const ptmi_triangle* triangulation, uint32_t triangulation_size, const uint8_t* material_is_simple_color,
                          uint32_t materiaux_size, bool tris_precomputed, uint32_t* verdict, void* stream, std::string* err)

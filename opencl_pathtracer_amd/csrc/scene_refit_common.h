@@ -3,7 +3,8 @@
 //
 // Three things live here, once:
 //   * the screen of a new triangle - why build_layout or an in-place update refuses it, as a small code (ScreenCode) - for the
-//     host loops and for the screen kernel of ptmi_update_triangles_device (tests/update_screen_model.cpp runs it on its own);
+//     host loops and for the screen kernel of ptmi_update_triangles_device (tests/update_screen_model.cpp runs it on its own),
+//     and its material part restated on the DShade record a context keeps (ptmi_update_materials; tests/material_screen_model.cpp);
 //   * a triangle's device records (DTri / DTriPre / DShade) as build_layout writes them at upload, so that a record rewritten on
 //     the device holds the bytes a fresh upload of the same triangle would;
 //   * the refit of a box from the boxes below it: a leaf's box is the fold of its triangles' `aabb` in ascending index order
@@ -20,6 +21,7 @@
 #define PTMI_SCENE_REFIT_COMMON_H
 
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 
 #include "bvh_build_common.h"
@@ -89,6 +91,16 @@ PTMI_HD void make_shade_record(const ptmi_triangle& t, DShade* s)
     s->pad[0] = s->pad[1] = 0;
 }
 
+// A material without its host pointer: the record the shading reads (build_layout at upload, ptmi_update_materials in place).
+PTMI_HD void make_mat_record(const ptmi_material& m, ptmi_internal::DMat* d)
+{
+    store4(d->color, m.simple_color);
+    d->opacity = m.opacity;
+    d->texture_id = m.texture_id;
+    d->type = m.type;
+    d->is_simple_color = m.is_simple_color ? 1u : 0u;
+}
+
 // ---- the screen ------------------------------------------------------------------------------------------------------------
 
 // Why one triangle is refused, as a small code: what build_layout asks of every triangle (scene_layout.cpp: its materials and
@@ -131,6 +143,53 @@ PTMI_HD uint32_t screen_materials(const ptmi_triangle& t, const uint8_t* materia
               within2(t.uvn1, kScreenTexCoordBound) && within2(t.uvn2, kScreenTexCoordBound) && within2(t.uvn3, kScreenTexCoordBound)))
             return kScreenTexCoord;
     return kScreenOk;
+}
+
+// screen_materials restated on the DShade record of a triangle - what a context still holds of it once the caller's array is
+// gone (ptmi_update_materials: a material that turns textured puts the texture coordinates of its triangles to the test they were
+// spared at upload).  make_shade_record copies the twelve coordinates and both indices unchanged, so the verdict is the
+// triangle's.  The record is taken as its seven 16-byte quads, through quad_at(k): the indices lie in quad 6, the coordinates in
+// quads 3, 4 and 5, which are fetched only where one of the two materials is textured under the table given.
+struct ShadeQuad {
+    uint32_t w[4];
+};
+constexpr uint32_t kShadeQuadTexCoords = 3, kShadeQuadMaterials = 6;
+static_assert(offsetof(DShade, uvp) == 16 * kShadeQuadTexCoords && offsetof(DShade, uvn) + sizeof(DShade::uvn) == 16 * kShadeQuadMaterials &&
+              offsetof(DShade, mat_pos) == 16 * kShadeQuadMaterials && offsetof(DShade, mat_neg) == 16 * kShadeQuadMaterials + 4 &&
+              sizeof(DShade) == 16 * (kShadeQuadMaterials + 1), "the quads of a DShade record");
+
+PTMI_HD bool quad_within(const ShadeQuad& q, float bound)
+{
+    float v[4];
+    __builtin_memcpy(v, q.w, 16);
+    return std::fabs(v[0]) <= bound && std::fabs(v[1]) <= bound && std::fabs(v[2]) <= bound && std::fabs(v[3]) <= bound;  // (false for NaN)
+}
+
+template <class QuadAt>
+PTMI_HD uint32_t screen_shade_materials(QuadAt quad_at, const uint8_t* material_is_simple_color, uint32_t materiaux_size)
+{
+    const ShadeQuad m = quad_at(kShadeQuadMaterials);
+    const uint32_t mat_pos = m.w[0], mat_neg = m.w[1];
+    if (mat_pos >= materiaux_size || mat_neg >= materiaux_size) return kScreenMaterial;
+    if (!material_is_simple_color[mat_pos] || !material_is_simple_color[mat_neg]) {
+        const ShadeQuad a = quad_at(kShadeQuadTexCoords), b = quad_at(kShadeQuadTexCoords + 1), c = quad_at(kShadeQuadTexCoords + 2);
+        if (!(quad_within(a, kScreenTexCoordBound) && quad_within(b, kScreenTexCoordBound) && quad_within(c, kScreenTexCoordBound)))
+            return kScreenTexCoord;
+    }
+    return kScreenOk;
+}
+
+// ... on a record in host memory (the model of the tests; the device fetches the quads as 16-byte loads: scene_refit.hip)
+inline uint32_t screen_shade_record(const DShade& s, const uint8_t* material_is_simple_color, uint32_t materiaux_size)
+{
+    const unsigned char* const bytes = reinterpret_cast<const unsigned char*>(&s);
+    return screen_shade_materials(
+        [bytes](uint32_t k) {
+            ShadeQuad q;
+            __builtin_memcpy(q.w, bytes + 16 * k, 16);
+            return q;
+        },
+        material_is_simple_color, materiaux_size);
 }
 
 PTMI_HD bool determinant_is_usable(float d) { return d != 0.0f && std::isfinite(d) && std::isfinite(1.0f / d); }
