@@ -21,7 +21,8 @@ LIB_OBJS   := $(OBJDIR)/kernels.o $(OBJDIR)/kernel_wavefront.o $(OBJDIR)/kernels
               $(OBJDIR)/path_query.o $(OBJDIR)/path_query_da.o $(OBJDIR)/ptmi_paths.o \
               $(OBJDIR)/guide_buffers.o $(OBJDIR)/guide_buffers_da.o \
               $(OBJDIR)/denoise.o $(OBJDIR)/ptmi_denoise.o \
-              $(OBJDIR)/reproject.o $(OBJDIR)/ptmi_reproject.o $(OBJDIR)/ptmi_display.o
+              $(OBJDIR)/reproject.o $(OBJDIR)/ptmi_reproject.o $(OBJDIR)/ptmi_display.o \
+              $(OBJDIR)/mesh_assemble.o $(OBJDIR)/ptmi_mesh.o
 
 .PHONY: all lib shim oracle ref clean resources kernel-resources
 all: lib shim oracle
@@ -61,4 +62,4 @@ clean:
 kernel-resources: resources
 resources:
 	@for f in kernels kernel_wavefront ray_query guide_buffers path_query; do for m in 0 1; do $(HIPCC) $(HIPFLAGS) -DPTMI_DEFAULT_ARITHMETIC=$$m --cuda-device-only -c $(CSRC)/$$f.hip -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs:|ScratchSize|Occupancy|LDS Size|Spill" | sed 's/.*remark: *//' | tr '\n' ' '; echo; done; done
-	@for f in denoise reproject display scene_refit; do $(HIPCC) $(HIPFLAGS) --cuda-device-only -c $(CSRC)/$$f.hip -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs:|ScratchSize|Occupancy|LDS Size|Spill" | sed 's/.*remark: *//' | tr '\n' ' '; echo; done
+	@for f in denoise reproject display scene_refit mesh_assemble; do $(HIPCC) $(HIPFLAGS) --cuda-device-only -c $(CSRC)/$$f.hip -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "Function Name|VGPRs:|ScratchSize|Occupancy|LDS Size|Spill" | sed 's/.*remark: *//' | tr '\n' ' '; echo; done

@@ -312,6 +312,82 @@ int ptmi_update_triangles(ptmi_ctx* ctx, const ptmi_triangle* triangulation, uin
  * other devices (0 on one device), device_ms and levels as above.  Both forms may be mixed freely on one context. */
 int ptmi_update_triangles_device(ptmi_ctx* ctx, const void* d_triangulation, uint32_t triangulation_size, ptmi_update_info* info);
 
+/* ptmi_update_vertices: the same update from what a caller has - a vertex buffer (and, for a smooth mesh, a normal buffer) and
+ * a topology bound once.  The library derives the 336-byte records itself, one lane per triangle on devices[0], and hands them
+ * to the update above: screen, records, shading records, refit.
+ *
+ * THE RECORD.  Assembled record i is a pure function of the bound topology and the vertex buffers: the importer's
+ * Triangle_Create (Maya/PathTracer_MayaImporter.cpp:943-1047).  Every operation is one IEEE binary32 operation in the written
+ * order - no contraction, correctly rounded / and sqrt, denormals kept - and the same in both arithmetic modes of a context.
+ * dot3(a,b) = (a.x*b.x + a.y*b.y) + a.z*b.z.
+ *  1. Corners, IN THE FACE'S OWN WINDING: p_k = (positions[indices[3i+k]].xyz, 1), m_k = (normals[indices[3i+k]].xyz, 0), or
+ *     with no normal buffer m_k = (N.xyz, 0), N of step 3.  Points carry w = 1 and directions w = 0 (MayaImporter.h:29-37).
+ *  2. Box (BoundingBox_Create, Structs.h:197-205, all four components): pMin = min(min(p0,p1),p2), pMax = max(max(p0,p1),p2)
+ *     with min(a,b) = b < a ? b : a and max(a,b) = a < b ? b : a (std::min / std::max: a tie keeps the first);
+ *     centroid = (pMin + pMax) / 2, isEmpty = 0, the other bytes of the 64 are 0.
+ *  3. Normal: e1 = p1 - p0, e2 = p2 - p0, c = (e1.y*e2.z - e1.z*e2.y, e1.z*e2.x - e1.x*e2.z, e1.x*e2.y - e1.y*e2.x),
+ *     l = sqrt(dot3(c,c)), n = (c.x/l, c.y/l, c.z/l, 1).
+ *  4. Order: the Vector_LexLessThan cascade of MayaImporter.cpp:961-1020 with its six outcomes as written there puts the
+ *     corners into s1 < s2 < s3; m, uvp and uvn follow it.  (Ties matter only for triangles the screen refuses.)
+ *  5. Shading normals (:1030-1036): l_k = sqrt(dot3(m_k, m_k)); n_k = n (w = 1) where l_k < 0.5f, else m_k / l_k in all four
+ *     components.
+ *  6. t1..bt3 are +0: the integrator never reads them (and the scenes of this library leave them so).  mat_pos, mat_neg and
+ *     id come from the topology.  Every padding byte is 0: all 336 bytes are defined.
+ *
+ * ptmi_bind_mesh copies the host arrays of `topology` to devices[0] (72 bytes per triangle, 24 where uvp and uvn are both NULL);
+ * triangle i of the topology is triangle i of the array ptmi_initialize_memory was given.  It needs an initialised context
+ * (PTMI_ERR_STATE).  PTMI_ERR_INVALID_ARGUMENT: a wrong struct_size, reserved != 0, n_triangles other than the uploaded count,
+ * and with triangles n_vertices == 0, indices or mat_pos NULL, an index >= n_vertices (the message names triangle, corner and
+ * index).  Material indices are NOT checked here: the update's screen does.  A second bind replaces the first, a NULL topology
+ * unbinds; ptmi_initialize_memory and ptmi_release free it.  It touches nothing rendered and nothing of the scene.
+ *
+ * ptmi_update_vertices_device: positions (and normals, or NULL for a flat mesh) are addresses on devices[0], 16-byte aligned:
+ * three floats at base + v * stride, whatever else the stride holds is never read (a torch (V,3) tensor has stride 12).
+ * Checked in this order before any device work: PTMI_ERR_INVALID_ARGUMENT for a NULL or wrongly sized struct; PTMI_ERR_STATE
+ * with no scene or no bound mesh; PTMI_ERR_INVALID_ARGUMENT for n_vertices other than the bound one, a stride below 12 or not
+ * a multiple of 4, NULL positions, a pointer that is not 16-byte aligned; PTMI_ERR_UNSUPPORTED where the scene has a
+ * ptmi_literal_kernel_reason, in ptmi_update_triangles' words.  Then one kernel on the main stream of devices[0]
+ * (ptmi_set_stream's, where one was given) writes the records into the context's scratch copy of the triangles (336 bytes per
+ * triangle, allocated by the first update, freed with the scene), and ptmi_update_triangles_device's work runs on them under
+ * this entry point's name: statuses and messages are those of ptmi_update_triangles for the assembled records, the refused
+ * triangle's index included; nothing of the scene is written after a refusal; every other listed device gets the
+ * device-to-device copy.  SYNCHRONOUS; the buffers are read on the main stream and never written.
+ *
+ * ptmi_update_vertices: the same from host buffers (no alignment asked), copied to a staging buffer on devices[0] that grows
+ * on demand.  Of each buffer the bytes from its address to the last vertex's third float are read, (n_vertices - 1) * stride + 12,
+ * and none beyond: positions and normals may interleave in one allocation that ends with the last normal.  The 336-byte records never exist on the host, and the screen runs on the device.
+ *
+ * info: upload_ms includes the vertex copy, device_ms the assemble kernel (HIP events), total_ms is the whole call.  The call
+ * waits once for the assemble kernel and the screen behind it, so validate_ms contains the wait for both.
+ *
+ * ptmi_assemble_triangles: steps 1-6 on the host - the same code - into out[0 .. n_triangles).  No context, no device; the
+ * refusals of ptmi_bind_mesh's arguments and of the buffers as PTMI_ERR_INVALID_ARGUMENT, messages in ptmi_last_error(NULL).
+ * For callers that keep GlobalVars.triangulation in step, as ptmi_bvh_refit is for the tree. */
+typedef struct ptmi_mesh_topology {   /* host arrays, copied by the call */
+    uint32_t struct_size;             /* = sizeof(ptmi_mesh_topology) */
+    uint32_t n_triangles;             /* = the uploaded count */
+    uint32_t n_vertices;              /* >= 1 */
+    uint32_t reserved;                /* 0 */
+    const uint32_t* indices;          /* [3*n_triangles], each < n_vertices; triangle i = triangle i of the uploaded array */
+    const ptmi_float2* uvp;           /* [3*n_triangles] per corner in face order; NULL = zeros */
+    const ptmi_float2* uvn;           /* NULL = uvp */
+    const uint32_t* mat_pos;          /* [n_triangles] */
+    const uint32_t* mat_neg;          /* NULL = mat_pos */
+    const uint32_t* ids;              /* NULL = i */
+} ptmi_mesh_topology;
+typedef struct ptmi_vertex_buffers {
+    uint32_t struct_size;             /* = sizeof(ptmi_vertex_buffers) */
+    uint32_t n_vertices;              /* = the bound one */
+    uint32_t position_stride;         /* bytes, >= 12, a multiple of 4 */
+    uint32_t normal_stride;           /* the same; not read where normals is NULL */
+    const void* positions;            /* float x,y,z at positions + v*position_stride; anything else in the stride is never read */
+    const void* normals;              /* NULL: flat */
+} ptmi_vertex_buffers;
+int ptmi_bind_mesh(ptmi_ctx* ctx, const ptmi_mesh_topology* topology);
+int ptmi_update_vertices(ptmi_ctx* ctx, const ptmi_vertex_buffers* host, ptmi_update_info* info);
+int ptmi_update_vertices_device(ptmi_ctx* ctx, const ptmi_vertex_buffers* device, ptmi_update_info* info);
+int ptmi_assemble_triangles(const ptmi_mesh_topology* topology, const ptmi_vertex_buffers* host, ptmi_triangle* out);
+
 /* Materials, lights and sky of the loaded scene, edited in place: what a look-development session changes between renders.
  * The three calls below follow the contract of ptmi_set_camera and ptmi_update_triangles above, word for word: an initialised
  * context (PTMI_ERR_STATE otherwise), every check before the first device write (after any error the context renders the scene

@@ -87,6 +87,19 @@ class UpdateInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class MeshTopology(C.Structure):
+    """ptmi_mesh_topology: host arrays ptmi_bind_mesh copies (None = the default ptmi.h names)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_triangles", C.c_uint32), ("n_vertices", C.c_uint32), ("reserved", C.c_uint32),
+                ("indices", C.c_void_p), ("uvp", C.c_void_p), ("uvn", C.c_void_p), ("mat_pos", C.c_void_p), ("mat_neg", C.c_void_p),
+                ("ids", C.c_void_p)]
+
+
+class VertexBuffers(C.Structure):
+    """ptmi_vertex_buffers: host or device addresses of the positions and (None: a flat mesh) the normals, strides in bytes."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_vertices", C.c_uint32), ("position_stride", C.c_uint32), ("normal_stride", C.c_uint32),
+                ("positions", C.c_void_p), ("normals", C.c_void_p)]
+
+
 class MaterialUpdateInfo(C.Structure):
     """ptmi_material_update_info: what ptmi_update_materials did (whether its device screen ran, and the plain-shading flip)."""
     _fields_ = [("struct_size", C.c_uint32), ("screened_triangles", C.c_uint32), ("plain_before", C.c_uint32),
@@ -196,6 +209,7 @@ ABI_SYMBOLS = ["ptmi_setup_context", "ptmi_initialize_memory", "ptmi_render", "p
                "ptmi_device_variance", "ptmi_last_error",
                "ptmi_abi_version", "ptmi_device_count", "ptmi_device_share", "ptmi_bvh_create",
                "ptmi_bvh_create_device", "ptmi_set_camera", "ptmi_update_triangles", "ptmi_update_triangles_device", "ptmi_bvh_refit",
+               "ptmi_bind_mesh", "ptmi_update_vertices", "ptmi_update_vertices_device", "ptmi_assemble_triangles",
                "ptmi_update_materials", "ptmi_update_lights", "ptmi_set_sky",
                "ptmi_query_rays", "ptmi_query_rays_device", "ptmi_render_guides", "ptmi_render_guides_device",
                "ptmi_denoise", "ptmi_denoise_device", "ptmi_trace_paths", "ptmi_trace_paths_device",
@@ -280,6 +294,10 @@ def load_library():
     lib.ptmi_set_camera.argtypes = [vp, C.POINTER(Float4), C.POINTER(Float4), C.POINTER(Float4), C.POINTER(Float4)]
     lib.ptmi_update_triangles.argtypes = [vp, vp, u32, C.POINTER(UpdateInfo)]
     lib.ptmi_update_triangles_device.argtypes = [vp, vp, u32, C.POINTER(UpdateInfo)]
+    lib.ptmi_bind_mesh.argtypes = [vp, C.POINTER(MeshTopology)]
+    lib.ptmi_update_vertices.argtypes = [vp, C.POINTER(VertexBuffers), C.POINTER(UpdateInfo)]
+    lib.ptmi_update_vertices_device.argtypes = [vp, C.POINTER(VertexBuffers), C.POINTER(UpdateInfo)]
+    lib.ptmi_assemble_triangles.argtypes = [C.POINTER(MeshTopology), C.POINTER(VertexBuffers), vp]
     lib.ptmi_update_materials.argtypes = [vp, u32, vp, u32, C.POINTER(MaterialUpdateInfo)]
     lib.ptmi_update_lights.argtypes = [vp, vp, u32]
     lib.ptmi_set_sky.argtypes = [vp, vp]
@@ -380,6 +398,58 @@ def bvh_refit(scene):
     return scene
 
 
+def mesh_topology(mesh):
+    """(ptmi_mesh_topology pointing into contiguous copies of ``mesh``'s arrays, those arrays - keep them alive while it is
+    used).  ``mesh``: a ``scenes.Mesh``, or anything with its fields; uvp, uvn, mat_neg and ids may be None (ptmi.h's defaults)."""
+    def arr(x, dtype, shape):
+        return None if x is None else np.ascontiguousarray(x, dtype).reshape(shape)
+    n = len(mesh.indices)
+    keep = dict(indices=arr(mesh.indices, np.uint32, (n, 3)), uvp=arr(getattr(mesh, "uvp", None), np.float32, (n, 3, 2)),
+                uvn=arr(getattr(mesh, "uvn", None), np.float32, (n, 3, 2)), mat_pos=arr(mesh.mat_pos, np.uint32, (n,)),
+                mat_neg=arr(getattr(mesh, "mat_neg", None), np.uint32, (n,)), ids=arr(getattr(mesh, "ids", None), np.uint32, (n,)))
+    t = MeshTopology(C.sizeof(MeshTopology), n, len(mesh.positions), 0)
+    for name, a in keep.items():
+        setattr(t, name, None if a is None else a.ctypes.data)
+    return t, keep
+
+
+def _host_vertex_buffers(positions, normals):
+    """(ptmi_vertex_buffers over float32 (V, 3+) arrays whose rows are ``strides[0]`` bytes apart, the arrays to keep alive)"""
+    def rows(a):
+        a = np.asarray(a)
+        if a.dtype != np.float32 or a.ndim != 2 or a.shape[1] < 3 or (len(a) and a.strides[1] != 4) or (len(a) > 1 and a.strides[0] <= 0):
+            a = np.ascontiguousarray(a, np.float32).reshape(len(a), -1)
+        return a, (a.strides[0] if len(a) > 1 else 4 * a.shape[1])
+    p, ps = rows(positions)
+    b = VertexBuffers(C.sizeof(VertexBuffers), len(p), ps, 0, p.ctypes.data, None)
+    keep = [p]
+    if normals is not None:
+        m, ms = rows(normals)
+        if len(m) != len(p):
+            raise PtmiError(-1, "positions and normals differ in length")
+        b.normal_stride, b.normals = ms, m.ctypes.data
+        keep.append(m)
+    return b, keep
+
+
+MESH_NORMALS = object()  # assemble_triangles(normals=...): the mesh's own normal buffer (None there means a flat mesh)
+
+
+def assemble_triangles(mesh, positions=None, normals=MESH_NORMALS):
+    """``ptmi_assemble_triangles``: the 336-byte records ``update_vertices`` would give the context, on the host (no GPU needed).
+    ``positions`` / ``normals``: (V, 3) float32 arrays (rows may be strided views), default ``mesh``'s own; normals None: flat."""
+    lib = load_library()
+    t, keep = mesh_topology(mesh)
+    b, keep2 = _host_vertex_buffers(mesh.positions if positions is None else positions,
+                                    getattr(mesh, "normals", None) if normals is MESH_NORMALS else normals)
+    out = np.frombuffer(bytearray(max(t.n_triangles, 1) * S.Triangle.itemsize), dtype=S.Triangle)[:t.n_triangles]
+    rc = lib.ptmi_assemble_triangles(C.byref(t), C.byref(b), out.ctypes.data_as(C.c_void_p))
+    del keep, keep2
+    if rc:
+        raise PtmiError(rc, lib.ptmi_last_error(None).decode())
+    return out
+
+
 def scene_desc(scene):
     """(ptmi_scene struct pointing into contiguous copies of the scene's arrays, those arrays - keep them alive while it is used)"""
     arrays = dict(bvh=np.ascontiguousarray(scene.bvh), tri=np.ascontiguousarray(scene.triangulation),
@@ -477,6 +547,34 @@ class Backend:
         and read where they are, none crosses the bus.  Synchronous; the buffer is not written.  Returns the UpdateInfo as a dict."""
         info = UpdateInfo()
         self._check(self._lib.ptmi_update_triangles_device(self._ctx, C.c_void_p(d_triangulation), n_triangles, C.byref(info)))
+        return info.as_dict()
+
+    def bind_mesh(self, mesh):
+        """``ptmi_bind_mesh``: the topology of ``mesh`` (a ``scenes.Mesh``: face i is triangle i of the uploaded array) copied to
+        the context's first device, for ``update_vertices``.  None unbinds.  Touches nothing of the scene."""
+        if mesh is None:
+            self._check(self._lib.ptmi_bind_mesh(self._ctx, None))
+            return
+        t, keep = mesh_topology(mesh)
+        self._check(self._lib.ptmi_bind_mesh(self._ctx, C.byref(t)))
+        del keep
+
+    def update_vertices(self, positions, normals=None):
+        """New positions (and vertex normals; None: a flat mesh) for the bound mesh, from host arrays of shape (V, 3) float32
+        (rows may be strided views): the records are derived and checked on the device, the tree is refit.  Returns the
+        UpdateInfo as a dict.  What has been rendered stays: call clear() for a fresh image."""
+        b, keep = _host_vertex_buffers(positions, normals)
+        info = UpdateInfo()
+        self._check(self._lib.ptmi_update_vertices(self._ctx, C.byref(b), C.byref(info)))
+        del keep
+        return info.as_dict()
+
+    def update_vertices_device(self, n_vertices, d_positions, d_normals=None, position_stride=12, normal_stride=12):
+        """The same from device addresses on the context's first device, 16-byte aligned (``tensor.data_ptr()`` of a contiguous
+        float32 (V, 3) tensor: stride 12): nothing crosses the bus.  Synchronous; the buffers are not written."""
+        b = VertexBuffers(C.sizeof(VertexBuffers), n_vertices, position_stride, normal_stride, d_positions, d_normals)
+        info = UpdateInfo()
+        self._check(self._lib.ptmi_update_vertices_device(self._ctx, C.byref(b), C.byref(info)))
         return info.as_dict()
 
     def update_materials(self, first, materiaux):

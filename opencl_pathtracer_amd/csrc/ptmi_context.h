@@ -1,5 +1,5 @@
 // ptmi_context.h - the state behind a ptmi_ctx, grouped by WHEN IT DIES, and what the host units of libptmi.so share
-// (ptmi_api.cpp, ptmi_scene_memory.cpp, ptmi_render.cpp, ptmi_readback.cpp, ptmi_query.cpp, ptmi_paths.cpp, ptmi_guides.cpp, ptmi_denoise.cpp, ptmi_reproject.cpp, ptmi_display.cpp).  Private: not ABI, never installed.
+// (ptmi_api.cpp, ptmi_scene_memory.cpp, ptmi_render.cpp, ptmi_readback.cpp, ptmi_query.cpp, ptmi_paths.cpp, ptmi_guides.cpp, ptmi_denoise.cpp, ptmi_reproject.cpp, ptmi_display.cpp, ptmi_mesh.cpp).  Private: not ABI, never installed.
 //
 // Two lifetimes.  PER SCENE (DeviceScene, ContextScene): free_scene_memory() frees what the struct owns and assigns a
 // value-initialised one, so a new per-scene field needs no line anywhere else.  PER CONTEXT (the members DeviceState and ptmi_ctx
@@ -65,6 +65,12 @@ struct DeviceScene {
     hipEvent_t snapshot_ready[kRingSlots] = {};
     SnapshotRing ring;
     float* d_peer_copy = nullptr;  // ON devices[0]: where this device's snapshot lands before the sum (ring.landed_*)
+    // ptmi_bind_mesh / ptmi_update_vertices (ptmi_mesh.cpp), devices[0] only, owned: the bound topology as ONE allocation (the
+    // planes of mesh_assemble.h: head | uv | tail), replaced by the next bind; and where the host form's vertex buffers land
+    // (positions, then normals from the next multiple of 16), grown on demand.  The assembled records go to d_update_tris
+    char* d_mesh_topology = nullptr;
+    char* d_vertex_staging = nullptr;
+    size_t vertex_staging_bytes = 0;
 };
 
 // One device's share of a render (one process drives all of them from one host thread: every launch and copy is asynchronous).
@@ -112,6 +118,10 @@ struct ContextScene {
     UpdateFacts update;
     RefitSchedule refit;
     bool have_refit = false;
+    // ptmi_bind_mesh: is a topology bound, its vertex count, and whether it came with texture coordinates (the uv planes exist)
+    bool have_mesh = false;
+    uint32_t mesh_vertices = 0;
+    bool mesh_has_uv = false;
     // on devices[0], owned
     float* d_reduced = nullptr;    // sum of the devices' snapshots (n_devices > 1)
     uint8_t* d_display = nullptr;  // the pixels of ptmi_read_display and of ptmi_read_display_tonemapped
@@ -279,6 +289,8 @@ int quiesce(ptmi_ctx* ctx, DeviceState& d);
 int camera_check(ptmi_ctx* ctx, const char* who, const ptmi_float4* position, const ptmi_float4* direction, const ptmi_float4* right,
                  const ptmi_float4* up);
 int camera_write(ptmi_ctx* ctx, const ptmi_float4& position, const ptmi_float4& direction, const ptmi_float4& right, const ptmi_float4& up);
+// ptmi_update_triangles_device under another entry point's name: ptmi_update_vertices, whose records are its own scratch
+int update_triangles_on_device(ptmi_ctx* ctx, const char* who, const ptmi_triangle* d_tris, uint32_t triangulation_size, ptmi_update_info* info);
 // ptmi_render.cpp
 int fold_events(ptmi_ctx* ctx, DeviceState& d);
 // ptmi_readback.cpp

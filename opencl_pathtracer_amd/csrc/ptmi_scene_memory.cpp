@@ -1,6 +1,6 @@
 // ptmi_scene_memory.cpp - a scene's life on the devices: upload (ptmi_initialize_memory), the calls that rewrite what was uploaded
 // (ptmi_clear, ptmi_bind_accumulators, ptmi_set_camera, ptmi_update_triangles, ptmi_update_materials, ptmi_update_lights,
-// ptmi_set_sky, the image and variance writes) and the one place
+// ptmi_set_sky, the image and variance writes; ptmi_update_vertices, in ptmi_mesh.cpp, ends in update_triangles here) and the one place
 // where it all dies (free_scene_memory).
 // Owns the per-scene state of ptmi_context.h: writes DeviceScene / ContextScene at upload and resets them whole; the other units
 // only fill the lazily allocated parts (stage sets, snapshot buffers, d_reduced, d_display).
@@ -63,6 +63,8 @@ void ptmi_internal::free_scene_memory(ptmi_ctx* ctx)
             if (d.snapshot_ready[k]) (void)hipEventDestroy(d.snapshot_ready[k]);
         }
         if (d.d_peer_copy) (void)hipFree(d.d_peer_copy);
+        if (d.d_mesh_topology) (void)hipFree(d.d_mesh_topology);
+        if (d.d_vertex_staging) (void)hipFree(d.d_vertex_staging);
         d.scene() = DeviceScene{};
     }
     if (!ctx->dev.empty()) (void)hipSetDevice(ctx->dev[0].device);
@@ -488,6 +490,12 @@ int update_materials(ptmi_ctx* ctx, uint32_t first, const ptmi_material* materia
 }
 
 }  // namespace
+
+int ptmi_internal::update_triangles_on_device(ptmi_ctx* ctx, const char* who, const ptmi_triangle* d_tris, uint32_t triangulation_size,
+                                              ptmi_update_info* info)
+{
+    return update_triangles(ctx, who, true, d_tris, triangulation_size, info);
+}
 
 extern "C" {
 

@@ -1053,3 +1053,50 @@ def build(name, width, height):
         n = int(spec[:-1]) * {"k": 1000, "m": 1000000}[spec[-1]] if spec[-1] in "km" else int(spec)
         return random_triangles(n, width, height)
     raise ValueError(f"unknown scene {name!r}")
+
+
+# --------------------------------------------------------------------------- indexed meshes (ptmi_update_vertices)
+
+@dataclass
+class Mesh:
+    """What ``Backend.bind_mesh`` / ``update_vertices`` take: vertex buffers and a topology (include/ptmi.h: ptmi_mesh_topology,
+    ptmi_vertex_buffers).  Face i is triangle i of the triangulation it was derived from, in the face's own winding."""
+    positions: np.ndarray  # (V, 3) float32
+    normals: np.ndarray    # (V, 3) float32
+    indices: np.ndarray    # (F, 3) uint32
+    uvp: np.ndarray        # (F, 3, 2) float32, per corner in face order
+    uvn: np.ndarray        # (F, 3, 2) float32
+    mat_pos: np.ndarray    # (F,) uint32
+    mat_neg: np.ndarray    # (F,) uint32
+    ids: np.ndarray        # (F,) uint32
+
+
+def mesh_from_triangulation(tris):
+    """Any triangulation as an indexed ``Mesh``: the corners are S1..S3 with their N1..N3 and texture coordinates, welded into
+    one vertex where position AND normal agree bit for bit (so neighbours share indices), and corners 1 and 2 are swapped
+    where ``dot3(cross(S2-S1, S3-S1), N) < 0``, so that the face's winding reproduces N's side.  ``triangle_create`` of the mesh
+    gives back S1..S3, the texture coordinates and the box bit for bit; N and N1..N3 may differ in a last bit (the lost
+    original winding; a re-normalised unit vector)."""
+    tris = np.ascontiguousarray(tris)
+    n = len(tris)
+    p = np.stack([tris["S1"], tris["S2"], tris["S3"]], axis=1)[:, :, :3].astype(f32)  # (n, 3, 3)
+    m = np.stack([tris["N1"], tris["N2"], tris["N3"]], axis=1)[:, :, :3].astype(f32)
+    uvp = np.stack([tris["UVP1"], tris["UVP2"], tris["UVP3"]], axis=1).astype(f32)    # (n, 3, 2)
+    uvn = np.stack([tris["UVN1"], tris["UVN2"], tris["UVN3"]], axis=1).astype(f32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        side = _dot3(_cross3(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]), tris["N"][:, :3])
+    order = np.where((side < 0)[:, None], np.array([0, 2, 1]), np.array([0, 1, 2]))  # (n, 3)
+    rows = np.arange(n)[:, None]
+    p, m, uvp, uvn = p[rows, order], m[rows, order], uvp[rows, order], uvn[rows, order]
+    keys = np.ascontiguousarray(np.concatenate([p, m], axis=2).reshape(3 * n, 6)).view(np.uint32)
+    if n:
+        uniq, inverse = np.unique(keys, axis=0, return_inverse=True)
+    else:
+        uniq, inverse = np.zeros((0, 6), np.uint32), np.zeros(0, np.int64)
+    verts = np.ascontiguousarray(uniq).view(f32)
+    return Mesh(positions=np.ascontiguousarray(verts[:, :3]), normals=np.ascontiguousarray(verts[:, 3:]),
+                indices=np.ascontiguousarray(np.asarray(inverse).reshape(n, 3).astype(np.uint32)),
+                uvp=np.ascontiguousarray(uvp), uvn=np.ascontiguousarray(uvn),
+                mat_pos=np.ascontiguousarray(tris["materialWithPositiveNormalIndex"].astype(np.uint32)),
+                mat_neg=np.ascontiguousarray(tris["materialWithNegativeNormalIndex"].astype(np.uint32)),
+                ids=np.ascontiguousarray(tris["id"].astype(np.uint32)))
