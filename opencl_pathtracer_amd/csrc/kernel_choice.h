@@ -15,6 +15,7 @@
 #include "dev_switches.h"
 #include "leaf_cull.h"
 #include "ptmi_internal.h"
+#include "trip_choice.h"
 
 namespace ptmi_choice {
 
@@ -167,7 +168,13 @@ inline WavefrontChoice choose_wavefront(const DScene& sc, bool scheduler_stats, 
     //                           256: - / 4883 / 1876    384: 733 / - / 1969    512: 740 / 4804 / 1986    768: 742 / 4896 / 1944
     //                           1024: 737 / 4845 / 1872    2048: - / 4840 / 1718
     // (a fixed threshold of 8 waiting lanes instead of a debt measured 474 / 743 with an early build)
-    c.wait_debt = c.stack_levels >= 16u ? 768u : (c.plain ? 320u : 512u);
+    // (Never 0: the kernel asks "is path logic due" as `debt >= bound` alone, trip_choice.h, and a bound of 0 is due with no
+    // lane waiting - a wave that runs passes for ever.  Checked here where the bound is made; with_instance refuses a choice
+    // whose bound was set to 0 behind this function's back.)
+    constexpr uint32_t kWaitDebtDeep = 768, kWaitDebtPlain = 320, kWaitDebtGeneral = 512;
+    static_assert(ptmi_trip::wait_debt_bound_is_valid(kWaitDebtDeep) && ptmi_trip::wait_debt_bound_is_valid(kWaitDebtPlain) &&
+                  ptmi_trip::wait_debt_bound_is_valid(kWaitDebtGeneral), "trip_choice.h: path_logic_due needs a bound of at least 1");
+    c.wait_debt = c.stack_levels >= 16u ? kWaitDebtDeep : (c.plain ? kWaitDebtPlain : kWaitDebtGeneral);
     c.lds_bytes = wavefront_lds_bytes(c.stack_levels, c.block);
     return c;
 }
@@ -219,11 +226,13 @@ bool with_instance_of(unsigned bits, F&& f, InstanceList<BITS...>)
     return ((bits == BITS ? (f(Instance<BITS>{}), true) : false) || ...);
 }
 // Calls f(Instance<...>{}) for the instantiation `c` names and returns true; false - and no call - where the list does not
-// hold it: the caller's error, never a neighbouring instantiation.
+// hold it, or the choice carries a wait-debt bound the kernel cannot run with (trip_choice.h): the caller's error, never a
+// neighbouring instantiation.
 template <class F>
 bool with_instance(const WavefrontChoice& c, F&& f)
 {
     if (c.block != kWideBlock && c.block != kNarrowBlock) return false;
+    if (!ptmi_trip::wait_debt_bound_is_valid(c.wait_debt)) return false;
     return with_instance_of(instance_bits(c), f, Instances{});
 }
 

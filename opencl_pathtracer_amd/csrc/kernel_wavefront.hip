@@ -58,6 +58,7 @@
 #include "ptmi_device.hpp"
 #include "ptmi_shading.hpp"
 #include "ptmi_literal_path.hpp"
+#include "trip_choice.h"
 
 #include <atomic>
 #include <cstdlib>
@@ -108,6 +109,9 @@ constexpr int kHitRecordWords = 4;
 #endif
 #ifndef PTMI_WF_LEAF_RATIO
 #define PTMI_WF_LEAF_RATIO 2
+#endif
+#ifndef PTMI_WF_TRIP_CHOICE
+#define PTMI_WF_TRIP_CHOICE 1  // the trip choice of trip_choice.h ("The node trip's tail"); 0 in a variant build: the former predicates, for A/B runs
 #endif
 // a pass (up to 64 triangles, one per lane) runs when this many lanes wait at a leaf (3 triangles each on average), or when
 // the waiting triangles are kLeafRatio times as many as the lanes left to take node steps
@@ -757,6 +761,13 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
     // the debt crosses a bound: bursts of finishers are served together (and leave path logic in lockstep, which
     // keeps the following traversal trips uniform), stragglers are not waited for.
     int wait_debt = 0;
+    constexpr bool kMaskedStep = PLAIN || CULL || BLOCK == kWfBlockNarrow;  // (the loop below: a trip's kind as the node step's exec mask)
+    // The trip choice of trip_choice.h: one compare each for "path logic is due" and "a pass is due".  In the instantiations whose
+    // trip's kind is the step's exec mask, the statistics builds apart; the others keep the former predicates and compile to what
+    // they were (with the shorter ones the strict <0,0,0,0,1> reloads a fourth spilled register inside the loop, where
+    // tests/test_resources.py allows it three, and the statistics builds of the culling kernel get their trips' copies back:
+    // 16 v_mov on a node trip's way in).
+    constexpr bool kTripChoice = kMaskedStep && !STATS && PTMI_WF_TRIP_CHOICE;
     // lane states: triangles pending (idle and dead lanes keep an empty range) / `cur` is an inner-node reference /
     // neither: the query is finished (REF_NONE) or there is no path (REF_IDLE) -> path logic / REF_DEAD
     bool pending, want_inner, want_post;
@@ -772,7 +783,7 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
         want_inner = !pending & has_node;
         step_mask = m_i;
         want_post = !pending & !has_node & (cur != REF_DEAD);
-        any_lane = (m_t | m_i | m_p) != 0ull;
+        any_lane = kTripChoice ? ptmi_trip::any_lane(b_t, b_n, b_dead) : (m_t | m_i | m_p) != 0ull;
         n_t = __popcll(m_t); n_i = __popcll(m_i); n_p = __popcll(m_p);
         // (scalars, and to stay scalars: left alone the compiler decides what the next trip is with packed 16-bit VECTOR
         // multiplies.  Going further - the two decisions as integer max / min arithmetic the loop branches on - measured
@@ -785,7 +796,10 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
     // (Tried: a wait debt of its own for the lanes whose shadow query has finished - the expensive kind of path logic - so
     // that each kind is served at a higher lane count: 809 -> 685-700 Msamples/s; lanes kept waiting are lanes that do not traverse.)
     const int wait_debt_bound = (int)sc.wait_debt;
-    auto path_logic_due = [&]() { return n_p > 0 && wait_debt >= wait_debt_bound; };
+    auto path_logic_due = [&]() {
+        if (kTripChoice) return ptmi_trip::path_logic_due(wait_debt, wait_debt_bound);
+        return n_p > 0 && wait_debt >= wait_debt_bound;
+    };
     auto nothing_traverses = [&]() { return n_t == 0 && n_i == 0; };
     // Loop nest: path logic in the outer loop, traversal trips in an inner loop of their own, so that the traversal
     // state is loop-carried through ONE small loop (as one if/else in one loop the two big branches were merged through
@@ -796,7 +810,10 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
         if (!any_lane) break;
         // node trips for the lanes at inner nodes; a leaf pass when enough lanes wait at leaves (or as many as run)
         auto to_path_logic = [&]() { return path_logic_due() || nothing_traverses(); };
-        auto pass_is_due = [&]() { return n_t >= kLeafLanes || (n_t > 0 && 3 * n_t >= kLeafRatio * n_i); };
+        auto pass_is_due = [&]() {
+            if (kTripChoice) return ptmi_trip::pass_is_due<kLeafLanes, kLeafRatio>(n_t, n_i);
+            return n_t >= kLeafLanes || (n_t > 0 && 3 * n_t >= kLeafRatio * n_i);
+        };
         // (One loop for both kinds of trip.  Tried: node trips in an inner loop of their own - same schedule, 851 -> 807
         // Msamples/s; the node step of the lanes at inner nodes in the same trip as a pass, its record loads in flight
         // during the pass - 894 -> 791, the sixteen registers held across the pass spill; requesting the record of a lane's
@@ -829,7 +846,6 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
         // tests/test_path_logic_loads.py pins for them (default arithmetic <0,0,0,0,0> 30 for 29 and <0,1,0,0,1> 44 for 26,
         // strict <0,1,0,0,0> 58 for 57, each with one full wait more in the pass), and the strict <0,0,0,0,1> reloads a
         // fourth spilled register inside this loop (tests/test_resources.py allows it three).
-        constexpr bool kMaskedStep = PLAIN || CULL || BLOCK == kWfBlockNarrow;
         while (!to_path_logic()) {
             if (!kMaskedStep) {
                 if (pass_is_due()) {

@@ -4,7 +4,8 @@ scratch bytes, occupancy, and the number of scratch instructions INSIDE the trav
 instruction mix of that loop, what a trip of it costs beyond its work (v_mov, the two trip paths' instruction counts, the register
 copies and full waits around the node step: trip_loop_copies), the kernel's flat instructions, the memory chain of a path-logic pass (the outer loop's body:
 vector loads, scalar loads, full vector-memory waits), and the waits of the node step: the s_waitcnt sequence from the
-step's four record loads to the first vmcnt(0) (the first wait must not be the one that waits for all four).
+step's four record loads to the first vmcnt(0) (the first wait must not be the one that waits for all four), and
+the node trip's tail: the stack's LDS reads and the waits behind the step's push (node_trip_tail).
 usage: tools/kernel_resources.py [source tree, default the repo] [arithmetic 0|1, default 1]"""
 import os
 import re
@@ -211,6 +212,31 @@ def trip_loop_copies(blocks):
             "full waits in": sum(l.startswith("s_waitcnt") and "vmcnt(0)" in l for l in way_in)}
 
 
+def node_trip_tail(blocks):
+    """The node trip's tail ("The node trip's tail"): the node-trip path from the step's push - the ds_write_b32
+    behind the record loads - to the back edge, in layout order.  -> dict(reads: the ds_read instructions there, read points:
+    the runs of them that no s_waitcnt divides, full lgkm waits: the s_waitcnt that carry lgkmcnt(0), scalar / vector: the
+    instructions of that stretch, without waits and nops); None where the loop has no node step."""
+    p = trip_paths(blocks)
+    if p is None:
+        return None
+    behind = sorted(_reach(blocks, p["node"], p["node_path"]))
+    push = next(((i, k) for i in behind for k, l in enumerate(blocks[i]["lines"]) if l.startswith("ds_write_b32")), None)
+    if push is None:
+        return None
+    lines = blocks[push[0]]["lines"][push[1] + 1:] + [l for i in behind if i > push[0] for l in blocks[i]["lines"]]
+    points, open_run = 0, False
+    for l in lines:
+        if l.startswith("ds_read"):
+            points += not open_run
+            open_run = True
+        elif l.startswith("s_waitcnt"):
+            open_run = False
+    vector, scalar = _mix(lines)
+    return {"reads": sum(l.startswith("ds_read") for l in lines), "read points": points,
+            "full lgkm waits": sum(l.startswith("s_waitcnt") and "lgkmcnt(0)" in l for l in lines), "vector": vector, "scalar": scalar}
+
+
 def resources(tree=ROOT, arithmetic=1, extra=()):
     out, remarks = compile_to_assembly(tree, arithmetic, extra)
     res = {}
@@ -236,6 +262,7 @@ def resources(tree=ROOT, arithmetic=1, extra=()):
         v.update(outer_loop_memory(blocks))
     for name, blocks in kernel_cfg(out).items():
         res[name]["trip loop"] = trip_loop_copies(blocks)
+        res[name]["tail"] = node_trip_tail(blocks)
     return res
 
 
@@ -264,10 +291,12 @@ if __name__ == "__main__":
           "before it, kernel | path-logic pass (the outer loop's body): vector loads, scalar loads, full vector-memory waits | "
           "node step: load offsets, then its waits | trip loop: v_mov in the loop; node-trip path vector, scalar instructions; leaf-pass path "
           "vector, scalar; register copies on a node trip's way in (header to the first record load), full vector-memory waits there, "
-          "copies on its way out (behind the step's last LDS operation to the back edge)")
+          "copies on its way out (behind the step's last LDS operation to the back edge) | node trip's tail (the push to the back edge): "
+          "LDS reads, read points (runs of reads no wait divides), waits with lgkmcnt(0), vector, scalar instructions")
     for k in sorted(res):
         v = res[k]
         offsets, waits, closed = v["node step"] or ([], [], False)
         print("   ".join(k[:5]) + ("  " + k[5:] if len(k) > 5 else ""), "|", v["VGPRs"], v["VGPRs Spill"], v["ScratchSize"], v["Occupancy"], "|", v["loop scratch"], v["loop VALU"], v["loop SALU"],
               v["loop LDS"], v["loop VMEM"], "|", v["loop flat"], v["flat before loop"], v["flat"], "|",
-              v["pass vector loads"], v["pass scalar loads"], v["pass full waits"], "|", ",".join(map(str, offsets)), "|", " / ".join(waits) + ("" if closed else " / (no vmcnt(0) before the next load)"), "|", trip_loop_text(v["trip loop"]))
+              v["pass vector loads"], v["pass scalar loads"], v["pass full waits"], "|", ",".join(map(str, offsets)), "|", " / ".join(waits) + ("" if closed else " / (no vmcnt(0) before the next load)"), "|", trip_loop_text(v["trip loop"]), "|",
+              " ".join(str(x) for x in v["tail"].values()) if v.get("tail") else "-")
