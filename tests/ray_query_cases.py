@@ -89,7 +89,9 @@ class Walker:
         return dict(point=st["point"], squared_distance=st["sqd"], s=st["s"], t=st["t"], triangle_id=st["id"],
                     front=_front(self.normal[st["id"]], direction), box_tests=n_box, triangle_tests=n_tri)
 
-    def walk(self, origin, direction, limit=np.inf, any_hit=False):
+    def walk(self, origin, direction, limit=np.inf, any_hit=False, on_push=None):
+        """on_push: called with the number of pending entries after every push (stack_depth_cases.py reads the stack's
+        occupancy off it); it changes nothing of the walk."""
         o, d = _c4(origin), _c4(direction)
         positive = _signs(direction)
         st = dict(sqd=float(f32(limit)))
@@ -114,6 +116,8 @@ class Walker:
                 if h_near:
                     if h_far:
                         stack.append(far)
+                        if on_push is not None:
+                            on_push(len(stack))
                     cur = near
                 elif h_far:
                     cur = far

@@ -13,7 +13,8 @@ check.  The trees of that depth among tests/bvh_stress_cases.py (deep_chain's 27
 triangles) are made of coordinates beyond 2^21, which the upload answers with the NaN-safe kernel in wide workgroups - they
 cannot reach the narrow ones.  So the deep scene is the one tests/test_reference_default_gpu.py already uses for them: the
 configs[4] stand-in (23 levels), at this module's image size.  Its materials are textured: general shading, whatever the
-switch says.
+switch says.  (Chains that do reach the narrow workgroups, with every level of their stack in use: the hand-made decks of
+tests/test_stack_depth_gpu.py, whose coordinates stay small.)
 """
 import os
 
