@@ -221,7 +221,8 @@ int ptmi_unpin_host_buffer(ptmi_ctx* ctx, void* buffer);
  *   ptmi_snapshot(slot)       queued behind the launches issued so far: a device-side copy of the accumulators
  *                             (every device of a multi-GPU render) into ring slot `slot` < PTMI_MAX_SNAPSHOT_SLOTS;
  *   ptmi_read_snapshot(slot)  waits for that copy only (not for launches queued after it), sums the devices'
- *                             partial images on devices[0], copies the result to the host buffers; with both
+ *                             partial images on devices[0] (any image size, an odd number of pixels too), copies
+ *                             the result to the host buffers; with both
  *                             pointers NULL it only waits until the snapshot has been taken (clFinish of that image).
  * Loop of a viewer: render(k+1); read_snapshot(k); show; snapshot(k+1) ...  (csrc/PathTracer_HIP.cpp).
  *   ptmi_render_snapshots(first, n, first_slot)   ptmi_render(first, n) that ALSO leaves a snapshot after every one of
@@ -232,6 +233,43 @@ int ptmi_unpin_host_buffer(ptmi_ctx* ctx, void* buffer);
 int ptmi_snapshot(ptmi_ctx* ctx, uint32_t slot);
 int ptmi_render_snapshots(ptmi_ctx* ctx, uint32_t first_iteration, uint32_t n_iterations, uint32_t first_slot);
 int ptmi_read_snapshot(ptmi_ctx* ctx, uint32_t slot, float* image_color, float* image_ray_nb);
+
+/* ---- A rectangle of the image ----------------------------------------------------------------------------------------------
+ * The render region of a look-development session (re-render the one object whose material changed, put more samples into a
+ * noisy corner) and the unit by which callers share a frame between contexts or machines: tiles. */
+typedef struct ptmi_region { uint32_t x, y, width, height; } ptmi_region;   /* pixels [x, x+width) x [y, y+height); row 0 first, as ptmi_read_image */
+
+/* ptmi_render for the work-items of a rectangle: traces exactly the paths ptmi_render(first_iteration, n_iterations) traces
+ * for the work-items (gx, gy) inside `region` and no other.  A path's seed index is still gx + gy * W + it * W * H over the
+ * FULL image; its sample, its camera ray and, under super_sampling, its stop criterion are those of ptmi_render, in the
+ * context's arithmetic.  It is ptmi_render with fewer work-items, not a second renderer: every mode ptmi_render serves is
+ * served - super_sampling, PTMI_FLAG_MEGAKERNEL, PTMI_FLAG_RUSSIAN_ROULETTE, PTMI_FLAG_SOURCE_SEED, scenes with a
+ * ptmi_literal_kernel_reason and scenes whose records can yield NaN distances, ptmi_bind_accumulators, ptmi_set_stream.
+ *   JITTERED / UNIFORM   every pixel of the region gains, in iteration order, bit for bit what ptmi_render would add to it; no
+ *                        word of any pixel outside the region is read or written.
+ *   RANDOM               the region selects WORK-ITEMS; their samples land where they land, possibly outside the region,
+ *                        atomically as in ptmi_render.
+ *   statistics           the histograms, ptmi_counters and the scheduler and invariant statistics gain what those paths
+ *                        contribute and nothing else.
+ *   several devices      the iteration ids spread over the listed devices exactly as for ptmi_render, each device over the
+ *                        same region.
+ * Asynchronous on the context's stream like ptmi_render, and bracketed for ptmi_kernel_time like it; at most the context's
+ * iterations per kernel launch (1 with super_sampling), as for ptmi_render.  A region caller is NEVER RENDERED AHEAD OF: the
+ * call adopts no launch that ran ahead, launches in flight ahead are dropped as for any call that leaves the pattern, and none
+ * is left in flight behind it; nothing a caller can read differs.  A region equal to the whole image goes the same way as any
+ * other region - it does not delegate to ptmi_render; the two are equal in everything a caller can read.
+ * Returns PTMI_ERR_STATE before ptmi_initialize_memory; PTMI_ERR_INVALID_ARGUMENT for a NULL region, a region that does not lie
+ * inside the image (x + width and y + height are checked in 64 bits) or an iteration range that overflows 32 bits.  A width or
+ * height of 0, or n_iterations == 0, is PTMI_OK and launches nothing.  After any error the context renders as before.
+ * Not offered for a region: ptmi_render_snapshots, the guides, ptmi_denoise, reprojection; a list of rectangles is a loop. */
+int ptmi_render_region(ptmi_ctx* ctx, const ptmi_region* region, uint32_t first_iteration, uint32_t n_iterations);
+
+/* The region of what ptmi_read_image would return at this moment: image_color = float4[width * height], image_ray_nb =
+ * float[width * height], densely packed, rows first.  Either pointer may be NULL.  Waits as ptmi_read_image does; the shares of
+ * several devices are summed first, as ptmi_read_image does.  One strided device-to-host copy per plane - straight into the
+ * destination where the caller has page-locked it (ptmi_pin_host_buffer) -, so 20 bytes per pixel of the REGION cross the bus.
+ * Statuses as for ptmi_render_region (an empty region copies nothing). */
+int ptmi_read_region(ptmi_ctx* ctx, const ptmi_region* region, float* image_color, float* image_ray_nb);
 
 /* The inverse of ptmi_read_image: load the accumulators (e.g. to resume a render saved earlier, or to accumulate on top of
  * another device's partial result).  Either pointer may be NULL (left as is).  Synchronises first. */

@@ -215,7 +215,7 @@ ABI_SYMBOLS = ["ptmi_setup_context", "ptmi_initialize_memory", "ptmi_render", "p
                "ptmi_denoise", "ptmi_denoise_device", "ptmi_trace_paths", "ptmi_trace_paths_device",
                "ptmi_reproject_device", "ptmi_set_camera_reprojected",
                "ptmi_display_table", "ptmi_read_display_tonemapped", "ptmi_display_device", "ptmi_luminance_histogram",
-               "ptmi_luminance_histogram_device"]
+               "ptmi_luminance_histogram_device", "ptmi_render_region", "ptmi_read_region"]
 
 QUERY_CLOSEST, QUERY_ANY = 0, 1  # ptmi.h: PTMI_QUERY_*
 
@@ -318,6 +318,8 @@ def load_library():
     lib.ptmi_display_device.argtypes = [vp, C.POINTER(DisplayParams), vp, vp, vp]
     lib.ptmi_luminance_histogram.argtypes = [vp, vp]
     lib.ptmi_luminance_histogram_device.argtypes = [vp, vp, vp, vp]
+    lib.ptmi_render_region.argtypes = [vp, vp, u32, u32]
+    lib.ptmi_read_region.argtypes = [vp, vp, vp, vp]
     lib.ptmi_device_share.argtypes = [u32, u32, u32, u32, C.POINTER(u32), C.POINTER(u32)]
     lib.ptmi_device_share.restype = None
     _lib = lib
@@ -768,6 +770,27 @@ class Backend:
     # -- one launch of the loop body of OpenCL_RunKernel, generalised to a range ----------
     def render(self, first_iteration, n_iterations):
         self._check(self._lib.ptmi_render(self._ctx, first_iteration, n_iterations))
+
+    @staticmethod
+    def region(x, y, width, height):
+        """ptmi_region as a one-element ``structs.REGION`` array: pixels [x, x + width) x [y, y + height), row 0 first."""
+        r = np.zeros(1, S.REGION)
+        r["x"], r["y"], r["width"], r["height"] = x, y, width, height
+        return r
+
+    def render_region(self, x, y, width, height, first_iteration, n_iterations):
+        """render() for the work-items of one rectangle (ptmi_render_region): the very paths render() traces there, nothing
+        outside read or written with the JITTERED / UNIFORM samplers."""
+        r = self.region(x, y, width, height)
+        self._check(self._lib.ptmi_render_region(self._ctx, _ptr(r), first_iteration, n_iterations))
+
+    def read_region(self, x, y, width, height, out=None):
+        """(color float32[height,width,4], count float32[height,width]): the rectangle of what read_image() would return now
+        (ptmi_read_region); ``out`` = (color, count) arrays to fill, DMA'd into directly if page-locked with pin_host_buffer."""
+        r = self.region(x, y, width, height)
+        color, count = out if out is not None else (np.empty((height, width, 4), np.float32), np.empty((height, width), np.float32))
+        self._check(self._lib.ptmi_read_region(self._ctx, _ptr(r), None if color is None else _ptr(color), None if count is None else _ptr(count)))
+        return color, count
 
     def synchronize(self):
         self._check(self._lib.ptmi_synchronize(self._ctx))

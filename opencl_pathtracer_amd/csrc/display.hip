@@ -186,9 +186,16 @@ struct ImageParts {
     const float* p[PTMI_MAX_DEVICES];
 };
 __global__ void __launch_bounds__(256) sum_images_kernel(float* __restrict__ out, const ImageParts parts, const uint32_t n_parts,
-                                                         const size_t n_quads)
+                                                         const size_t n_quads, const uint32_t n_tail)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == n_quads) {  // the floats behind the last whole quad (an image of an odd number of pixels: 5 floats each), in the same order
+        for (uint32_t j = 0; j < n_tail; j++) {
+            float s = parts.p[0][4 * n_quads + j];
+            for (uint32_t k = 1; k < n_parts; k++) s = s + parts.p[k][4 * n_quads + j];
+            out[4 * n_quads + j] = s;
+        }
+    }
     if (i >= n_quads) return;
     float4 s = reinterpret_cast<const float4*>(parts.p[0])[i];
     for (uint32_t k = 1; k < n_parts; k++) {
@@ -219,15 +226,16 @@ int launch_add_counters(unsigned long long* dst, const unsigned long long* src, 
 
 int launch_sum_images(float* out, const float* const* parts, uint32_t n_parts, size_t n_floats, void* stream, std::string* err)
 {
-    if (n_parts == 0 || n_parts > PTMI_MAX_DEVICES || (n_floats & 3u)) {
-        if (err) *err = "launch_sum_images: bad part count or a float count that is not a multiple of 4";
+    if (n_parts == 0 || n_parts > PTMI_MAX_DEVICES) {
+        if (err) *err = "launch_sum_images: bad part count";
         return PTMI_ERR_INVALID_ARGUMENT;
     }
     ptmi_dev::ImageParts ip{};
     for (uint32_t k = 0; k < n_parts; k++) ip.p[k] = parts[k];
     const size_t n_quads = n_floats / 4;
-    hipLaunchKernelGGL(ptmi_dev::sum_images_kernel, dim3((unsigned)((n_quads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, ip,
-                       n_parts, n_quads);
+    const uint32_t n_tail = (uint32_t)(n_floats & 3u);  // (every buffer comes from hipMalloc: the quads are aligned)
+    hipLaunchKernelGGL(ptmi_dev::sum_images_kernel, dim3((unsigned)((n_quads + 1 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, ip,
+                       n_parts, n_quads, n_tail);
     return launch_status(hipGetLastError(), "sum_images_kernel", err);
 }
 

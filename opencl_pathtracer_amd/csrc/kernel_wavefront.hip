@@ -250,7 +250,12 @@ __device__ __forceinline__ void give_path_up(V4& radiance, V4& transfer, uint32_
 // in index order whatever the distances are, and its limit never changes.)  Clean scenes run the instantiations without it.
 // BLOCK: lanes per workgroup (kWfBlock, or kWfBlockNarrow for deep trees: see there).
 // CULL: leaves beyond a query's limit are counted instead of tested (leaf_cull.h; precomputed records only).
-template <bool STATS, bool PRE, bool SS, bool PLAIN = false, bool NANSAFE = false, int BLOCK = 256, bool CULL = false>
+// REGION: the launch renders the rectangle `region_arg` of the image (ptmi_render_region; render_region.h).  false - every
+// launch of ptmi_render - fixes the region to the whole image, and the kernel compiles to what it was before regions existed:
+// the four scalars, kept alive across both loops as plain arguments, cost EVERY production instantiation one to three full
+// vector-memory waits in the path-logic pass (tools/kernel_resources.py; tests/test_path_logic_loads.py pins them).  So only
+// region calls pay for them.  Every instantiation of the list (kernel_choice.h) exists in both forms.
+template <bool STATS, bool PRE, bool SS, bool PLAIN = false, bool NANSAFE = false, int BLOCK = 256, bool CULL = false, bool REGION = false>
 __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN_WAVES_GENERAL) render_wavefront_kernel(
                                                                     const DScene* __restrict__ scene_in_memory, const DWarm sc_arg, const uint32_t first_iteration,
                                                                     const uint32_t n_iterations, const uint32_t iteration_stride,
@@ -258,13 +263,20 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
                                                                     uint32_t* __restrict__ job_counter,
                                                                     const uint32_t stack_levels,
                                                                     float* __restrict__ stage,
-                                                                    uint32_t* __restrict__ stage_stats)
+                                                                    uint32_t* __restrict__ stage_stats,
+                                                                    const Region region_arg)
 {
     // traversal stacks: [level][lane], one dword per entry, as many levels as the tree is deep (the reference
     // reserves 30, FullKernel.cl:627; the deepest possible chain of pending far children is the tree depth)
     // PLAIN also fixes the JITTERED sampler, no Russian roulette and ONE light (the launch only picks it then): constants below
     DWarm sc = sc_arg;
     if (PLAIN) { sc.sampler = PTMI_SAMPLER_JITTERED; sc.russian_roulette = 0; sc.n_lights = 1; }  // ... and ONE light
+    // (four scalars, not the struct; REGION false: the whole image, and the code below is the code of before regions.  The hand-out
+    // and the slot below take render_region.h's region_tile_pixel and region_slot as the header's MACROS, in place: through the
+    // functions the non-REGION instantiations no longer compile to the very code the pinned figures were read off - tried, both
+    // arithmetics, profiles/render_region_ab.txt.  The text is the one the CPU model of the tests plays.)
+    const uint32_t reg_x = REGION ? region_arg.x : 0u, reg_y = REGION ? region_arg.y : 0u;
+    const uint32_t reg_w = REGION ? region_arg.w : sc.width, reg_h = REGION ? region_arg.h : sc.height;
     constexpr bool kOneLight = PLAIN;  // (nothing gathered across shadow queries, no light index: five registers fewer per lane)
     constexpr int kWfBlock = BLOCK;  // (shadows the namespace's: every LDS stride below is the workgroup's own width)
     // The top entry of a lane's traversal stack ALSO in a register (round 4): a pop takes the register and the LDS read that refills
@@ -355,7 +367,7 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
     // | kHitFound: the query has found a triangle
     constexpr uint32_t kHitFront = 0x80000000u, kHitFound = 0x40000000u;
     constexpr int kWordS = 1, kWordT = 2, kWordTri = 3;  // (word 0: the ray parameter)
-    const uint32_t tiles_x = (sc.width + 7u) >> 3;
+    const uint32_t tiles_x = (reg_w + 7u) >> 3;  // (region_tiles_x: tiles cover the launch's region from its own origin, render_region.h)
     const bool owns_pixel = sc.sampler != PTMI_SAMPLER_RANDOM;
     const uint32_t n_tiles = (n_jobs / n_iterations) >> 6;
     uint32_t q_cur = blockIdx.x % (uint32_t)kQueues, q_done = 0;  // wave-uniform: current queue, queues seen empty
@@ -364,7 +376,8 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
     // Whether a lane has a path in flight, or is done for good, is kept IN `cur` (REF_IDLE / REF_DEAD) so that the
     // wave's three step masks come from three integer compares; the two bools below only live inside a path-logic trip.
     bool alive = true, need_path = true;
-    // The path's job as ONE word: its slot in the staging arrays = it_local * W * H + y * W + x.  Iteration ids of this
+    // The path's job as ONE word: its slot in the staging arrays = it_local * w * h + (y - y0) * w + (x - x0) over the launch's
+    // region (x0, y0, w, h) - the whole image for ptmi_render (render_region.h: region_slot).  Iteration ids of this
     // launch: first_iteration + it_local * iteration_stride, it_local < n_iterations (the stride is the number of devices
     // that share a render: each takes the ids of its own residue class, ptmi_api.cpp).  Pixel and iteration are only needed
     // when the path starts; everything a lane keeps across traversal trips costs a register of the 96 (5 waves per SIMD).
@@ -449,7 +462,7 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
             // RANDOM sampler: the sample lands on an arbitrary pixel; the reference races there (:1339-1345).  The sample
             // position is drawn again from the path's seed (the first two draws, :1137-1141) instead of being kept.
             uint32_t gx, gy, it;
-            decode_slot(slot, sc.width, sc.width * sc.height, first_iteration, iteration_stride, gx, gy, it);
+            decode_slot(slot, reg_x, reg_y, reg_w, reg_w * reg_h, first_iteration, iteration_stride, gx, gy, it);
             int seed0 = lcg_seed(gx, gy, sc.width, sc.height, it, sc.source_seed != 0);
             float sample_x, sample_y;
             draw_sample(sc, gx, gy, it, seed0, sample_x, sample_y);
@@ -977,7 +990,7 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
         // workgroup's XCD group (blockIdx % 8: which blocks share an XCD and its L2, not which XCD - a speed matter
         // only) and moves on to the next one when its queue is exhausted, so neighbouring tiles run on one L2.
         bool got_job = false;
-        uint32_t gx = 0, gy = 0, it_local = 0;  // of the new job; live only until the path has started, below
+        uint32_t gx = 0, gy = 0, it_local = 0;  // of the new job (the pixel RELATIVE to the region's origin until the path starts); live only until the path has started, below
         const bool want_job = want_post && need_path;
         const unsigned long long m_job = __ballot(want_job);
         if (m_job != 0ull) {
@@ -1004,9 +1017,10 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
                     const uint32_t tile_in_q = unit / n_iterations;
                     it_local = unit - tile_in_q * n_iterations;
                     const uint32_t tile = tile_lo + tile_in_q;
-                    gx = (tile % tiles_x) * 8u + (in_tile & 7u);
-                    gy = (tile / tiles_x) * 8u + (in_tile >> 3);
-                    got_job = gx < sc.width && gy < sc.height;  // edge tiles: pixel outside the image, ask again
+                    // (region_tile_pixel, render_region.h: its text, in place)
+                    gx = PTMI_REGION_TILE_RX(tile, tiles_x, in_tile);
+                    gy = PTMI_REGION_TILE_RY(tile, tiles_x, in_tile);
+                    got_job = gx < reg_w && gy < reg_h;  // edge tiles: pixel outside the region, ask again
                 }  // else: the queue ran out under this wave; the lane asks again in the next pass
             }
             if (open && base + n_want > q_size) {  // wave-uniform: this queue is (now) exhausted
@@ -1020,7 +1034,8 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
             // (the lane-per-ray kernels make the same ray in primary_ray, ptmi_literal_path.hpp)
             if (got_job) {
                 const uint32_t it = first_iteration + it_local * iteration_stride;
-                slot = it_local * (sc.width * sc.height) + gy * sc.width + gx;
+                slot = PTMI_REGION_SLOT(reg_w, reg_h, gx, gy, it_local);  // (region_slot, render_region.h: its text, in place)
+                if (REGION) { gx += reg_x; gy += reg_y; }  // the work-item: seed and sample are the full image's
                 seed = lcg_seed(gx, gy, sc.width, sc.height, it, sc.source_seed != 0);
                 float sample_x, sample_y;
                 draw_sample(sc, gx, gy, it, seed, sample_x, sample_y);
@@ -1051,7 +1066,8 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
                     skip = (double)lcg_random(seed) > (double)fdiv(100 * sigma2_n, as_global(cs.x2inv)[idx]) + 0.05;
                 }
                 if (skip) {
-                    if (owns_pixel) as_global(cold_scene().stage_flag)[gy * sc.width + gx] = 0.f;  // returns before statistics and accumulation
+                    // (stage_flag is indexed like the staging slots of the ONE iteration such a launch renders: region-relative)
+                    if (owns_pixel) as_global(cold_scene().stage_flag)[(gy - reg_y) * reg_w + (gx - reg_x)] = 0.f;  // returns before statistics and accumulation
                     need_path = true;
                 } else
                 if (sc.max_depth > 0) {
@@ -1155,7 +1171,8 @@ __global__ void __launch_bounds__(BLOCK, PLAIN ? PTMI_WF_MIN_WAVES : PTMI_WF_MIN
 template <bool PRE>
 __global__ void __launch_bounds__(kBlock) redo_poisoned_kernel(const DScene sc, const uint32_t first_iteration, const uint32_t n_iterations,
                                                                const uint32_t iteration_stride, float* __restrict__ stage,
-                                                               uint32_t* __restrict__ stage_stats, const uint32_t* __restrict__ job_counter)
+                                                               uint32_t* __restrict__ stage_stats, const uint32_t* __restrict__ job_counter,
+                                                               const Region region)
 {
     if (__builtin_nontemporal_load(&job_counter[1]) == 0u) return;  // (the same for every lane of the grid)
     __shared__ uint32_t stack_mem[kStackDepth * kBlock];
@@ -1165,10 +1182,10 @@ __global__ void __launch_bounds__(kBlock) redo_poisoned_kernel(const DScene sc, 
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     if (tid < PTMI_COUNTER_SPLITS * kSplitWords) block_counters[tid] = 0;
     __syncthreads();
-    const uint32_t n_pixels = sc.width * sc.height, n_slots = n_pixels * n_iterations;
+    const uint32_t n_slots = region_pixels(region) * n_iterations;  // the slots the launch wrote, all of them and no other (render_region.h)
     auto trace_slot = [&](const uint32_t slot) {
         uint32_t gx, gy, it;
-        decode_slot(slot, sc.width, n_pixels, first_iteration, iteration_stride, gx, gy, it);
+        decode_slot(slot, region, first_iteration, iteration_stride, gx, gy, it);
         float sx, sy;
         uint32_t depth = 0, n_seg = 0, n_shadow = 0;
         PathCounters pc;
@@ -1222,7 +1239,8 @@ __global__ void __launch_bounds__(kBlock) redo_poisoned_kernel(const DScene sc, 
 // falls on (FullKernel.cl:1333-1349) - its three histogram bins and its counts.
 template <bool PRE>
 __global__ void __launch_bounds__(kBlock) redo_random_kernel(const DScene sc, const uint32_t first_iteration, const uint32_t n_iterations,
-                                                             const uint32_t iteration_stride, const uint32_t* __restrict__ job_counter)
+                                                             const uint32_t iteration_stride, const uint32_t* __restrict__ job_counter,
+                                                             const Region region)
 {
     if (__builtin_nontemporal_load(&job_counter[1]) == 0u) return;
     __shared__ uint32_t stack_mem[kStackDepth * kBlock];
@@ -1231,10 +1249,9 @@ __global__ void __launch_bounds__(kBlock) redo_random_kernel(const DScene sc, co
     if (tid <= C_TRI) block_counters[tid] = 0;
     __syncthreads();
     const uint32_t listed = job_counter[2], n = listed < kGiveUpListCap ? listed : kGiveUpListCap;
-    const uint32_t n_pixels = sc.width * sc.height;
     for (uint32_t i = blockIdx.x * kBlock + tid; i < n; i += gridDim.x * kBlock) {
         uint32_t gx, gy, it;
-        decode_slot(job_counter[kGiveUpListFirst + i], sc.width, n_pixels, first_iteration, iteration_stride, gx, gy, it);
+        decode_slot(job_counter[kGiveUpListFirst + i], region, first_iteration, iteration_stride, gx, gy, it);
         float sx, sy;
         uint32_t depth = 0, n_seg = 0, n_shadow = 0;
         PathCounters pc;
@@ -1278,19 +1295,28 @@ __global__ void __launch_bounds__(1024) histogram_staged_kernel(uint32_t* __rest
     }
 }
 
+// Slot q of one iteration of a launch over `region` -> the pixel's index in the image: the ONE place where a slot becomes a
+// pixel (render_region.h).  (Rows as wide as the image - ptmi_render's launches among them - are contiguous: no division.)
+__device__ __forceinline__ uint32_t pixel_of_slot(const Region& region, uint32_t q, uint32_t width)
+{
+    return region.w == width ? region.y * width + q : region_pixel(region, q, width);
+}
+
 // Adds the staged radiances of one launch to the accumulators, per pixel in iteration order:
 // sumAfter = sumBefore + radiance; nRayAfter = nRayBefore + 1 (FullKernel.cl:1339-1345), n_iterations times.
+// One lane per slot of an iteration (n_pixels = the region's pixels): no pixel outside the region is read or written.
 __global__ void __launch_bounds__(256) accumulate_staged_kernel(float* __restrict__ image_color,
                                                                  float* __restrict__ image_ray_nb,
                                                                  const float* __restrict__ stage, const uint32_t n_pixels,
-                                                                 const uint32_t n_iterations)
+                                                                 const uint32_t n_iterations, const Region region, const uint32_t width)
 {
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n_pixels) return;
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n_pixels) return;
+    const uint32_t p = pixel_of_slot(region, q, width);
     float4 sum = reinterpret_cast<const float4*>(image_color)[p];
     float count = image_ray_nb[p];
     for (uint32_t k = 0; k < n_iterations; k++) {
-        const float4 r = reinterpret_cast<const float4*>(stage)[(size_t)k * n_pixels + p];
+        const float4 r = reinterpret_cast<const float4*>(stage)[(size_t)k * n_pixels + q];
         sum.x = sum.x + r.x; sum.y = sum.y + r.y; sum.z = sum.z + r.z; sum.w = sum.w + r.w;
         count = count + 1.f;
     }
@@ -1305,13 +1331,15 @@ __global__ void __launch_bounds__(256) accumulate_staged_ss_kernel(float* __rest
                                                                     float* __restrict__ image_v,
                                                                     const float* __restrict__ stage,
                                                                     const float* __restrict__ stage_flag,
-                                                                    const uint32_t n_pixels, const uint32_t iteration)
+                                                                    const uint32_t n_pixels, const uint32_t iteration,
+                                                                    const Region region, const uint32_t width)
 {
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n_pixels) return;
-    if (stage_flag[p] == 0.f) return;
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;  // the slot: stage and stage_flag are the launch's, region-relative
+    if (q >= n_pixels) return;
+    if (stage_flag[q] == 0.f) return;
+    const uint32_t p = pixel_of_slot(region, q, width);  // the pixel: the accumulators are the image's
     const float4 before = reinterpret_cast<const float4*>(image_color)[p];
-    const float4 r = reinterpret_cast<const float4*>(stage)[p];
+    const float4 r = reinterpret_cast<const float4*>(stage)[q];
     const float4 after = make_float4(before.x + r.x, before.y + r.y, before.z + r.z, before.w + r.w);
     const float n_before = image_ray_nb[p];
     const float n_after = n_before + 1.f;
@@ -1403,6 +1431,8 @@ struct WavefrontLaunch {
     uint32_t* job_counter;
     float* stage;
     uint32_t* stage_stats;
+    Region region;
+    bool region_call;  // ptmi_render_region (the whole image included): the REGION form of the instantiation
 };
 constexpr int kMaxCachedDevices = 64;
 
@@ -1426,10 +1456,11 @@ static bool five_wide_workgroups_fit(int device, bool cached_device, uint32_t lv
 // partition mode, hence in workgroups held at once): asked once per (instantiation, device, stack levels); host threads that
 // drive contexts of their own may race for an entry, and then write the same value.
 // I: the instantiation's arguments by name (kernel_choice.h: Instance), which w.choice names too.
-template <class I>
+// REGION: the form of it that renders a rectangle (render_wavefront_kernel's REGION).
+template <class I, bool REGION>
 static void launch_instance(const WavefrontLaunch& w)
 {
-    auto kernel = PTMI_DEV_NS::render_wavefront_kernel<I::stats, I::pre, I::ss, I::plain, I::nansafe, I::block, I::cull>;
+    auto kernel = PTMI_DEV_NS::render_wavefront_kernel<I::stats, I::pre, I::ss, I::plain, I::nansafe, I::block, I::cull, REGION>;
     constexpr int B = I::block;
     const uint32_t lv = w.choice.stack_levels;
     static std::atomic<int> resident_cache[kMaxCachedDevices][PTMI_BVH_MAX_DEPTH + 1];
@@ -1442,17 +1473,24 @@ static void launch_instance(const WavefrontLaunch& w)
     uint32_t nb = (w.n_jobs + B - 1) / B;
     if (resident > 0 && nb > (uint32_t)resident) nb = (uint32_t)resident;
     hipLaunchKernelGGL(kernel, dim3(nb), dim3(B), w.choice.lds_bytes, w.st, w.scene_in_device_memory, w.warm, w.first_iteration,
-                       w.n_iterations, w.iteration_stride, w.n_jobs, w.job_counter, lv, w.stage, w.stage_stats);
+                       w.n_iterations, w.iteration_stride, w.n_jobs, w.job_counter, lv, w.stage, w.stage_stats, w.region);
 }
 
 }  // namespace
 
 int PTMI_ARITH(launch_render_wavefront)(const DScene& sc, const DScene* scene_in_device_memory, uint32_t first_iteration,
                             uint32_t n_iterations, uint32_t iteration_stride, uint32_t* job_counter, uint32_t stack_levels,
-                            bool scheduler_stats, float* stage, uint32_t* stage_stats, void* stream, std::string* err)
+                            bool scheduler_stats, float* stage, uint32_t* stage_stats, const Region& region, bool region_call, void* stream,
+                            std::string* err)
 {
-    if (n_iterations == 0) return PTMI_OK;
-    const uint32_t tiles = ((sc.width + 7u) / 8u) * ((sc.height + 7u) / 8u);
+    if (n_iterations == 0 || region_is_empty(region)) return PTMI_OK;
+    if (!check_region(sc.width, sc.height, region, err)) return PTMI_ERR_INTERNAL;  // (the callers have checked: refused, never a fault)
+    if (!region_call && !(region.x == 0u && region.y == 0u && region.w == sc.width && region.h == sc.height)) {
+        // (the forms without REGION ignore the argument: they would stage whole-image slots behind a region's accumulate kernels)
+        if (err) *err = "launch_render_wavefront: a region that is not the whole image needs region_call";
+        return PTMI_ERR_INTERNAL;
+    }
+    const uint32_t tiles = region_tiles(region);
     const uint64_t jobs64 = (uint64_t)tiles * 64u * n_iterations;
     if (jobs64 > (sc.sampler == PTMI_SAMPLER_RANDOM ? 0x7FFFFFF0ull : 0xFFFFFFF0ull)) {  // (RANDOM: bit 31 of a slot word is kGivenUp)
         if (err) *err = "too many jobs in one launch";
@@ -1470,12 +1508,15 @@ int PTMI_ARITH(launch_render_wavefront)(const DScene& sc, const DScene* scene_in
         w.n_jobs = n_jobs; w.st = (hipStream_t)stream;
         w.scene_in_device_memory = scene_in_device_memory;
         w.first_iteration = first_iteration; w.n_iterations = n_iterations; w.iteration_stride = iteration_stride;
-        w.job_counter = job_counter; w.stage = stage; w.stage_stats = stage_stats;
+        w.job_counter = job_counter; w.stage = stage; w.stage_stats = stage_stats; w.region = region; w.region_call = region_call;
         w.cached_device = hipGetDevice(&w.device) == hipSuccess && w.device >= 0 && w.device < kMaxCachedDevices;
         const bool five_wide_fit = five_wide_workgroups_fit(w.device, w.cached_device, ptmi_choice::clamp_levels(stack_levels));
         w.choice = ptmi_choice::choose_wavefront(sc, scheduler_stats, stack_levels, five_wide_fit, launch);
         w.warm = PTMI_DEV_NS::warm_of(sc, w.choice.wait_debt);
-        if (!ptmi_choice::with_instance(w.choice, [&w](auto instance) { launch_instance<decltype(instance)>(w); })) {
+        if (!ptmi_choice::with_instance(w.choice, [&w](auto instance) {
+                if (w.region_call) launch_instance<decltype(instance), true>(w);
+                else launch_instance<decltype(instance), false>(w);
+            })) {
             const ptmi_choice::WavefrontChoice& c = w.choice;
             if (err)
                 *err = "no render_wavefront_kernel<STATS " + std::to_string(c.stats) + ", PRE " + std::to_string(c.pre) + ", SS " + std::to_string(c.ss) +
@@ -1488,13 +1529,13 @@ int PTMI_ARITH(launch_render_wavefront)(const DScene& sc, const DScene* scene_in
         const dim3 redo_block(PTMI_DEV_NS::kBlock);
         if (e == hipSuccess && stage == nullptr && sc.sampler == PTMI_SAMPLER_RANDOM) {  // the paths on the give-up list
             const auto redo_random = sc.tris_precomputed ? PTMI_DEV_NS::redo_random_kernel<true> : PTMI_DEV_NS::redo_random_kernel<false>;
-            hipLaunchKernelGGL(redo_random, dim3(64), redo_block, 0, w.st, sc, first_iteration, n_iterations, iteration_stride, job_counter);
+            hipLaunchKernelGGL(redo_random, dim3(64), redo_block, 0, w.st, sc, first_iteration, n_iterations, iteration_stride, job_counter, region);
             e = hipGetLastError();
         }
         if (e == hipSuccess && stage != nullptr) {  // the staging slots it marked
             const auto redo_poisoned = sc.tris_precomputed ? PTMI_DEV_NS::redo_poisoned_kernel<true> : PTMI_DEV_NS::redo_poisoned_kernel<false>;
             hipLaunchKernelGGL(redo_poisoned, dim3(1024), redo_block, 0, w.st, sc, first_iteration, n_iterations, iteration_stride, stage,
-                               stage_stats, job_counter);
+                               stage_stats, job_counter, region);
             e = hipGetLastError();
         }
     }
@@ -1505,26 +1546,29 @@ int PTMI_ARITH(launch_render_wavefront)(const DScene& sc, const DScene* scene_in
 // in iteration order) and the staged statistics words into the three histograms.  May run on another stream than the
 // launch (the caller orders them with an event): these two small kernels are what keeps launches in iteration order.
 int PTMI_ARITH(launch_accumulate_staged)(const DScene& sc, uint32_t first_iteration, uint32_t n_iterations, const float* stage,
-                             const uint32_t* stage_stats, bool with_histograms, void* stream, std::string* err)
+                             const uint32_t* stage_stats, bool with_histograms, const Region& region, void* stream, std::string* err)
 {
-    if (n_iterations == 0 || sc.sampler == PTMI_SAMPLER_RANDOM) return PTMI_OK;
-    const uint32_t n_pixels = sc.width * sc.height;
+    if (n_iterations == 0 || sc.sampler == PTMI_SAMPLER_RANDOM || region_is_empty(region)) return PTMI_OK;
+    if (!check_region(sc.width, sc.height, region, err)) return PTMI_ERR_INTERNAL;
+    const uint32_t n_pixels = region_pixels(region);  // slots of one iteration
     if (sc.super_sampling)
         hipLaunchKernelGGL(PTMI_DEV_NS::accumulate_staged_ss_kernel, dim3((n_pixels + 255u) / 256u), dim3(256), 0,
-                           (hipStream_t)stream, sc.image_color, sc.image_ray_nb, sc.image_v, stage, sc.stage_flag, n_pixels, first_iteration);
+                           (hipStream_t)stream, sc.image_color, sc.image_ray_nb, sc.image_v, stage, sc.stage_flag, n_pixels, first_iteration, region, sc.width);
     else
         hipLaunchKernelGGL(PTMI_DEV_NS::accumulate_staged_kernel, dim3((n_pixels + 255u) / 256u), dim3(256), 0,
-                           (hipStream_t)stream, sc.image_color, sc.image_ray_nb, stage, n_pixels, n_iterations);
+                           (hipStream_t)stream, sc.image_color, sc.image_ray_nb, stage, n_pixels, n_iterations, region, sc.width);
     const int status = launch_status(hipGetLastError(), "accumulate_staged_kernel", err);
     if (status != PTMI_OK) return status;
-    if (with_histograms && stage_stats != nullptr) return PTMI_ARITH(launch_histogram_staged)(sc, n_iterations, stage_stats, stream, err);
+    if (with_histograms && stage_stats != nullptr) return PTMI_ARITH(launch_histogram_staged)(sc, n_iterations, stage_stats, region, stream, err);
     return PTMI_OK;
 }
 
 // the staged statistics words of `n_iterations` iterations into the three histograms
-int PTMI_ARITH(launch_histogram_staged)(const DScene& sc, uint32_t n_iterations, const uint32_t* stage_stats, void* stream, std::string* err)
+int PTMI_ARITH(launch_histogram_staged)(const DScene& sc, uint32_t n_iterations, const uint32_t* stage_stats, const Region& region, void* stream,
+                            std::string* err)
 {
-    const uint32_t n_slots = sc.width * sc.height * n_iterations;
+    const uint32_t n_slots = region_pixels(region) * n_iterations;  // the slots the launch wrote (render_region.h)
+    if (n_slots == 0) return PTMI_OK;
     uint32_t hb = (n_slots + 1023u) / 1024u;
     if (hb > 512u) hb = 512u;
     hipLaunchKernelGGL(PTMI_DEV_NS::histogram_staged_kernel, dim3(hb), dim3(1024), 0, (hipStream_t)stream, sc.hist_depths,

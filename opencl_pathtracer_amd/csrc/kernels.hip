@@ -21,7 +21,8 @@ namespace PTMI_DEV_NS {
 
 template <bool PRE>
 __global__ void __launch_bounds__(kBlock) render_kernel(const DScene sc, const uint32_t first_iteration,
-                                                        const uint32_t n_iterations, const uint32_t iteration_stride)
+                                                        const uint32_t n_iterations, const uint32_t iteration_stride,
+                                                        const Region region)
 {
     __shared__ uint32_t stack_mem[kStackDepth * kBlock];
     __shared__ unsigned long long block_counters[C_COUNT];
@@ -30,11 +31,12 @@ __global__ void __launch_bounds__(kBlock) render_kernel(const DScene sc, const u
     if (tid < C_COUNT) block_counters[tid] = 0;
     __syncthreads();
 
-    // wave -> 8x8 pixel tile; block (4 waves) -> 16x16
+    // wave -> 8x8 pixel tile; block (4 waves) -> 16x16, laid over the launch's region from its own origin (render_region.h)
     const uint32_t wave = tid >> 6, lane = tid & 63u;
-    const uint32_t gx = blockIdx.x * 16u + (wave & 1u) * 8u + (lane & 7u);
-    const uint32_t gy = blockIdx.y * 16u + (wave >> 1) * 8u + (lane >> 3);
-    const bool valid = gx < sc.width && gy < sc.height;
+    const uint32_t rx = blockIdx.x * 16u + (wave & 1u) * 8u + (lane & 7u);
+    const uint32_t ry = blockIdx.y * 16u + (wave >> 1) * 8u + (lane >> 3);
+    const uint32_t gx = region.x + rx, gy = region.y + ry;  // the work-item: seed and sample are the full image's
+    const bool valid = rx < region.w && ry < region.h;
     uint32_t* stack = &stack_mem[tid];
 
     if (valid) {
@@ -86,13 +88,14 @@ __global__ void __launch_bounds__(kBlock) render_kernel(const DScene sc, const u
 
 namespace ptmi_internal {
 
-int PTMI_ARITH(launch_render)(const DScene& sc, uint32_t first_iteration, uint32_t n_iterations, uint32_t iteration_stride, void* stream,
-                  std::string* err)
+int PTMI_ARITH(launch_render)(const DScene& sc, uint32_t first_iteration, uint32_t n_iterations, uint32_t iteration_stride,
+                  const Region& region, void* stream, std::string* err)
 {
-    if (n_iterations == 0) return PTMI_OK;
-    const dim3 grid((sc.width + 15u) / 16u, (sc.height + 15u) / 16u);
+    if (n_iterations == 0 || region_is_empty(region)) return PTMI_OK;
+    if (!check_region(sc.width, sc.height, region, err)) return PTMI_ERR_INTERNAL;  // (the callers have checked: refused, never a fault)
+    const dim3 grid((region.w + 15u) / 16u, (region.h + 15u) / 16u);
     const auto kernel = sc.tris_precomputed ? PTMI_DEV_NS::render_kernel<true> : PTMI_DEV_NS::render_kernel<false>;
-    hipLaunchKernelGGL(kernel, grid, dim3(PTMI_DEV_NS::kBlock), 0, (hipStream_t)stream, sc, first_iteration, n_iterations, iteration_stride);
+    hipLaunchKernelGGL(kernel, grid, dim3(PTMI_DEV_NS::kBlock), 0, (hipStream_t)stream, sc, first_iteration, n_iterations, iteration_stride, region);
     return launch_status(hipGetLastError(), "render_kernel", err);
 }
 

@@ -9,6 +9,7 @@
 #include "dev_switches.h"
 #include "ptmi.h"
 #include "ptmi_hd.h"
+#include "render_region.h"
 #ifdef __HIPCC__  // (host code that is built without HIP reads this header too: it gets everything but launch_status)
 #include <hip/hip_runtime.h>
 #endif
@@ -228,21 +229,26 @@ struct DScene {
     /* kernels.hip: one path per lane (kept for A/B and as a second implementation in the parity tests)                         \
        iteration ids of a launch: first_iteration + k * iteration_stride, k < n_iterations */                                   \
     int launch_render##SUFFIX(const DScene& sc, uint32_t first_iteration, uint32_t n_iterations, uint32_t iteration_stride,      \
-                              void* stream, std::string* err);                                                                  \
+                              const Region& region, void* stream, std::string* err);                                            \
     /* kernel_wavefront.hip: persistent wavefront state machine (default)                                                       \
        stack_levels = LDS traversal-stack entries per lane = depth of the uploaded tree (>= 1, <= 30) */                        \
     /* scene_in_device_memory = a device copy of `sc` (the kernel takes only the hot fields by value)                           \
-       stage_stats: one word per staged path for the histograms (nullptr: the kernel issues the reference's atomics itself) */  \
+       stage_stats: one word per staged path for the histograms (nullptr: the kernel issues the reference's atomics itself)     \
+       region: the work-items the launch traces (render_region.h; the whole image for ptmi_render); stage / stage_stats are     \
+       numbered by the region's slots, as the two calls below read them.  region_call: ptmi_render_region's launch - the       \
+       kernel's REGION form, also for the whole image; false needs region = the whole image */                                 \
     int launch_render_wavefront##SUFFIX(const DScene& sc, const DScene* scene_in_device_memory, uint32_t first_iteration,        \
                                         uint32_t n_iterations, uint32_t iteration_stride, uint32_t* job_counter,                \
                                         uint32_t stack_levels, bool scheduler_stats, float* stage,                              \
-                                        uint32_t* stage_stats, void* stream, std::string* err);                                 \
+                                        uint32_t* stage_stats, const Region& region, bool region_call, void* stream,            \
+                                        std::string* err);                                                                      \
     void last_wavefront_grid##SUFFIX(int device, uint32_t* lanes_per_workgroup, uint32_t* resident_workgroups);                  \
     /* ... and what must follow it, in launch order: staged radiances -> accumulators, staged statistics -> histograms */       \
     int launch_accumulate_staged##SUFFIX(const DScene& sc, uint32_t first_iteration, uint32_t n_iterations, const float* stage,  \
-                                         const uint32_t* stage_stats, bool with_histograms, void* stream, std::string* err);    \
-    int launch_histogram_staged##SUFFIX(const DScene& sc, uint32_t n_iterations, const uint32_t* stage_stats, void* stream,     \
-                                        std::string* err);
+                                         const uint32_t* stage_stats, bool with_histograms, const Region& region, void* stream, \
+                                         std::string* err);                                                                     \
+    int launch_histogram_staged##SUFFIX(const DScene& sc, uint32_t n_iterations, const uint32_t* stage_stats,                   \
+                                        const Region& region, void* stream, std::string* err);
 PTMI_DECLARE_INTEGRATOR_ENTRY_POINTS()
 PTMI_DECLARE_INTEGRATOR_ENTRY_POINTS(_da)
 #undef PTMI_DECLARE_INTEGRATOR_ENTRY_POINTS

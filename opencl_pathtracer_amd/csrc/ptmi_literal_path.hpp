@@ -6,6 +6,7 @@
 
 #include "ptmi_device.hpp"
 #include "ptmi_shading.hpp"
+#include "render_region.h"
 
 namespace PTMI_DEV_NS {
 
@@ -16,15 +17,7 @@ struct PathCounters {
     uint32_t bbx, tri;  // numIntersectedBBx / numIntersectedTri of the current path
 };
 
-// A staging slot = it_local * W * H + y * W + x of a launch -> the path's pixel and iteration id (n_pixels = W * H).
-__device__ __forceinline__ void decode_slot(uint32_t slot, uint32_t width, uint32_t n_pixels, uint32_t first_iteration,
-                                            uint32_t iteration_stride, uint32_t& gx, uint32_t& gy, uint32_t& iteration)
-{
-    const uint32_t it_local = slot / n_pixels, pixel = slot - it_local * n_pixels;
-    gy = pixel / width;
-    gx = pixel - gy * width;
-    iteration = first_iteration + it_local * iteration_stride;
-}
+// (A launch's staging slot -> the path's pixel and iteration id: decode_slot, render_region.h.)
 
 // The three statistics atomics of a finished path as the reference issues them (FullKernel.cl:1319-1331).
 __device__ __forceinline__ void count_path_in_histograms(const DScene& sc, uint32_t depth, uint32_t bbx, uint32_t tri)

@@ -46,6 +46,33 @@ int copy_out(ptmi_ctx* ctx, hipStream_t stream, const float* d_color, const floa
     return land(ctx, items, stream, reinterpret_cast<char*>(ctx->h_staging));
 }
 
+// The same for rectangle `r` of the two planes (ptmi_read_region): ONE strided copy per plane, device pitch = the image's row,
+// host rows densely packed - 20 bytes per pixel of the rectangle cross the bus.  Straight into a destination the caller has
+// page-locked, otherwise through the context's staging buffer (which holds a whole image: any rectangle fits).
+int copy_out_region(ptmi_ctx* ctx, hipStream_t stream, const float* d_color, const float* d_count, const Region& r, float* image_color,
+                    float* image_ray_nb)
+{
+    const size_t W = ctx->cfg.image_width, n = (size_t)r.w * r.h, first = (size_t)r.y * W + r.x;
+    struct Plane { void* to; const char* from; size_t texel, offset; };
+    const Plane planes[2] = {{image_color, reinterpret_cast<const char*>(d_color) + first * 16, 16, 0},
+                             {image_ray_nb, reinterpret_cast<const char*>(d_count) + first * 4, 4, n * 16}};
+    bool direct[2];
+    for (int k = 0; k < 2; k++) direct[k] = !planes[k].to || ctx->host_is_pinned(planes[k].to, n * planes[k].texel);
+    if (!(direct[0] && direct[1]))
+        if (int rc = lazy_pinned_buffer(ctx, ctx->h_staging, ctx->image_bytes())) return rc;
+    char* const landing = reinterpret_cast<char*>(ctx->h_staging);
+    for (int k = 0; k < 2; k++) {
+        const Plane& p = planes[k];
+        if (p.to)
+            HIP_TRY(ctx, hipMemcpy2DAsync(direct[k] ? p.to : landing + p.offset, r.w * p.texel, p.from, W * p.texel, r.w * p.texel, r.h,
+                                          hipMemcpyDeviceToHost, stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    for (int k = 0; k < 2; k++)
+        if (!direct[k]) std::memcpy(planes[k].to, landing + planes[k].offset, n * planes[k].texel);
+    return PTMI_OK;
+}
+
 // ---- RCCL, loaded at run time (the library has no link-time dependency on it) --------------------------------------------
 // north_star: "samples-per-pixel shard across the GPUs of one node with an RCCL reduce of the framebuffer over xGMI".  One
 // process drives all devices of a context, so the communicators come from ncclCommInitAll and the G reduce calls of an image
@@ -271,6 +298,30 @@ int ptmi_read_image(ptmi_ctx* ctx, float* image_color, float* image_ray_nb)
     }
     if (int rc = snapshot_all(ctx, kInternalSlot)) return rc;
     return ptmi_read_snapshot(ctx, kInternalSlot, image_color, image_ray_nb);
+}
+
+int ptmi_read_region(ptmi_ctx* ctx, const ptmi_region* region, float* image_color, float* image_ray_nb)
+{
+    NEED_SCENE(ctx);
+    if (!region) return fail(ctx, PTMI_ERR_INVALID_ARGUMENT, "ptmi_read_region: region is NULL");
+    const Region r{region->x, region->y, region->width, region->height};
+    std::string why;
+    if (!check_region(ctx->cfg.image_width, ctx->cfg.image_height, r, &why)) return fail(ctx, PTMI_ERR_INVALID_ARGUMENT, "ptmi_read_region: " + why);
+    // an empty rectangle copies nothing but waits like any other: "the region of what ptmi_read_image would return at this moment"
+    const bool nothing = region_is_empty(r);
+    float* const color = nothing ? nullptr : image_color;
+    float* const count = nothing ? nullptr : image_ray_nb;
+    if (ctx->n_dev() == 1) {  // straight from the accumulators, in order on the render stream
+        DeviceState& d = ctx->dev[0];
+        ON_DEVICE(ctx, d);
+        return copy_out_region(ctx, d.stream, d.ds.image_color, d.ds.image_ray_nb, r, color, count);
+    }
+    // several devices: their shares are summed first, as for ptmi_read_image (whole images: the sum is not cut to the rectangle)
+    if (int rc = snapshot_all(ctx, kInternalSlot)) return rc;
+    const float* image = nullptr;
+    if (int rc = gather_snapshot(ctx, kInternalSlot, &image)) return rc;
+    ON_DEVICE(ctx, ctx->dev[0]);
+    return copy_out_region(ctx, ctx->dev[0].copy_stream, image, image + 4 * ctx->npix(), r, color, count);
 }
 
 int ptmi_read_display(ptmi_ctx* ctx, uint8_t* bgr, uint32_t row_stride)

@@ -92,7 +92,10 @@ uint32_t* stats_of(const ptmi_ctx* ctx, const DeviceState& d, int set)
 // A launch of m iterations from id f: on the main stream into set 0 (`main`; staged or not), or a SHORT one on stage set `set`:
 // on the set's own stream, counting into the set's own block - it touches nothing else of the context, whether a call has asked
 // for it or not.  `calls` > 1: the launch renders for that many calls of m / calls iterations each, and counts per call.
-int launch(ptmi_ctx* ctx, DeviceState& d, bool main, bool staged, int set, uint32_t f, uint32_t m, uint32_t stride, uint32_t calls = 1)
+// `region`: the work-items it traces; its staging slots are numbered over the region (render_region.h), so a set that holds m
+// iterations of the whole image holds m of any region.
+int launch(ptmi_ctx* ctx, DeviceState& d, bool main, bool staged, int set, uint32_t f, uint32_t m, uint32_t stride, const Region& region,
+           bool region_call, uint32_t calls = 1)
 {
     hipStream_t st = main ? d.stream : d.launch_stream[set];
     if (d.reuse_after[set]) HIP_TRY(ctx, hipStreamWaitEvent(st, d.reuse_after[set], 0));  // (main: a short launch nobody adopted)
@@ -103,12 +106,12 @@ int launch(ptmi_ctx* ctx, DeviceState& d, bool main, bool staged, int set, uint3
     if (!main) {
         HIP_TRY(ctx, hipMemsetAsync(d.d_set_counters[set], 0, PTMI_COUNTER_SPLITS * C_COUNT * 8, st));
         k.counters = d.d_set_counters[set];
-        k.split_paths = calls > 1 ? (uint32_t)((m / calls) * ctx->npix()) : 0u;
+        k.split_paths = calls > 1 ? (m / calls) * region_pixels(region) : 0u;  // (in staging slots)
     }
     std::string err;
     if (int rc = KERNELS_OF(ctx, launch_render_wavefront)(k, main ? d.d_scene : d.d_scene_set[set], f, m, stride, d.d_job_counter + set * 8 * 1024,
                                                           ctx->stack_levels, d.schedule.call.stats_build, staged ? d.d_stage[set] : nullptr,
-                                                          staged ? stats_of(ctx, d, set) : nullptr, st, &err))
+                                                          staged ? stats_of(ctx, d, set) : nullptr, region, region_call, st, &err))
         return fail(ctx, rc, err);
     if (main) return PTMI_OK;
     d.reuse_after[set] = d.rendered[set];  // (until the main stream adopts it)
@@ -117,8 +120,11 @@ int launch(ptmi_ctx* ctx, DeviceState& d, bool main, bool staged, int set, uint3
 }
 
 // One device's launches for its share of a ptmi_render call, as d.schedule plans them, bracketed by an event pair for
-// ptmi_kernel_time.
-int render_on_device(ptmi_ctx* ctx, DeviceState& d, uint32_t first, uint32_t n, uint32_t stride, SnapshotPlan* plan = nullptr)
+// ptmi_kernel_time.  `region_call` = nullptr: ptmi_render, the whole image.  A call with a region (ptmi_render_region, the whole
+// image included) is planned as one that cannot run ahead: it adopts no launch ahead, the ones in flight are dropped, and none
+// is left behind it.
+int render_on_device(ptmi_ctx* ctx, DeviceState& d, uint32_t first, uint32_t n, uint32_t stride, SnapshotPlan* plan = nullptr,
+                     const Region* region_call = nullptr)
 {
     if (n == 0) return plan ? snapshots_up_to(ctx, d, *plan, plan->n) : PTMI_OK;
     ON_DEVICE(ctx, d);
@@ -133,7 +139,8 @@ int render_on_device(ptmi_ctx* ctx, DeviceState& d, uint32_t first, uint32_t n, 
     const bool may_overlap = staged && !ctx->cfg.super_sampling && d.stream == d.own_stream && !serial_env;
     // rendering ahead (per device: with G devices each sees every G-th call, stride G): nothing but staged results leaves the
     // kernel (the histograms of very deep paths are atomics inside it), and the caller has not asked for an image per iteration
-    const bool ahead_allowed = !plan && !(d.ds.hist_depths && ctx->cfg.ray_max_depth >= 64);
+    const bool ahead_allowed = !plan && !region_call && !(d.ds.hist_depths && ctx->cfg.ray_max_depth >= 64);
+    const Region region = region_call ? *region_call : whole_image(ctx->cfg.image_width, ctx->cfg.image_height);
     const StageNeed need = d.schedule.begin({first, n, stride, ctx->iterations_per_launch, ctx->cfg.super_sampling != 0, may_overlap,
                                              ahead_allowed, (uint32_t)ptmi_switches::clamped(call.render_ahead, 2, 0, kStageSets - 2),
                                              (uint32_t)ptmi_switches::clamped(call.render_ahead_calls, PTMI_COUNTER_SPLITS, 1, PTMI_COUNTER_SPLITS),
@@ -154,34 +161,35 @@ int render_on_device(ptmi_ctx* ctx, DeviceState& d, uint32_t first, uint32_t n, 
     if (!d.free_events.back().first) HIP_TRY(ctx, hipEventCreate(&d.free_events.back().first));
     if (!d.free_events.back().second) HIP_TRY(ctx, hipEventCreate(&d.free_events.back().second));
     const std::pair<hipEvent_t, hipEvent_t> ev = d.free_events.back();
-    const size_t npix = ctx->npix();
+    const size_t nslot = region_pixels(region);  // staging slots of one iteration
     std::string err;
     // both events on the MAIN stream, [previous launch accumulated, this one accumulated]: the intervals tile the time line
     HIP_TRY(ctx, hipEventRecord(ev.first, d.stream));
     if (megakernel) {
-        if (int rc = KERNELS_OF(ctx, launch_render)(d.ds, first, n, stride, d.stream, &err)) return fail(ctx, rc, err);
+        if (int rc = KERNELS_OF(ctx, launch_render)(d.ds, first, n, stride, region, d.stream, &err)) return fail(ctx, rc, err);
     } else {
         for (const Step& s : d.schedule.steps()) {
             if (s.kind != Step::kAdopt)
-                if (int rc = launch(ctx, d, s.kind == Step::kMain, staged, s.set, s.first, s.n, stride)) return rc;
+                if (int rc = launch(ctx, d, s.kind == Step::kMain, staged, s.set, s.first, s.n, stride, region, region_call != nullptr)) return rc;
             if (s.kind != Step::kMain) HIP_TRY(ctx, hipStreamWaitEvent(d.stream, d.rendered[s.set], 0));
-            float* const stage = staged ? d.d_stage[s.set] + (size_t)s.part * s.n * npix * 4 : nullptr;
-            uint32_t* const stage_stats = staged && stats_of(ctx, d, s.set) ? stats_of(ctx, d, s.set) + (size_t)s.part * s.n * npix : nullptr;
+            float* const stage = staged ? d.d_stage[s.set] + (size_t)s.part * s.n * nslot * 4 : nullptr;
+            uint32_t* const stage_stats = staged && stats_of(ctx, d, s.set) ? stats_of(ctx, d, s.set) + (size_t)s.part * s.n * nslot : nullptr;
             if (!plan) {
-                if (int rc = KERNELS_OF(ctx, launch_accumulate_staged)(d.ds, s.first, s.n, stage, stage_stats, true, d.stream, &err))
+                if (int rc = KERNELS_OF(ctx, launch_accumulate_staged)(d.ds, s.first, s.n, stage, stage_stats, true, region, d.stream, &err))
                     return fail(ctx, rc, err);
             } else {
                 // one accumulation per iteration, each followed by the snapshots of the global iterations up to it
                 for (uint32_t j = 0; j < s.n; j++) {
                     const uint32_t id = s.first + j * stride;
                     if (int rc = snapshots_up_to(ctx, d, *plan, id - plan->first)) return rc;  // images before this device's next own one
-                    if (int rc = KERNELS_OF(ctx, launch_accumulate_staged)(d.ds, id, 1, stage + (size_t)j * npix * 4,
-                                                                           stage_stats ? stage_stats + (size_t)j * npix : nullptr, false, d.stream, &err))
+                    if (int rc = KERNELS_OF(ctx, launch_accumulate_staged)(d.ds, id, 1, stage + (size_t)j * nslot * 4,
+                                                                           stage_stats ? stage_stats + (size_t)j * nslot : nullptr, false, region, d.stream,
+                                                                           &err))
                         return fail(ctx, rc, err);
                     plan->changed = true;
                     if (int rc = snapshots_up_to(ctx, d, *plan, id - plan->first + 1)) return rc;
                 }
-                if (int rc = stage_stats ? KERNELS_OF(ctx, launch_histogram_staged)(d.ds, s.n, stage_stats, d.stream, &err) : PTMI_OK)
+                if (int rc = stage_stats ? KERNELS_OF(ctx, launch_histogram_staged)(d.ds, s.n, stage_stats, region, d.stream, &err) : PTMI_OK)
                     return fail(ctx, rc, err);
             }
             if (s.kind != Step::kMain)
@@ -196,7 +204,8 @@ int render_on_device(ptmi_ctx* ctx, DeviceState& d, uint32_t first, uint32_t n, 
         const bool caller_waits = d.previous_call_done == nullptr || hipEventQuery(d.previous_call_done) == hipSuccess;
         (void)hipGetLastError();  // (hipErrorNotReady is not an error)
         for (const LaunchSchedule::Ahead& a : d.schedule.launches_ahead(caller_waits, d.stage_cap))
-            if (int rc = launch(ctx, d, false, true, a.set, a.first, a.n * a.calls, stride, a.calls)) return rc;
+            if (int rc = launch(ctx, d, false, true, a.set, a.first, a.n * a.calls, stride, whole_image(ctx->cfg.image_width, ctx->cfg.image_height), false, a.calls))
+                return rc;  // (launches ahead render whole images, whatever call leaves them)
     }
     if (int rc = plan ? snapshots_up_to(ctx, d, *plan, plan->n) : PTMI_OK) return rc;  // images after its last own one
     HIP_TRY(ctx, hipEventRecord(ev.second, d.stream));
@@ -204,6 +213,7 @@ int render_on_device(ptmi_ctx* ctx, DeviceState& d, uint32_t first, uint32_t n, 
     d.pending_events.push_back(ev);
     d.previous_call_done = ev.second;  // (stays valid in the pool: fold_events only moves the pair to free_events)
     d.schedule.commit();
+    if (region_call) d.schedule.forget();  // (no pattern of ptmi_render calls continues a region call: the schedule's own "no call to continue")
     return PTMI_OK;
 }
 
@@ -231,6 +241,26 @@ int ptmi_render(ptmi_ctx* ctx, uint32_t first_iteration, uint32_t n_iterations)
         uint32_t first_k, n_k;
         device_share(first_iteration, n_iterations, k, G, &first_k, &n_k);
         if (int rc = render_on_device(ctx, ctx->dev[k], first_k, n_k, G)) return rc;
+    }
+    return PTMI_OK;
+}
+
+int ptmi_render_region(ptmi_ctx* ctx, const ptmi_region* region, uint32_t first_iteration, uint32_t n_iterations)
+{
+    NEED_SCENE(ctx);
+    if (!region) return fail(ctx, PTMI_ERR_INVALID_ARGUMENT, "ptmi_render_region: region is NULL");
+    const Region r{region->x, region->y, region->width, region->height};
+    std::string why;
+    if (!check_region(ctx->cfg.image_width, ctx->cfg.image_height, r, &why)) return fail(ctx, PTMI_ERR_INVALID_ARGUMENT, "ptmi_render_region: " + why);
+    if ((uint64_t)first_iteration + n_iterations > 0xFFFFFFFFull)
+        return fail(ctx, PTMI_ERR_INVALID_ARGUMENT, "ptmi_render_region: iteration range overflows 32 bits");
+    if (n_iterations == 0 || region_is_empty(r)) return PTMI_OK;
+    // (the whole image goes the same way as any other rectangle: this is the case that proves the two entry points equal)
+    const uint32_t G = ctx->n_dev();
+    for (uint32_t k = 0; k < G; k++) {
+        uint32_t first_k, n_k;
+        device_share(first_iteration, n_iterations, k, G, &first_k, &n_k);
+        if (int rc = render_on_device(ctx, ctx->dev[k], first_k, n_k, G, nullptr, &r)) return rc;
     }
     return PTMI_OK;
 }

@@ -90,6 +90,14 @@ PATH_SUM = np.dtype({
     "itemsize": 48,
 })
 
+# include/ptmi.h: ptmi_region, the rectangle Backend.render_region / read_region take: pixels [x, x + width) x [y, y + height)
+REGION = np.dtype({
+    "names": ["x", "y", "width", "height"],
+    "formats": [np.uint32] * 4,
+    "offsets": [0, 4, 8, 12],
+    "itemsize": 16,
+})
+
 # enums (PathTracer_Structs.h:24-30, 43-51, 66-71, 130-135)
 LIGHT_DIRECTIONNAL, LIGHT_POINT, LIGHT_SPOT, LIGHT_UNKNOWN = 0, 1, 2, 3
 MAT_STANDART, MAT_WATER, MAT_GLASS, MAT_VARNHISHED, MAT_METAL, MAT_UNKNOWN = 0, 1, 2, 3, 4, 5
@@ -103,4 +111,4 @@ MAX_LIGHT_SIZE = 30             # PathTracer_PreProc.h:20
 
 assert BoundingBox.itemsize == 64 and Light.itemsize == 64 and Material.itemsize == 48
 assert Node.itemsize == 160 and Texture.itemsize == 12 and Triangle.itemsize == 336 and Sky.itemsize == 92
-assert RAY.itemsize == 48 and RAY_HIT.itemsize == 48 and PATH_SUM.itemsize == 48
+assert RAY.itemsize == 48 and RAY_HIT.itemsize == 48 and PATH_SUM.itemsize == 48 and REGION.itemsize == 16

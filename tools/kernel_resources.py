@@ -17,12 +17,13 @@ from collections import Counter
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-# the mangled template arguments: five bools, the workgroup's lanes, and whether the instantiation culls leaves (leaf_cull.h)
-NAME = r"\w+?23render_wavefront_kernelI((?:Lb[01]E){5})(?:Li(\d+)E)?(?:Lb([01])E)?E"
+# the mangled template arguments: five bools, the workgroup's lanes, whether the instantiation culls leaves (leaf_cull.h), and
+# whether it is the form that renders a rectangle (ptmi_render_region: key suffix r; the forms without it keep their keys)
+NAME = r"\w+?23render_wavefront_kernelI((?:Lb[01]E){5})(?:Li(\d+)E)?(?:Lb([01])E)?(?:Lb([01])E)?E"
 
 
 def key_of(m):
-    return "".join(re.findall(r"Lb([01])E", m.group(1))) + ("b" + m.group(2) if m.group(2) not in (None, "256") else "") + ("c" if m.group(3) == "1" else "")
+    return "".join(re.findall(r"Lb([01])E", m.group(1))) + ("b" + m.group(2) if m.group(2) not in (None, "256") else "") + ("c" if m.group(3) == "1" else "") + ("r" if m.group(4) == "1" else "")
 
 
 def compile_to_assembly(tree=ROOT, arithmetic=1, extra=()):
@@ -237,16 +238,21 @@ def node_trip_tail(blocks):
             "full lgkm waits": sum(l.startswith("s_waitcnt") and "lgkmcnt(0)" in l for l in lines), "vector": vector, "scalar": scalar}
 
 
-def resources(tree=ROOT, arithmetic=1, extra=()):
+def resources(tree=ROOT, arithmetic=1, extra=(), region_forms=False):
+    """region_forms: also the forms that render a rectangle (key suffix r).  Without them the keys are those of before regions
+    existed: every launch of ptmi_render runs one of these, and the tests that pin figures name them."""
     out, remarks = compile_to_assembly(tree, arithmetic, extra)
     res = {}
+    wanted = lambda key: region_forms or not key.endswith("r")
     for block in re.split(r"Function Name: ", remarks)[1:]:
         m = re.match(NAME, block)
-        if not m:
+        if not m or not wanted(key_of(m)):
             continue
-        key = key_of(m)  # STATS PRE SS PLAIN NANSAFE [bN: lanes per workgroup] [c: the culling instantiation]
+        key = key_of(m)  # STATS PRE SS PLAIN NANSAFE [bN: lanes per workgroup] [c: the culling instantiation] [r: renders a rectangle]
         res[key] = {k.strip(): int(v) for k, v in re.findall(r"remark: [^\n]*?\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", block)}
     for name, blocks in kernel_blocks(out).items():
+        if not wanted(name):
+            continue
         v = res[name]
         c = Counter(l.split()[0] for depth, lines in blocks if depth == 2 for l in lines)
         tot = lambda p: sum(n for i, n in c.items() if i.startswith(p))
@@ -261,6 +267,8 @@ def resources(tree=ROOT, arithmetic=1, extra=()):
         v["node step"] = node_step_waits(blocks)
         v.update(outer_loop_memory(blocks))
     for name, blocks in kernel_cfg(out).items():
+        if not wanted(name):
+            continue
         res[name]["trip loop"] = trip_loop_copies(blocks)
         res[name]["tail"] = node_trip_tail(blocks)
     return res
@@ -286,8 +294,8 @@ def trip_loop_text(t):
 if __name__ == "__main__":
     tree = sys.argv[1] if len(sys.argv) > 1 else ROOT
     arith = int(sys.argv[2]) if len(sys.argv) > 2 else 1
-    res = resources(tree, arith)
-    print("STATS PRE SS PLAIN NANSAFE | VGPRs spilled scratch occupancy | traversal loop: scratch VALU SALU LDS VMEM | flat: in the loop, "
+    res = resources(tree, arith, region_forms=True)
+    print("STATS PRE SS PLAIN NANSAFE [b64: narrow workgroups] [c: culls leaves] [r: renders a rectangle, ptmi_render_region] | VGPRs spilled scratch occupancy | traversal loop: scratch VALU SALU LDS VMEM | flat: in the loop, "
           "before it, kernel | path-logic pass (the outer loop's body): vector loads, scalar loads, full vector-memory waits | "
           "node step: load offsets, then its waits | trip loop: v_mov in the loop; node-trip path vector, scalar instructions; leaf-pass path "
           "vector, scalar; register copies on a node trip's way in (header to the first record load), full vector-memory waits there, "
