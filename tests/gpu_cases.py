@@ -30,6 +30,30 @@ def context(sc, width, height, depth=4, flags=0, sampler=S.JITTERED, super_sampl
     return be
 
 
+def require_probe_tools():
+    """The two libraries the record checks read a context's scene with; a GPU test without them fails, it does not skip."""
+    import pytest
+    import scene_record_cases as R
+    if R.model() is None:
+        pytest.fail("oracle/build/libscene_refit_model.so not built (make -C oracle probe)", pytrace=False)
+    if R.probe() is None:
+        pytest.fail("oracle/build/libscene_record_probe.so not built (make -C oracle probe)", pytrace=False)
+
+
+def tensor_on_device(array):
+    """The array as a torch tensor on the device, copied before this returns (the context's stream is not torch's)"""
+    import torch
+    t = torch.from_numpy(np.ascontiguousarray(array)).cuda()
+    torch.cuda.synchronize()
+    return t
+
+
+def bytes_of(tensor):
+    import torch
+    torch.cuda.synchronize()
+    return tensor.view(torch.int32).cpu().numpy().tobytes()
+
+
 def state(be, variance=False):
     color, count = be.read_image()
     out = dict(color=color.view(np.uint32).copy(), count=count.copy(), stats=[s.copy() for s in be.read_statistics()], counters=be.counters())

@@ -2,13 +2,12 @@
 rays of a path as the reference shoots them, and one BVH query of the model with the oracle's deciders."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 
 from opencl_pathtracer_amd import backend, structs as S
 from f32_cases import camera_direction, fma as _fma, mad as _mad
+import model_build
 import oracle_ffi as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,15 +21,9 @@ WALK_FIELDS = ("hit", "limit_bits", "n_bbx", "n_tri", "direct", "popped", "direc
                "popped_culled_tris", "tested", "direct_uncertified")
 
 
-def build_model(folder):
-    gxx = shutil.which("g++")
-    if not gxx:
-        return None
-    so = os.path.join(str(folder), "libleaf_cull_model.so")
-    r = subprocess.run([gxx, "-std=c++17", "-O2", "-fPIC", "-shared", "-Wall", "-ffp-contract=off", "-fno-fast-math",
-                        "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, *SRCS, "-o", so], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    m = C.CDLL(so)
+def build_model(folder, extra_sources=()):
+    m = C.CDLL(model_build.library([*SRCS, *extra_sources], folder, "libleaf_cull_model.so", opt="-O2", werror=False, fp_strict=True,
+                                   includes=[os.path.join(ROOT, "include"), CSRC]))
     m.cull_rule.argtypes = [FP, FP, FP, C.c_float, C.c_float]
     m.cull_box_distance2.argtypes = [FP, FP, FP]
     m.cull_box_distance2.restype = C.c_float

@@ -19,15 +19,8 @@ THIN_WIDE_ONLY = (0.04, 0.1)  # of the base edge: below what the tight tier cert
 
 
 def build_model(folder):
-    """K.build_model's library plus the wide model's functions (None without g++)."""
-    srcs = K.SRCS
-    K.SRCS = srcs + [WIDE_SRC]
-    try:
-        m = K.build_model(folder)
-    finally:
-        K.SRCS = srcs
-    if m is None:
-        return None
+    """K.build_model's library plus the wide model's functions."""
+    m = K.build_model(folder, extra_sources=[WIDE_SRC])
     m.wide_constants.argtypes = [C.POINTER(C.c_double)]
     m.wide_bits.argtypes = [C.c_void_p]
     m.wide_rule.argtypes = [FP, FP, FP, C.c_float, C.c_float]

@@ -27,6 +27,7 @@ import pytest
 
 from opencl_pathtracer_amd import Backend, backend, structs as S
 import api_fuzz_cases as F
+import gpu_cases
 import guide_cases as G
 import path_query_cases as P
 
@@ -93,10 +94,7 @@ class DeviceIO:
 
     def update(self, be, tris):
         """ptmi_update_triangles_device from a 16-byte-aligned float32 (n, 84) tensor (a byte copy of the records).  Synchronous."""
-        import torch
-        words = np.frombuffer(bytearray(np.ascontiguousarray(tris).tobytes()), np.float32).reshape(len(tris), 84)
-        t = torch.from_numpy(words).cuda()
-        torch.cuda.synchronize()  # (the context's stream is not torch's)
+        t = gpu_cases.tensor_on_device(np.frombuffer(bytearray(np.ascontiguousarray(tris).tobytes()), np.float32).reshape(len(tris), 84))
         assert t.data_ptr() % 16 == 0
         return be.update_triangles_device(t.data_ptr(), len(tris))
 

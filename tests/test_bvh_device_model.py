@@ -7,7 +7,6 @@ else.  And ptmi_bvh_create_device must refuse a missing device without touching 
 """
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -15,13 +14,12 @@ import pytest
 
 from opencl_pathtracer_amd import backend, scenes, bvh_create, structs as S, PtmiError
 import bvh_stress_cases as stress
+import model_build
 import test_bvh
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODEL_SRC = os.path.join(ROOT, "tests", "bvh_device_model.cpp")
-INCLUDES = ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "opencl_pathtracer_amd", "csrc")]
-# g++ contracts a*b+c into an FMA unless told not to: the numerics of the host builder forbid it
-FP_FLAGS = ["-ffp-contract=off", "-fno-fast-math"]
+INCLUDES = [os.path.join(ROOT, "include"), os.path.join(ROOT, "opencl_pathtracer_amd", "csrc")]
 
 FUZZ_NAMES = [f"fuzz{seed}{suffix}_l1" for seed in range(0, 58, 3) for suffix in ("", "h", "r", "hr")]
 WALL_SEEDS = range(40)
@@ -94,14 +92,8 @@ def host_build(tris):
 
 
 def build_model(tmp_dir):
-    gxx = shutil.which("g++")
-    if not gxx:
-        pytest.skip("g++ not installed")
-    so = str(tmp_dir / "libbvh_model.so")
-    r = subprocess.run([gxx, "-std=c++17", "-O2", "-fPIC", "-shared", *FP_FLAGS, *INCLUDES, MODEL_SRC, "-o", so],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    lib = C.CDLL(so)
+    # (fp_strict: g++ contracts a*b+c into an FMA unless told not to, and the numerics of the host builder forbid it)
+    lib = C.CDLL(model_build.library([MODEL_SRC], tmp_dir, "libbvh_model.so", opt="-O2", werror=None, fp_strict=True, includes=INCLUDES))
     lib.model_bvh_build_ex.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                        C.c_uint32, C.POINTER(C.c_uint32)]
 
@@ -243,13 +235,7 @@ def test_model_flags_the_stale_splits_of_cloud_and_wall(model, built):
 def test_model_under_sanitizers(tmp_path, built):
     """The model compiled with -fsanitize=address,undefined, run once over the fuzzed scenes, a cloud + wall scene, the signed
     zeros and the small stress cases (the refused chain among them)."""
-    gxx = shutil.which("g++")
-    if not gxx:
-        pytest.skip("g++ not installed")
-    asan = subprocess.run([gxx, "-print-file-name=libasan.so"], capture_output=True, text=True).stdout.strip()
-    ubsan = subprocess.run([gxx, "-print-file-name=libubsan.so"], capture_output=True, text=True).stdout.strip()
-    if not (os.path.isabs(asan) and os.path.exists(asan) and os.path.isabs(ubsan) and os.path.exists(ubsan)):
-        pytest.skip("libasan / libubsan not installed")
+    model_build.sanitizer_runtimes_or_skip()
     main = tmp_path / "main.cpp"
     main.write_text(r'''
 #include <cstdio>
@@ -272,11 +258,9 @@ int main(int argc, char** argv) {
     return 0;
 }
 ''')
-    exe = tmp_path / "model_asan"
-    r = subprocess.run([gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
-                        "-fno-sanitize-recover=undefined", *FP_FLAGS, *INCLUDES, MODEL_SRC, str(main), "-o", str(exe)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
+    # (the strict floating-point flags behind the sanitizers': this program's command line as it has always been)
+    exe = model_build.program([MODEL_SRC, main], tmp_path, "model_asan", opt=["-O1", "-g"], werror=None, sanitize=model_build.SANITIZE,
+                              extra=["-ffp-contract=off", "-fno-fast-math"], includes=INCLUDES)
     files = []
     for i, t in enumerate([scenes.build(nm, 32, 32).triangulation for nm in FUZZ_NAMES[::5]] + [cloud_wall(0), signed_zero_tris()] +
                           [stress.make(*case) for case in stress.SMALL]):

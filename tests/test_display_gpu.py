@@ -30,11 +30,7 @@ def stride_of(w):
     return (3 * w + 3) & ~3
 
 
-def to_device(array):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(array)).cuda()
-    torch.cuda.synchronize()  # (the context's stream is not torch's)
-    return t
+to_device = gpu_cases.tensor_on_device
 
 
 def filled(n_bytes):

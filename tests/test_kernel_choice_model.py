@@ -16,10 +16,11 @@ independently (parent_*, transcriptions), and checks:
 import itertools
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
+
+import model_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "opencl_pathtracer_amd", "csrc")
@@ -36,13 +37,8 @@ ENVIRONMENTS = [dict(([("PTMI_LEAF_CULL", lc)] if lc is not None else []) + ([(s
 
 @pytest.fixture(scope="module")
 def model(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not installed")
-    exe = str(tmp_path_factory.mktemp("kernel_choice") / "kernel_choice_model")
-    subprocess.run([gxx, "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I" + CSRC, "-I" + os.path.join(ROOT, "include"), MODEL_SRC, "-o", exe],
-                   check=True)
-    return exe
+    return model_build.program([MODEL_SRC], tmp_path_factory.mktemp("kernel_choice"), "kernel_choice_model", opt="-O1", werror=True,
+                               includes=[CSRC, os.path.join(ROOT, "include")])
 
 
 def run(model, mode, env=None):

@@ -19,25 +19,21 @@ This file checks, from what the scheduler decided:
 """
 import os
 import random
-import shutil
 import subprocess
 
 import pytest
 
+import model_build
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODEL_SRC = os.path.join(ROOT, "tests", "launch_schedule_model.cpp")
-INCLUDE = "-I" + os.path.join(ROOT, "opencl_pathtracer_amd", "csrc")
+CSRC = os.path.join(ROOT, "opencl_pathtracer_amd", "csrc")
 K_SHORT, K_AHEAD, K_SETS, MAX_CAP = 4, 4, 4, 32
 U32 = 0xFFFFFFFF
 
 
-def _compile(tmp, extra=()):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not installed")
-    exe = str(tmp / "launch_schedule_model")
-    subprocess.run([gxx, "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", *extra, INCLUDE, MODEL_SRC, "-o", exe], check=True)
-    return exe
+def _compile(tmp, sanitize=()):
+    return model_build.program([MODEL_SRC], tmp, "launch_schedule_model", opt="-O1", werror=True, sanitize=sanitize, includes=[CSRC])
 
 
 @pytest.fixture(scope="module")
@@ -454,14 +450,8 @@ def test_invariants_of_the_schedule(played):
 
 def test_model_under_sanitizers(tmp_path):
     """The driver compiled with -fsanitize=address,undefined, over the table of small caps and the random sequences."""
-    gxx = shutil.which("g++")
-    if not gxx:
-        pytest.skip("g++ not installed")
-    asan = subprocess.run([gxx, "-print-file-name=libasan.so"], capture_output=True, text=True).stdout.strip()
-    ubsan = subprocess.run([gxx, "-print-file-name=libubsan.so"], capture_output=True, text=True).stdout.strip()
-    if not (os.path.isabs(asan) and os.path.exists(asan) and os.path.isabs(ubsan) and os.path.exists(ubsan)):
-        pytest.skip("libasan / libubsan not installed")
-    exe = _compile(tmp_path, ["-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-fno-sanitize-recover=undefined"])
+    model_build.sanitizer_runtimes_or_skip()
+    exe = _compile(tmp_path, ["-g", *model_build.SANITIZE])
     env = {**os.environ, "ASAN_OPTIONS": "detect_leaks=1"}
     r = subprocess.run([exe, "table", "8"], capture_output=True, text=True, env=env)
     assert r.returncode == 0 and r.stdout.count("end\n") > 0, r.stderr[-3000:]

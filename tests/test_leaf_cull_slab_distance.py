@@ -9,11 +9,11 @@ negation, and the sign goes in the square - and 0 between.  tests/leaf_cull_slab
 import ctypes as C
 import itertools
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
+
+import model_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "opencl_pathtracer_amd", "csrc")
@@ -23,15 +23,9 @@ FP = C.POINTER(C.c_float)
 
 @pytest.fixture(scope="module")
 def model(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if not gxx:
-        pytest.skip("g++ not installed")
-    so = os.path.join(str(tmp_path_factory.mktemp("leaf_cull_slab_model")), "libleaf_cull_slab_model.so")
-    r = subprocess.run([gxx, "-std=c++17", "-O2", "-fPIC", "-shared", "-Wall", "-ffp-contract=off", "-fno-fast-math",
-                        "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, os.path.join(ROOT, "tests", "leaf_cull_slab_model.cpp"), "-o", so],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    m = C.CDLL(so)
+    folder = tmp_path_factory.mktemp("leaf_cull_slab_model")
+    m = C.CDLL(model_build.library([os.path.join(ROOT, "tests", "leaf_cull_slab_model.cpp")], folder, "libleaf_cull_slab_model.so",
+                                   opt="-O2", werror=False, fp_strict=True, includes=[os.path.join(ROOT, "include"), CSRC]))
     m.slab_box_distance2_bits.argtypes = [FP, FP, FP]
     m.slab_box_distance2_bits.restype = C.c_uint32
     m.slab_from_slabs_bits.argtypes = [FP, FP, FP, C.c_int]

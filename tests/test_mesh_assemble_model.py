@@ -11,7 +11,6 @@ loses the original winding's last bit of N.
 """
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -19,6 +18,7 @@ import pytest
 
 from opencl_pathtracer_amd import PtmiError, backend, scenes, structs as S
 import abi_cases
+import model_build
 import scene_record_cases as R
 import vertex_update_cases as V
 
@@ -215,18 +215,11 @@ def test_a_round_trip_through_the_mesh_keeps_vertices_coordinates_and_box(name):
 
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if not gxx:
-        pytest.skip("g++ not installed")
-    asan = subprocess.run([gxx, "-print-file-name=libasan.so"], capture_output=True, text=True).stdout.strip()
-    ubsan = subprocess.run([gxx, "-print-file-name=libubsan.so"], capture_output=True, text=True).stdout.strip()
-    if not (os.path.isabs(asan) and os.path.exists(asan) and os.path.isabs(ubsan) and os.path.exists(ubsan)):
-        pytest.skip("libasan / libubsan not installed")
+    model_build.sanitizer_runtimes_or_skip()
     tmp = tmp_path_factory.mktemp("mesh_assemble")
-    exe = str(tmp / "mesh_assemble_model")
-    subprocess.run([gxx, "-std=c++17", "-O1", "-g", "-Wall", "-ffp-contract=off", "-fno-fast-math", "-fsanitize=address,undefined",
-                    "-fno-omit-frame-pointer", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
-                    os.path.join(ROOT, "tests", "mesh_assemble_model.cpp"), "-o", exe], check=True)
+    exe = model_build.program([os.path.join(ROOT, "tests", "mesh_assemble_model.cpp")], tmp, "mesh_assemble_model",
+                              opt=["-O1", "-g"], werror=False, fp_strict=True,
+                              sanitize=model_build.SANITIZE, includes=[os.path.join(ROOT, "include"), CSRC])
 
     def run(blocks):
         """blocks: (mesh, stride) -> the records of every block, one array each"""

@@ -1,7 +1,8 @@
 """The node trip of the culling instantiations after its diet ("The node step's diet"; kernel_wavefront.hip:
-cull_step): the static instruction counts of the node-trip path - loop header to back edge, as tools/kernel_resources.py:
-trip_loop_copies counts them from the assembly hipcc makes (it cross-compiles without a GPU) - stay at or below what the change
-reached, the flagship's within the issue's 158 vector / 100 scalar, and the leaf-pass path is not above what it was.
+cull_step): the static instruction counts of the node-trip path - loop header to back edge, as the resource tool's
+parsing counts them (through tests/kernel_figures.py) from the assembly hipcc makes (it cross-compiles without a GPU) - stay at
+or below what the change reached, the flagship's within the issue's 158 vector / 100 scalar, and the leaf-pass path is not above
+what it was.
 
 NODE_TRIP: (vector, scalar) per instantiation, [strict, default].  The parent's figures: plain 170 / 104, general 180 / 104.
 The general instantiation of 256 lanes (01000c) keeps the parent's step: under the counting step the allocator spills more of it
@@ -14,15 +15,14 @@ bit for bit, and certified_and_beyond_wide is "bit 0 set and box_is_beyond_wide"
 """
 import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_figures as K
+import model_build
+
+ROOT = K.ROOT
 
 NODE_TRIP = {
     "01010c": [(157, 100), (156, 100)],     # <- the flagship's kernel (default arithmetic)
@@ -33,38 +33,28 @@ NODE_TRIP = {
 LEAF_PASS = [(151, 108), (146, 108)]  # plain culling instantiations, the parent's figures
 FLAGSHIP_BOUND = (158, 100)
 
-_cfg = {}
 
-
-def figures(arithmetic):
-    if arithmetic not in _cfg:
-        import kernel_resources as R
-        path, _ = R.compile_to_assembly(ROOT, arithmetic)
-        _cfg[arithmetic] = {key: R.trip_loop_copies(blocks) for key, blocks in R.kernel_cfg(path).items()}
-    return _cfg[arithmetic]
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@K.needs_hipcc
 @pytest.mark.parametrize("arithmetic", [0, 1], ids=["strict", "default"])
 def test_node_trip_counts_stay_where_the_diet_left_them(arithmetic):
-    found = figures(arithmetic)
+    found = K.trip_loops(arithmetic)
     for key, pinned in sorted(NODE_TRIP.items()):
         vector, scalar = found[key]["node trip"]
         print(key, "node trip", (vector, scalar), "pinned", pinned[arithmetic])
         assert vector <= pinned[arithmetic][0] and scalar <= pinned[arithmetic][1], (key, (vector, scalar), pinned[arithmetic])
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@K.needs_hipcc
 def test_flagship_is_within_the_issues_bound():
-    vector, scalar = figures(1)["01010c"]["node trip"]
+    vector, scalar = K.trip_loops(1)["01010c"]["node trip"]
     assert vector <= FLAGSHIP_BOUND[0] and scalar <= FLAGSHIP_BOUND[1], (vector, scalar)
     assert 170 - vector >= 12 and 104 - scalar >= 4, (vector, scalar)  # (the issue's target, from the parent's 170 / 104)
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@K.needs_hipcc
 @pytest.mark.parametrize("arithmetic", [0, 1], ids=["strict", "default"])
 def test_leaf_pass_path_is_not_above_what_it_was(arithmetic):
-    found = figures(arithmetic)
+    found = K.trip_loops(arithmetic)
     for key in ("01010c", "01010b64c"):
         vector, scalar = found[key]["leaf pass"]
         print(key, "leaf pass", (vector, scalar))
@@ -86,16 +76,12 @@ void diet_constants(float* out) { out[0] = ptmi_cull::kRelWide; out[1] = ptmi_cu
 @pytest.fixture(scope="module")
 def model(tmp_path_factory):
     """csrc/leaf_cull.h compiled for the host with -ffp-contract=off, as the library is."""
-    import shutil
-    if shutil.which("g++") is None:
-        pytest.skip("g++ not installed")
     folder = tmp_path_factory.mktemp("node_step_diet_model")
-    src, lib = os.path.join(folder, "diet_model.cpp"), os.path.join(folder, "libdiet_model.so")
+    src = os.path.join(folder, "diet_model.cpp")
     with open(src, "w") as f:
         f.write(MODEL_SRC)
-    subprocess.run(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"),
-                    "-I" + os.path.join(ROOT, "opencl_pathtracer_amd", "csrc"), src, "-o", lib], check=True)
-    m = C.CDLL(lib)
+    m = C.CDLL(model_build.library([src], folder, "libdiet_model.so", opt="-O2", werror=None, extra=["-ffp-contract=off"],
+                                   includes=[os.path.join(ROOT, "include"), os.path.join(ROOT, "opencl_pathtracer_amd", "csrc")]))
     m.diet_threshold.restype = m.diet_fmaf.restype = C.c_float
     m.diet_threshold.argtypes = m.diet_fmaf.argtypes = [C.c_float]
     m.diet_beyond.argtypes = [C.c_float, C.c_float]

@@ -5,21 +5,16 @@ box test reads quads a and b, the second b and c, and quad d (child references, 
 the compiler places must follow that: vmcnt(3), (2), (1), and vmcnt(0) only where quad d is read.  They did not while the
 kernel held flat_ instructions in path logic (a generic pointer to the scene's rare fields): with a flat operation possibly
 pending, the first wait behind the loads waited for all four.  Read from the assembly hipcc makes of kernel_wavefront.hip
-(it cross-compiles without a GPU), with the parsing of tools/kernel_resources.py, for every production instantiation in
+(it cross-compiles without a GPU), with the parsing tests/kernel_figures.py shares, for every production instantiation in
 both arithmetics.
 
 "Before the block ends": the compiler ends the basic block of the loads at the branch between the ordered and the literal box
 test, so the waits are followed in layout order through the blocks of the traversal loop that come next, up to the first that
 carries vmcnt(0) - which must stand before the loop issues another vector memory load (the leaf pass's) or ends.
 """
-import os
-import sys
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_figures as K
 
 # STATS PRE SS PLAIN NANSAFE [b64: workgroups of 64 lanes] [c: culls leaves] - the instantiations instance_for() launches
 # without scheduler statistics and without SUPER_SAMPLING (tests/test_resources.py names the same set, before culling)
@@ -27,28 +22,17 @@ PRODUCTION = {"00000", "00001", "01000", "01001", "01010", "01011", "01000b64", 
 # every instantiation reads the rare scene fields through a global pointer: none got the fence instead
 CAUSE_REMOVED = PRODUCTION
 
-_blocks = {}
-
-
-def blocks(arithmetic):
-    if arithmetic not in _blocks:
-        import kernel_resources as R
-        path, _ = R.compile_to_assembly(ROOT, arithmetic)
-        _blocks[arithmetic] = R.kernel_blocks(path)
-    return _blocks[arithmetic]
-
 
 def waits_behind_the_loads(kernel):
-    import kernel_resources as R
-    found = R.node_step_waits(kernel)
+    found = K.node_step_waits(kernel)
     assert found is not None, "no block of the traversal loop loads four quads from one address"
     return found
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@K.needs_hipcc
 @pytest.mark.parametrize("arithmetic", [0, 1], ids=["strict", "default"])
 def test_node_step_waits_for_its_quads_one_by_one(arithmetic):
-    kernels = blocks(arithmetic)
+    kernels = K.blocks(arithmetic)
     assert PRODUCTION <= set(kernels), sorted(kernels)
     for key in sorted(PRODUCTION):
         offsets, waits, found = waits_behind_the_loads(kernels[key])
@@ -60,13 +44,13 @@ def test_node_step_waits_for_its_quads_one_by_one(arithmetic):
         assert len(waits) >= 2, (key, waits)  # (the list ends at the first vmcnt(0): it is not the first wait)
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@K.needs_hipcc
 @pytest.mark.parametrize("arithmetic", [0, 1], ids=["strict", "default"])
 def test_no_flat_instruction_in_or_before_the_traversal_loop(arithmetic):
     """Where the cause was removed: no flat_ instruction in the traversal loop (the depth-2 blocks), in the path-logic loop around
     it, or in front of the loops.  (As built, the kernels hold none at all; what follows the loops - the counter flush - is not
     a path into them and is left free.)"""
-    kernels = blocks(arithmetic)
+    kernels = K.blocks(arithmetic)
     for key in sorted(CAUSE_REMOVED):
         kernel = kernels[key]
         last_loop = max(i for i, (depth, _) in enumerate(kernel) if depth > 0)

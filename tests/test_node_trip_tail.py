@@ -1,6 +1,6 @@
 """The node trip's tail of the wavefront kernel, read off the assembly ("The node trip's tail").
 
-hipcc cross-compiles kernel_wavefront.hip without a GPU; tools/kernel_resources.py: trip_loop_copies reads the whole trip,
+hipcc cross-compiles kernel_wavefront.hip without a GPU; the resource tool's parsing (through tests/kernel_figures.py) reads the whole trip,
 node_trip_tail the node-trip path from the step's push (the ds_write_b32 behind the record loads) to the back edge.
 
 CHOICE: the instantiations whose trip's kind is the step's exec mask (plain shading, culling, or 64 lanes; the statistics builds
@@ -17,14 +17,9 @@ PARENT: the parent commit's figures, [strict, default] = ((VGPRs, spilled, scrat
 scalar, leaf pass vector, scalar, copies in, full waits in, copies out), (tail: LDS reads, read points, waits with lgkmcnt(0),
 vector, scalar)).
 """
-import os
-import sys
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_figures as K
 
 PARENT = {
     "00000": [((96, 58, 108), (70, 141, 93, 221, 123, 6, 1, 8), (2, 1, 2, 29, 36)),
@@ -66,22 +61,13 @@ ALONE = set(PARENT) - CHOICE
 SCALAR = {"01010": (74, 95), "01010b64": (74, 95), "01011": (74, 105), "01010c": (87, 95), "01010b64c": (87, 95),
           "01000b64": (75, 95), "01000b64c": (87, 95), "01000c": (91, 95)}
 
-_res = {}
-
 
 def figures(arithmetic):
-    if arithmetic not in _res:
-        import kernel_resources as R
-        found = R.resources(ROOT, arithmetic)
-        _res[arithmetic] = {key: ((v["VGPRs"], v["VGPRs Spill"], v["ScratchSize"]), tuple(map(int, R.trip_loop_text(v["trip loop"]).split())),
-                                  tuple(v["tail"].values())) for key, v in found.items()}
-    return _res[arithmetic]
+    return {key: ((v["VGPRs"], v["VGPRs Spill"], v["ScratchSize"]), tuple(map(int, K.trip_loop_text(v["trip loop"]).split())),
+                  tuple(v["tail"].values())) for key, v in K.resources(arithmetic).items()}
 
 
-needs_hipcc = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-
-
-@needs_hipcc
+@K.needs_hipcc
 @pytest.mark.parametrize("arithmetic", [0, 1], ids=["strict", "default"])
 def test_the_trip_choice_takes_scalar_instructions_out_of_both_kinds_of_trip(arithmetic):
     found = figures(arithmetic)
@@ -98,7 +84,7 @@ def test_the_trip_choice_takes_scalar_instructions_out_of_both_kinds_of_trip(ari
         assert tail[:4] == p_tail[:4] and tail[4] < p_tail[4], (key, tail, p_tail)  # the stack's reads and waits behind the push: the parent's
 
 
-@needs_hipcc
+@K.needs_hipcc
 @pytest.mark.parametrize("arithmetic", [0, 1], ids=["strict", "default"])
 def test_every_instantiation_left_alone_is_the_parents(arithmetic):
     found = figures(arithmetic)

@@ -3,9 +3,9 @@
 A pass of the wavefront kernel fetched its launch constants - the camera, the sky's rotation, the one light of the plain
 instantiations - with vector loads: one address for the whole wave, fetched by every active lane, each a round trip of its own
 through the L1 queue the traversal keeps full.  They are scalar loads now (ptmi_device.hpp: as_constant).  Counted per production
-instantiation, in both arithmetics, by tools/kernel_resources.py over the body of the outer loop (the depth-1 blocks of the
-assembly hipcc makes of kernel_wavefront.hip; it cross-compiles without a GPU): vector loads from memory, scalar loads, and waits
-that let no vector memory operation stay outstanding.
+instantiation, in both arithmetics, by the resource tool's parsing (through tests/kernel_figures.py) over the body of the outer
+loop (the depth-1 blocks of the assembly hipcc makes of kernel_wavefront.hip; it cross-compiles without a GPU): vector loads from
+memory, scalar loads, and waits that let no vector memory operation stay outstanding.
 
 PARENT holds the same tool's figures for the parent commit (recorded in profiles/path_logic_constants_ab.txt), PINNED the
 figures of this tree, which are upper bounds from now on, as the spill budgets of tests/test_resources.py are.
@@ -16,14 +16,9 @@ the camera (four dwordx4): NINE.  (The two other loads of the sky branch - the h
 have addresses of the lane's own: they stay vector loads.)  The general instantiations index their lights per lane and lose
 five: the rotation and the camera.
 """
-import os
-import sys
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_figures as K
 
 # STATS PRE SS PLAIN NANSAFE [b64] [c] (tests/test_node_step_waits.py: PRODUCTION) ->
 # (VGPRs, spilled VGPRs, static LDS bytes, vector loads, scalar loads, full vector-memory waits of the pass); key: arithmetic
@@ -46,19 +41,13 @@ PINNED = {
 FLAGSHIP = "01010c"  # bench.py's kernel: precomputed records, plain shading, culling, 256 lanes
 UNIFORM_LOADS_PLAIN, UNIFORM_LOADS_GENERAL = 9, 5
 
-_figures = {}
-
 
 def figures(arithmetic):
-    if arithmetic not in _figures:
-        from kernel_resources import resources
-        res = resources(ROOT, arithmetic)
-        _figures[arithmetic] = {k: (v["VGPRs"], v["VGPRs Spill"], v["LDS Size"], v["pass vector loads"], v["pass scalar loads"], v["pass full waits"])
-                                for k, v in res.items()}
-    return _figures[arithmetic]
+    return {k: (v["VGPRs"], v["VGPRs Spill"], v["LDS Size"], v["pass vector loads"], v["pass scalar loads"], v["pass full waits"])
+            for k, v in K.resources(arithmetic).items()}
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@K.needs_hipcc
 @pytest.mark.parametrize("arithmetic", [0, 1], ids=["strict", "default"])
 def test_the_pass_keeps_its_memory_counts(arithmetic):
     got = figures(arithmetic)
@@ -69,7 +58,7 @@ def test_the_pass_keeps_its_memory_counts(arithmetic):
             assert now <= bound, (key, name, now, bound)
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@K.needs_hipcc
 @pytest.mark.parametrize("arithmetic", [0, 1], ids=["strict", "default"])
 def test_the_uniform_loads_left_the_vector_memory_queue(arithmetic):
     got, parent = figures(arithmetic), PARENT[arithmetic]
@@ -81,7 +70,7 @@ def test_the_uniform_loads_left_the_vector_memory_queue(arithmetic):
         assert got[key][4] >= 1, (key, got[key])  # (something IS fetched by scalar loads: the counts did not fall by dead code)
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@K.needs_hipcc
 @pytest.mark.parametrize("arithmetic", [0, 1], ids=["strict", "default"])
 def test_no_production_instantiation_pays_in_registers_spills_or_lds(arithmetic):
     got = figures(arithmetic)

@@ -20,20 +20,17 @@ import subprocess
 import numpy as np
 import pytest
 
+import model_build
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODEL_SRC = os.path.join(ROOT, "tests", "render_region_model.cpp")
-INCLUDE = "-I" + os.path.join(ROOT, "opencl_pathtracer_amd", "csrc")
+CSRC = os.path.join(ROOT, "opencl_pathtracer_amd", "csrc")
 ALL_43x29 = (43 * 44 // 2) * (29 * 30 // 2)
 SHARES = 6
 
 
-def _compile(tmp, name, extra=()):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not installed")
-    exe = str(tmp / name)
-    subprocess.run([gxx, "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", *extra, INCLUDE, MODEL_SRC, "-o", exe], check=True)
-    return exe
+def _compile(tmp, name, sanitize=()):
+    return model_build.program([MODEL_SRC], tmp, name, opt="-O2", werror=True, sanitize=sanitize, includes=[CSRC])
 
 
 @pytest.fixture(scope="module")
@@ -84,13 +81,9 @@ def test_the_model_under_the_sanitizers(tmp_path):
 
 def test_the_header_needs_no_hip_and_nothing_else_of_the_library(tmp_path):
     """render_region.h alone, by g++: what lets the model above be the kernels' own copy"""
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not installed")
     src = tmp_path / "alone.cpp"
     src.write_text('#include "render_region.h"\nint main() { return ptmi_internal::region_tiles(ptmi_internal::whole_image(43, 29)) == 24u ? 0 : 1; }\n')
-    subprocess.run([gxx, "-std=c++17", "-Wall", "-Wextra", "-Werror", INCLUDE, str(src), "-o", str(tmp_path / "alone")], check=True)
-    assert subprocess.run([str(tmp_path / "alone")]).returncode == 0
+    assert subprocess.run([model_build.program([src], tmp_path, "alone", opt=(), werror=True, includes=[CSRC])]).returncode == 0
 
 
 def test_the_binding():

@@ -30,11 +30,7 @@ def assert_equal(got, want):
     assert not msg, msg
 
 
-def to_device(array):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(array)).cuda()
-    torch.cuda.synchronize()  # (the context's stream is not torch's)
-    return t
+to_device = gpu_cases.tensor_on_device
 
 
 def empty_result(w, h):

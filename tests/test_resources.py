@@ -1,14 +1,9 @@
 """Register / LDS budget of the shipped wavefront-kernel specialisation, read from hipcc's resource remarks (cross-compiles
 without a GPU).  The kernel's speed hangs on 5 waves per SIMD (96 VGPRs) with no scratch traffic inside the traversal
 loop; hipcc's register allocation is fragile, so an innocent-looking edit can cost a wave of occupancy."""
-import os
-import re
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
+import kernel_figures as K
 
 
 # spilled registers: a regression budget per production specialisation (general shading, plain shading).  The plain-scene
@@ -19,13 +14,10 @@ HIPCC = "/opt/rocm/bin/hipcc"
 SPILL_BUDGET = {"general": 72, "plain": 8}
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@K.needs_hipcc
 @pytest.mark.parametrize("arithmetic", [0, 1])
 def test_wavefront_kernel_keeps_five_waves_per_simd(arithmetic):
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    from kernel_resources import resources
-    res = resources(ROOT, arithmetic)  # key = STATS PRE SS PLAIN NANSAFE as five 0/1 digits
+    res = K.resources(arithmetic)  # key = STATS PRE SS PLAIN NANSAFE as five 0/1 digits
     # the production specialisations: no scheduler statistics, no adaptive sampling; precomputed triangles or not, general /
     # plain shading, with / without the NaN check of scenes whose records yield NaN distances
     # ("01000b64", "01010b64": the two production kernels with workgroups of 64 lanes, launched where the tree's depth leaves a CU

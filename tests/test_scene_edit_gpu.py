@@ -86,10 +86,7 @@ def plain_now(be):
 
 
 def on_device(tris):
-    import torch
-    words = np.frombuffer(bytearray(np.ascontiguousarray(tris).tobytes()), np.float32).reshape(len(tris), 84)
-    t = torch.from_numpy(words).cuda()
-    torch.cuda.synchronize()  # (the context's stream is not torch's)
+    t = gpu_cases.tensor_on_device(np.frombuffer(bytearray(np.ascontiguousarray(tris).tobytes()), np.float32).reshape(len(tris), 84))
     assert t.data_ptr() % 16 == 0
     return t
 

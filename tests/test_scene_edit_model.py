@@ -9,7 +9,6 @@ combination of materials, lights and the PTMI_GENERIC_SHADING switch.
 """
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -17,6 +16,7 @@ import pytest
 
 from opencl_pathtracer_amd import backend, structs as S
 import abi_cases
+import model_build
 import scene_edit_cases as E
 
 ROOT = abi_cases.ROOT
@@ -63,18 +63,10 @@ def test_a_null_context_is_an_invalid_argument(built):
 
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if not gxx:
-        pytest.skip("g++ not installed")
-    asan = subprocess.run([gxx, "-print-file-name=libasan.so"], capture_output=True, text=True).stdout.strip()
-    ubsan = subprocess.run([gxx, "-print-file-name=libubsan.so"], capture_output=True, text=True).stdout.strip()
-    if not (os.path.isabs(asan) and os.path.exists(asan) and os.path.isabs(ubsan) and os.path.exists(ubsan)):
-        pytest.skip("libasan / libubsan not installed")
+    model_build.sanitizer_runtimes_or_skip()
     tmp = tmp_path_factory.mktemp("material_screen")
-    exe = str(tmp / "material_screen_model")
-    subprocess.run([gxx, "-std=c++17", "-O1", "-g", "-Wall", "-ffp-contract=off", "-fno-fast-math", "-fsanitize=address,undefined",
-                    "-fno-omit-frame-pointer", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
-                    *SOURCES, "-o", exe], check=True)
+    exe = model_build.program(SOURCES, tmp, "material_screen_model", opt=["-O1", "-g"], werror=False, fp_strict=True,
+                              sanitize=model_build.SANITIZE, includes=[os.path.join(ROOT, "include"), CSRC])
 
     def run(*args):
         env = {k: v for k, v in os.environ.items() if k != "PTMI_GENERIC_SHADING"}

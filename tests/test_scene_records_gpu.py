@@ -30,10 +30,7 @@ RECORD_FORMS = [pytest.param(False, id="precomputed"), pytest.param(True, id="ge
 
 @pytest.fixture(scope="module", autouse=True)
 def tools():
-    if R.model() is None:
-        pytest.fail("oracle/build/libscene_refit_model.so not built (make -C oracle probe)", pytrace=False)
-    if R.probe() is None:
-        pytest.fail("oracle/build/libscene_record_probe.so not built (make -C oracle probe)", pytrace=False)
+    gpu_cases.require_probe_tools()
 
 
 def context(sc, **kw):

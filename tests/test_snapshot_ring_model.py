@@ -20,27 +20,23 @@ event for event.  The same sequences run once more through the model built with 
 """
 import os
 import random
-import shutil
 import subprocess
 from collections import Counter
 
 import pytest
 
+import model_build
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODEL_SRC = os.path.join(ROOT, "tests", "snapshot_ring_model.cpp")
-INCLUDES = ["-I" + os.path.join(ROOT, "opencl_pathtracer_amd", "csrc"), "-I" + os.path.join(ROOT, "include")]
+INCLUDES = [os.path.join(ROOT, "opencl_pathtracer_amd", "csrc"), os.path.join(ROOT, "include")]
 RING = 65  # PTMI_MAX_SNAPSHOT_SLOTS
 USER_SLOTS = RING - 1
 INTERNAL = RING - 1
 
 
-def _compile(tmp, extra=()):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not installed")
-    exe = str(tmp / "snapshot_ring_model")
-    subprocess.run([gxx, "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", *extra, *INCLUDES, MODEL_SRC, "-o", exe], check=True)
-    return exe
+def _compile(tmp, sanitize=()):
+    return model_build.program([MODEL_SRC], tmp, "snapshot_ring_model", opt="-O1", werror=True, sanitize=sanitize, includes=INCLUDES)
 
 
 def device_share(first, n, k, G):
@@ -275,13 +271,7 @@ def test_invariants_of_the_ring(played):
 
 def test_model_under_sanitizers(tmp_path, parent):
     """The model compiled with -fsanitize=address,undefined as a program of its own, over the same sequences."""
-    gxx = shutil.which("g++")
-    if not gxx:
-        pytest.skip("g++ not installed")
-    asan = subprocess.run([gxx, "-print-file-name=libasan.so"], capture_output=True, text=True).stdout.strip()
-    ubsan = subprocess.run([gxx, "-print-file-name=libubsan.so"], capture_output=True, text=True).stdout.strip()
-    if not (os.path.isabs(asan) and os.path.exists(asan) and os.path.isabs(ubsan) and os.path.exists(ubsan)):
-        pytest.skip("libasan / libubsan not installed")
-    exe = _compile(tmp_path, ["-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-fno-sanitize-recover=undefined"])
+    model_build.sanitizer_runtimes_or_skip()
+    exe = _compile(tmp_path, ["-g", *model_build.SANITIZE])
     r = subprocess.run([exe], input="\n".join(SEQUENCES) + "\n", capture_output=True, text=True, env={**os.environ, "ASAN_OPTIONS": "detect_leaks=1"})
     assert r.returncode == 0 and r.stdout.splitlines() == parent, r.stderr[-3000:]

@@ -6,8 +6,8 @@ step leaves - p_bbx, p_tri, tri_end, tri_i, cur, sp - reached that block as PHIs
 trip began with a full vmcnt(0) and five to seven v_mov into temporaries and ended with five to ten v_mov back, under the full
 exec mask.  With the kind as the step's exec mask (kernel_wavefront.hip: kMaskedStep) the step works on the home registers.
 
-Read from the assembly hipcc makes of kernel_wavefront.hip (it cross-compiles without a GPU) with tools/kernel_resources.py:
-trip_loop_copies, for every production instantiation in both arithmetics:
+Read from the assembly hipcc makes of kernel_wavefront.hip (it cross-compiles without a GPU) with the resource tool's
+parsing (through tests/kernel_figures.py: trip_loops), for every production instantiation in both arithmetics:
   - the way IN - the node-trip path from the loop header to the step's first record load - holds no v_mov between two vector
     registers (and no full vector-memory wait: there is nothing the step's address waits for);
   - the way OUT - from the step's last LDS operation to the back edge - holds none either;
@@ -24,14 +24,9 @@ Two exceptions, named here:
     (cur <- tos) and the refill reaches tos through the register the LDS read returns in: two v_mov behind the last LDS
     operation, a third where a culled leaf pops twice.  Pinned at that; the way in holds none, as everywhere.
 """
-import os
-import sys
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_figures as K
 
 # STATS PRE SS PLAIN NANSAFE [b64: workgroups of 64 lanes] [c: culls leaves]: tests/test_node_step_waits.py's set
 PRODUCTION = {"00000", "00001", "01000", "01001", "01010", "01011", "01000b64", "01010b64", "01000c", "01010c", "01000b64c", "01010b64c"}
@@ -55,21 +50,11 @@ V_MOV = {
     "01011": [43, 43],      # parent 55, 55
 }
 
-_cfg = {}
 
-
-def figures(arithmetic):
-    if arithmetic not in _cfg:
-        import kernel_resources as R
-        path, _ = R.compile_to_assembly(ROOT, arithmetic)
-        _cfg[arithmetic] = {key: R.trip_loop_copies(blocks) for key, blocks in R.kernel_cfg(path).items()}
-    return _cfg[arithmetic]
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@K.needs_hipcc
 @pytest.mark.parametrize("arithmetic", [0, 1], ids=["strict", "default"])
 def test_node_trip_updates_the_cursor_in_place(arithmetic):
-    found = figures(arithmetic)
+    found = K.trip_loops(arithmetic)
     assert PRODUCTION <= set(found), sorted(found)
     for key in sorted(PRODUCTION - OLD_FORM):
         t = found[key]
@@ -84,10 +69,10 @@ def test_node_trip_updates_the_cursor_in_place(arithmetic):
             assert t["copies out"] == [], (key, t["copies out"])
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@K.needs_hipcc
 @pytest.mark.parametrize("arithmetic", [0, 1], ids=["strict", "default"])
 def test_loop_v_mov_count_and_no_scratch(arithmetic):
-    found = figures(arithmetic)
+    found = K.trip_loops(arithmetic)
     for key in sorted(PRODUCTION):
         t = found[key]
         print(key, t["loop v_mov"], t["loop scratch"], "node trip", t["node trip"], "leaf pass", t["leaf pass"])
@@ -96,10 +81,10 @@ def test_loop_v_mov_count_and_no_scratch(arithmetic):
         assert t["loop scratch"] <= (3 if key == "00001" and arithmetic == 0 else 0), (key, t["loop scratch"])
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+@K.needs_hipcc
 @pytest.mark.parametrize("arithmetic", [0, 1], ids=["strict", "default"])
 def test_old_form_is_what_it_was(arithmetic):
     """The instantiations that keep the branch still show what the others lost: the measure sees the copies."""
     for key in sorted(OLD_FORM):
-        t = figures(arithmetic)[key]
+        t = K.trip_loops(arithmetic)[key]
         assert len(t["copies in"]) >= 5 and t["full waits in"] == 1 and len(t["copies out"]) >= 5, (key, t)

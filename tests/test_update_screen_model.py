@@ -10,13 +10,13 @@ scene_record_cases.py) still say what they said on the cases that reach them.
 """
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 from opencl_pathtracer_amd import PtmiError, backend, structs as S
+import model_build
 import scene_record_cases as R
 import update_screen_cases as X
 
@@ -29,18 +29,10 @@ WHOLE = ["cornell", "feat_textured", "signed_zero-s0", "tris20k"]
 
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if not gxx:
-        pytest.skip("g++ not installed")
-    asan = subprocess.run([gxx, "-print-file-name=libasan.so"], capture_output=True, text=True).stdout.strip()
-    ubsan = subprocess.run([gxx, "-print-file-name=libubsan.so"], capture_output=True, text=True).stdout.strip()
-    if not (os.path.isabs(asan) and os.path.exists(asan) and os.path.isabs(ubsan) and os.path.exists(ubsan)):
-        pytest.skip("libasan / libubsan not installed")
+    model_build.sanitizer_runtimes_or_skip()
     tmp = tmp_path_factory.mktemp("update_screen")
-    exe = str(tmp / "update_screen_model")
-    subprocess.run([gxx, "-std=c++17", "-O1", "-g", "-Wall", "-ffp-contract=off", "-fno-fast-math", "-fsanitize=address,undefined",
-                    "-fno-omit-frame-pointer", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
-                    *SOURCES, "-o", exe], check=True)
+    exe = model_build.program(SOURCES, tmp, "update_screen_model", opt=["-O1", "-g"], werror=False, fp_strict=True,
+                              sanitize=model_build.SANITIZE, includes=[os.path.join(ROOT, "include"), CSRC])
 
     def run(blocks):
         """blocks: (triangles, facts) -> per block (word, status, message)"""

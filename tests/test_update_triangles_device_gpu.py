@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from opencl_pathtracer_amd import Backend, PtmiError, backend
-from gpu_cases import assert_same_state, state
+from gpu_cases import assert_same_state, bytes_of, state
 import gpu_cases
 import scene_record_cases as R
 import scene_update_cases as U
@@ -27,10 +27,7 @@ HOST, DEVICE = "ptmi_update_triangles: ", "ptmi_update_triangles_device: "
 
 @pytest.fixture(scope="module", autouse=True)
 def tools():
-    if R.model() is None:
-        pytest.fail("oracle/build/libscene_refit_model.so not built (make -C oracle probe)", pytrace=False)
-    if R.probe() is None:
-        pytest.fail("oracle/build/libscene_record_probe.so not built (make -C oracle probe)", pytrace=False)
+    gpu_cases.require_probe_tools()
 
 
 def context(sc, **kw):
@@ -39,18 +36,9 @@ def context(sc, **kw):
 
 def on_device(tris):
     """The records as a float32 (n, 84) torch tensor on the device (a byte copy: the payload of a NaN travels as it is)"""
-    import torch
-    words = np.frombuffer(bytearray(np.ascontiguousarray(tris).tobytes()), np.float32).reshape(len(tris), 84)
-    t = torch.from_numpy(words).cuda()
-    torch.cuda.synchronize()  # (the context's stream is not torch's)
+    t = gpu_cases.tensor_on_device(np.frombuffer(bytearray(np.ascontiguousarray(tris).tobytes()), np.float32).reshape(len(tris), 84))
     assert t.data_ptr() % 16 == 0
     return t
-
-
-def bytes_of(tensor):
-    import torch
-    torch.cuda.synchronize()
-    return tensor.view(torch.int32).cpu().numpy().tobytes()
 
 
 def update_device(be, tris):

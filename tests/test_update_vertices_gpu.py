@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from opencl_pathtracer_amd import Backend, PtmiError, backend
-from gpu_cases import assert_same_state, state
+from gpu_cases import assert_same_state, bytes_of, state
 import gpu_cases
 import scene_record_cases as R
 import scene_update_cases as U
@@ -32,10 +32,7 @@ f32 = np.float32
 
 @pytest.fixture(scope="module", autouse=True)
 def tools():
-    if R.model() is None:
-        pytest.fail("oracle/build/libscene_refit_model.so not built (make -C oracle probe)", pytrace=False)
-    if R.probe() is None:
-        pytest.fail("oracle/build/libscene_record_probe.so not built (make -C oracle probe)", pytrace=False)
+    gpu_cases.require_probe_tools()
 
 
 def context(sc, **kw):
@@ -44,17 +41,9 @@ def context(sc, **kw):
 
 def on_device(a, stride=12):
     """The (V, 3) array as a float32 (V, stride / 4) torch tensor on the device, NaN in every word of padding"""
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(V.padded(a, stride).base)).cuda()
-    torch.cuda.synchronize()  # (the context's stream is not torch's)
+    t = gpu_cases.tensor_on_device(V.padded(a, stride).base)
     assert t.data_ptr() % 16 == 0
     return t
-
-
-def bytes_of(tensor):
-    import torch
-    torch.cuda.synchronize()
-    return tensor.view(torch.int32).cpu().numpy().tobytes()
 
 
 def update_device(be, m, stride=12):
@@ -495,9 +484,8 @@ def test_records_form_vertex_form_host_records_form_on_one_context():
     be = context(sc)
     try:
         be.bind_mesh(V.derived("tris20k"))
-        import torch  # (the records form reads a torch tensor of the 336-byte records)
-        t = torch.from_numpy(np.frombuffer(bytearray(tris1.tobytes()), f32).reshape(len(tris1), 84)).cuda()
-        torch.cuda.synchronize()
+        # (the records form reads a torch tensor of the 336-byte records)
+        t = gpu_cases.tensor_on_device(np.frombuffer(bytearray(tris1.tobytes()), f32).reshape(len(tris1), 84))
         be.update_triangles_device(t.data_ptr(), len(tris1))
         assert_holds(be, wants[0], "after the records form")
         update_device(be, the_motion("tris20k"))

@@ -241,7 +241,11 @@ def node_trip_tail(blocks):
 def resources(tree=ROOT, arithmetic=1, extra=(), region_forms=False):
     """region_forms: also the forms that render a rectangle (key suffix r).  Without them the keys are those of before regions
     existed: every launch of ptmi_render runs one of these, and the tests that pin figures name them."""
-    out, remarks = compile_to_assembly(tree, arithmetic, extra)
+    return figures_of(*compile_to_assembly(tree, arithmetic, extra), region_forms=region_forms)
+
+
+def figures_of(out, remarks, region_forms=False):
+    """resources() of an assembly that exists: compile_to_assembly's (path, remarks) -> the dictionary, without compiling"""
     res = {}
     wanted = lambda key: region_forms or not key.endswith("r")
     for block in re.split(r"Function Name: ", remarks)[1:]:
